@@ -1,18 +1,22 @@
 #!/usr/bin/env python
 """bench.py - EDVR hot-path throughput on MI355X, one process per GPU.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--mode infer|train]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--mode infer|train] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N ...
 
 A "step" is one pass of the hot path (EDVR forward, or forward+backward+Adam with --mode train) over one batch of synthetic
 REDS-shaped clips per GPU, inputs resident in HBM before timing.  Clips are independent, so ranks shard them with no data-path
 collective (inference) or with the DDP gradient all-reduce over RCCL (training).  `--gpus N` without a torchrun environment
 re-launches this script as N ranks through torch.distributed.run.  Rank 0 prints ONE JSON line - the COMPACT line (`compact_line`: the
-contract's fields, `roofline` with the measured `traffic`, `cpu_baseline`, `parity` and the headline number of every leg; < 6 KB,
-strict JSON, the last line of stdout) - and writes the full report described below to `bench_full.json` beside this file.
+contract's fields and, with --full, `roofline` with the measured `traffic`, `cpu_baseline`, `parity` and the headline number of every
+leg; < 6 KB, strict JSON, the last line of stdout) - and writes the full report described below to `bench_full.json` beside this file.
 `leg_plan()` says which legs run on which ranks (a leg with barriers runs on every rank or on none).
 
-Objects of the full report besides the contract's fields (everything below runs OUTSIDE the timed region):
+A plain run sets up, warms up, times the K steps and prints the line: the contract's fields and nothing else.  `--full` adds the
+legs below.  `--dump-outputs DIR` writes what the last timed step returned (`dump_outputs`) as DIR/*.npy, for comparing two builds
+output for output: the inputs and weights come from fixed seeds, so they are the same in every run with the same arguments.
+
+Objects of the full report besides the contract's fields (only with --full; everything below runs OUTSIDE the timed region):
   roofline            dominant kernel of the timed step, from an instrumented pass (every launch bracketed by HIP events on the
                       launch stream): `achieved` = flops the matrix cores EXECUTE (MFMA issues x 4096, tile and channel padding
                       included - edvr_conv2d_executed_flops, the quantity SQ_INSTS_VALU_MFMA_MOPS_F32 counts) / time, `frac` =
@@ -109,11 +113,16 @@ DTYPE = ('f32 (3x3 / stride-1 convs and their weight gradients, the tap-window D
          '`fp32_mfma` beside it = the same run with those kernels on the fp32 matrix pipe')
 
 
-def parse():
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
-    ap.add_argument('--steps', type=int, default=10)
+    ap.add_argument('--steps', type=int, default=10, help='timed steps (at least 1)')
     ap.add_argument('--warmup', type=int, default=3)
+    ap.add_argument('--full', action='store_true',
+                    help='also run every leg beside the headline (roofline and kernel table, fp32_mfma, batch4, target_4k, trained_like, '
+                         'configs, train, cpu_baseline + parity, stock_rocm_baseline); the --no-* options below switch single legs off')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last step returned to DIR/<name>.npy (float32 / float64, <= 64 MB)')
     ap.add_argument('--workload', default=None, choices=list(WORKLOADS),
                     help='default: edvr_l_x4_t5_180x320 (infer) / edvr_l_train_t5_64x64 (train)')
     ap.add_argument('--batch', type=int, default=0, help='clips per GPU (default: the workload\'s)')
@@ -130,7 +139,10 @@ def parse():
     ap.add_argument('--train-steps', type=int, default=20)
     ap.add_argument('--no-trained-like', action='store_true', help='headline workload: skip the trained-like-offsets leg')
     ap.add_argument('--no-configs', action='store_true', help='headline workload: skip the other BASELINE configs (`configs` object)')
-    return ap.parse_args()
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
+    return args
 
 
 def build_net(cfg, device, offset_bias_sigma=0.5):
@@ -431,8 +443,9 @@ def make_train_step(net, cfg, batch, device, rank, optimizer, x=None, lr=4e-4):
     return step
 
 
-def timed(step, steps, warmup, dist, device):
-    """W untimed steps, then EXACTLY `steps` steps bracketed by barrier + synchronize on both sides; returns the MAX over ranks."""
+def timed(step, steps, warmup, dist, device, last=None):
+    """W untimed steps, then EXACTLY `steps` steps bracketed by barrier + synchronize on both sides; returns the MAX over ranks.
+    `last` (a list): the last timed step's return value is appended to it."""
     sync = torch.cuda.synchronize if device.type == 'cuda' else (lambda: None)  # (cpu: the world-size-2 gloo test of this function)
     for _ in range(warmup):
         step()
@@ -453,6 +466,8 @@ def timed(step, steps, warmup, dist, device):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     assert torch.isfinite(out).all()
+    if last is not None:
+        last.append(out)
     return elapsed
 
 
@@ -895,11 +910,51 @@ def emit(result, rank, path=None):
     print(compact_line(result), flush=True)
 
 
+DUMP_LIMIT = 64 << 20     # bytes: every file --dump-outputs writes, together
+DUMP_SAMPLE = 1 << 20     # elements of the seeded sample taken from an output too large to write whole
+DUMP_SEED = 0
+
+
+def _seeded_sample(flat, n):
+    """`n` elements of the 1-D tensor `flat` at sorted positions drawn from a fixed seed (the same in every run), and the positions."""
+    idx = torch.randint(flat.numel(), (n,), generator=torch.Generator().manual_seed(DUMP_SEED)).sort().values
+    return flat[idx.to(flat.device)], idx
+
+
+def dump_outputs(directory, out, net, mode):
+    """Write what the last timed step returned to `directory` as .npy files (float32; sample positions float64), <= DUMP_LIMIT bytes.
+    infer: `output` = the batch of restored clips (N, 3, H, W) if it fits, else `output_clip0` (the first clip, whole) +
+    `output_sample` (DUMP_SAMPLE elements of the whole batch at seeded positions) + `output_sample_index` (their flat indices).
+    train: `loss` (the step's return value) + `params_sample` / `params_sample_index` (the parameters the step updated, concatenated in
+    named_parameters() order, at seeded positions).  Returns {name: shape}."""
+    import numpy as np
+    arrays = {}
+    if mode == 'train':
+        arrays['loss'] = out.detach().float().reshape(1)
+        flat = torch.cat([p.detach().reshape(-1) for _, p in net.named_parameters()])
+        arrays['params_sample'], arrays['params_sample_index'] = _seeded_sample(flat, min(DUMP_SAMPLE, flat.numel()))
+    elif out.numel() * 4 <= DUMP_LIMIT:
+        arrays['output'] = out
+    else:
+        arrays['output_clip0'] = out[0]
+        arrays['output_sample'], arrays['output_sample_index'] = _seeded_sample(out.detach().reshape(-1), DUMP_SAMPLE)
+    arrays = {k: v.detach().cpu().numpy().astype(np.float64 if k.endswith('_index') else np.float32) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_LIMIT, f'--dump-outputs would write {total} bytes (limit {DUMP_LIMIT})'
+    os.makedirs(directory, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(directory, f'{k}.npy'), a)
+    return {k: list(a.shape) for k, a in arrays.items()}
+
+
 def leg_plan(args, world, batch):
     """Which legs of the report run where: 'all' = every rank calls it (it holds barriers / collectives, so NO rank may skip it), 'rank0' =
     rank 0 alone and collective-free, None = not at this N.  Legs that can fail on one rank alone (out of memory in `configs`) or
     that use the host's cores (the CPU oracle, the stock-ops arm) run at N = 1 only: a rank that stopped there would leave the others
     waiting in the next collective (tests/test_dist_cpu.py)."""
+    if not args.full:  # a plain run: the timed steps and nothing beside them
+        return dict.fromkeys(('fp32_mfma', 'batch4', 'roofline', 'target_4k', 'trained_like', 'configs', 'train', 'cpu_baseline',
+                              'stock_rocm_baseline'))
     infer = args.mode == 'infer'
     headline = infer and args.workload == 'edvr_l_x4_t5_180x320'
     single = world == 1
@@ -954,7 +1009,11 @@ def main():
             with torch.no_grad():
                 return net(x)
 
-    elapsed = timed(step, args.steps, args.warmup, dist, device)
+    last = []
+    elapsed = timed(step, args.steps, args.warmup, dist, device, last=last)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last[0], net, args.mode)
+    del last
 
     result = None
     if rank == 0:

@@ -8,6 +8,8 @@ Golden vectors come from the REFERENCE ITSELF wherever it can execute here:
                (deform_conv_cuda_kernel.cu compiled serially for the CPU: oracle/_ref), fp64
   edvr_*.pt  - seeded input + output of the reference's own Python network (basicsr/models/archs/edvr_arch.py
                imported unchanged, oracle/ref_import.py) with the DCN op supplied by oracle/_ref
+  oracle_vs_ref/*.npz    - the random cases of tests/test_oracle_vs_ref.py through the reference's own kernels
+  reference_modules.json - seeded state dicts (hashed) of the reference's EDVR classes and its deform_conv_ext call sites
 Small shapes only: the fixtures are committed.
 """
 import os
@@ -83,6 +85,61 @@ def dcn1_case(name):
     y = O.ref_dcn1_forward(d['x'], d['offset'], d['weight'], *cfg)
     dx, doff, dw = O.ref_dcn1_backward(d['x'], d['offset'], d['weight'], d['dy'], *cfg)
     return dict(cfg=cfg, x=d['x'], offset=d['offset'], weight=d['weight'], dy=d['dy'], y=y, dx=dx, doffset=doff, dweight=dw)
+
+
+def _digest(*ts):
+    import hashlib
+    h = hashlib.sha256()
+    for t in ts:
+        h.update(t.contiguous().numpy().tobytes())
+    return h.hexdigest()
+
+
+def oracle_vs_ref_case():
+    """The random cases of tests/test_oracle_vs_ref.py through the reference's own kernels, one compressed file per case and
+    operator under tests/golden/oracle_vs_ref/: DCNv2 forward / backward and DCNv1 forward / backward in fp64, the fp32 DCNv2
+    forward of case 0.  The inputs are not stored: the test regenerates them (_mk) and checks them against `inputs_sha256`."""
+    import numpy as np
+    from test_oracle_vs_ref import CASES, _mk
+    out = os.path.join(OUT, 'oracle_vs_ref')
+    os.makedirs(out, exist_ok=True)
+
+    def save(name, inputs, **arrays):
+        np.savez_compressed(os.path.join(out, name), inputs_sha256=np.array(_digest(*inputs)),
+                            **{k: v.numpy() for k, v in arrays.items()})
+    for i, case in enumerate(CASES):
+        x, off, m, w, b, dy, cfg = _mk(case, torch.float64)
+        inputs = (x, off, m, w, b, dy)
+        dx, doff, dm, dw, db = O.ref_backward(x, off, m, w, dy, True, *cfg)
+        save(f'case{i}_dcnv2.npz', inputs, y=O.ref_forward(x, off, m, w, b, *cfg), dx=dx, doffset=doff, dmask=dm, dweight=dw, dbias=db)
+        dx, doff, dw = O.ref_dcn1_backward(x, off, w, dy, *cfg)
+        save(f'case{i}_dcnv1.npz', inputs, y=O.ref_dcn1_forward(x, off, w, *cfg), dx=dx, doffset=doff, dweight=dw)
+    x, off, m, w, b, dy, cfg = _mk(CASES[0], torch.float32)
+    save('case0_fp32.npz', (x, off, m, w, b, dy), y=O.ref_forward(x, off, m, w, b, *cfg))
+
+
+def reference_modules_case():
+    """What tests/test_modules_cpu.py compares with the reference's Python: the state dicts of its EDVR classes under seed 7
+    (key, shape, dtype and sha256 of the bytes of every tensor) and the positional-argument count of every call into its
+    pybind module in basicsr/models/ops/dcn/deform_conv.py."""
+    import ast
+    import hashlib
+    import json
+    from test_modules_cpu import SEED_CASES
+    ea, _ = ref_import.load()
+    params = []
+    for kwargs in SEED_CASES:
+        torch.manual_seed(7)
+        sd = ea.EDVR(**kwargs).state_dict()
+        params.append(dict(kwargs=kwargs, tensors=[[k, list(v.shape), str(v.dtype), hashlib.sha256(v.contiguous().numpy().tobytes()).hexdigest()]
+                                                   for k, v in sd.items()]))
+    src = os.path.join(ref_import.REF_ROOT, 'basicsr', 'models', 'ops', 'dcn', 'deform_conv.py')
+    calls = {}
+    for node in ast.walk(ast.parse(open(src).read())):
+        if isinstance(node, ast.Call) and isinstance(node.func, ast.Attribute) and getattr(node.func.value, 'id', None) == 'deform_conv_ext':
+            calls[node.func.attr] = len(node.args)
+    with open(os.path.join(OUT, 'reference_modules.json'), 'w') as f:
+        json.dump(dict(seed=7, state_dicts=params, deform_conv_ext_call_sites=calls), f, indent=0)
 
 
 def edvr_case(name):
@@ -557,6 +614,8 @@ def main():
     for name in DCN1_CASES:
         torch.save(dcn1_case(name), os.path.join(OUT, f'dcn1_{name}.pt'))
     torch.save(dcn1_rect_case(), os.path.join(OUT, 'dcn1_rect.pt'))
+    oracle_vs_ref_case()
+    reference_modules_case()
     lr_sched_case()
     psnr_case()
     ssim_case()

@@ -137,3 +137,56 @@ def test_training_mode_line_carries_iters_per_sec():
     full.update(metric='EDVR-L x4 training clips/sec (= iters/sec x global batch)', iters_per_sec=9.44)
     got = json.loads(b.compact_line(full))
     assert got['iters_per_sec'] == 9.44
+
+
+def test_steps_warmup_and_options_parse():
+    import pytest
+    b = _bench()
+    a = b.parse(['--gpus', '1', '--steps', '7', '--warmup', '2'])
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (7, 2, False, None)
+    a = b.parse(['--steps', '1', '--warmup', '0', '--full', '--dump-outputs', 'out'])
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (1, 0, True, 'out')
+    for bad in (['--steps', '0'], ['--warmup', '-1']):
+        with pytest.raises(SystemExit):
+            b.parse(bad)
+
+
+def test_timed_runs_exactly_the_steps_asked_for_and_keeps_the_last_output():
+    import torch
+    b = _bench()
+    calls = []
+
+    def step():
+        calls.append(1)
+        return torch.full((2,), float(len(calls)))
+    last = []
+    b.timed(step, 4, 3, None, torch.device('cpu'), last=last)
+    assert len(calls) == 7 and len(last) == 1 and torch.equal(last[0], torch.full((2,), 7.0))
+
+
+def test_dump_outputs_writes_float_arrays_within_the_limit(tmp_path):
+    import numpy as np
+    import torch
+    b = _bench()
+    small = torch.rand(2, 3, 8, 12)
+    assert b.dump_outputs(str(tmp_path / 's'), small, None, 'infer') == {'output': [2, 3, 8, 12]}
+    assert np.array_equal(np.load(tmp_path / 's' / 'output.npy'), small.numpy())
+    # the headline's output (10 clips of 3 x 720 x 1280, 110 MB): the first clip whole + a seeded sample, the same in every run
+    big = torch.rand(10, 3, 720, 1280)
+    shapes = b.dump_outputs(str(tmp_path / 'b1'), big, None, 'infer')
+    b.dump_outputs(str(tmp_path / 'b2'), big, None, 'infer')
+    assert shapes == {'output_clip0': [3, 720, 1280], 'output_sample': [b.DUMP_SAMPLE], 'output_sample_index': [b.DUMP_SAMPLE]}
+    files = sorted(os.listdir(tmp_path / 'b1'))
+    assert sum(os.path.getsize(tmp_path / 'b1' / f) for f in files) <= 64 << 20
+    for f in files:
+        a1, a2 = np.load(tmp_path / 'b1' / f), np.load(tmp_path / 'b2' / f)
+        assert a1.dtype in (np.float32, np.float64) and np.array_equal(a1, a2)
+    idx = np.load(tmp_path / 'b1' / 'output_sample_index.npy').astype(np.int64)
+    assert np.array_equal(np.load(tmp_path / 'b1' / 'output_sample.npy'), big.numpy().reshape(-1)[idx])
+    # training: the loss and a sample of the updated parameters
+    net = torch.nn.Sequential(torch.nn.Linear(4, 3), torch.nn.Linear(3, 2))
+    shapes = b.dump_outputs(str(tmp_path / 't'), torch.tensor(1.5), net, 'train')
+    assert shapes['loss'] == [1] and np.load(tmp_path / 't' / 'loss.npy')[0] == 1.5
+    flat = torch.cat([p.detach().reshape(-1) for p in net.parameters()]).numpy()
+    idx = np.load(tmp_path / 't' / 'params_sample_index.npy').astype(np.int64)
+    assert np.array_equal(np.load(tmp_path / 't' / 'params_sample.npy'), flat[idx])

@@ -8,6 +8,7 @@ import torch.multiprocessing as mp
 
 def _worker(rank, world, port, q):
     os.environ.update(RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank), MASTER_ADDR='127.0.0.1', MASTER_PORT=str(port))
+    torch.cuda.is_available = lambda: False  # the host path under test, also where a GPU is visible (rank 1 has no GPU of its own there)
     from edvr_amd import dist as D
     r, w = D.init_dist(backend='gloo')
     assert (r, w) == (rank, world) and D.get_dist_info() == (rank, world)
@@ -30,7 +31,7 @@ def test_two_rank_sharding_and_gradient_allreduce():
     world, port = 2, 29533 + os.getpid() % 1000
     ctx = mp.get_context('spawn')
     q = ctx.Queue()
-    procs = [ctx.Process(target=_worker, args=(r, world, port, q)) for r in range(world)]
+    procs = [ctx.Process(target=_worker, args=(r, world, port, q), daemon=True) for r in range(world)]
     for p in procs:
         p.start()
     got = sorted([q.get(timeout=120) for _ in range(world)], key=lambda t: t[0])
@@ -96,10 +97,14 @@ def test_bench_leg_plan_never_lets_one_rank_skip_a_collective_leg():
     from unittest import mock
     b = _bench()
     with mock.patch.object(sys, 'argv', ['bench.py']):
+        plain = b.parse()
+    plain.workload = 'edvr_l_x4_t5_180x320'
+    assert not any(v for n in (1, 8) for v in b.leg_plan(plain, n, 10).values())  # a plain run: no leg beside the timed steps
+    with mock.patch.object(sys, 'argv', ['bench.py', '--full']):
         args = b.parse()
     args.workload = 'edvr_l_x4_t5_180x320'
     one, eight = b.leg_plan(args, 1, 10), b.leg_plan(args, 8, 10)
-    assert all(one[k] for k in one), one  # the default run at N = 1: every leg
+    assert all(one[k] for k in one), one  # the --full run at N = 1: every leg
     assert one['cpu_baseline'] == one['stock_rocm_baseline'] == one['roofline'] == 'rank0'
     for leg in ('fp32_mfma', 'batch4', 'target_4k', 'trained_like', 'train'):  # barriers / DDP collectives inside: all ranks or none
         assert one[leg] == eight[leg] == 'all', (leg, one[leg], eight[leg])
@@ -143,7 +148,7 @@ def test_bench_timing_is_max_over_ranks_and_only_rank0_prints():
     world, port = 2, 30533 + os.getpid() % 1000
     ctx = mp.get_context('spawn')
     q = ctx.Queue()
-    procs = [ctx.Process(target=_bench_worker, args=(r, world, port, q)) for r in range(world)]
+    procs = [ctx.Process(target=_bench_worker, args=(r, world, port, q), daemon=True) for r in range(world)]
     for p in procs:
         p.start()
     got = sorted([q.get(timeout=120) for _ in range(world)], key=lambda t: t[0])

@@ -1,11 +1,17 @@
 """CPU: pin the oracle.  The C restatement and the torch restatement of DCNv2 must agree with the reference's
-OWN kernels (deform_conv_cuda_kernel.cu compiled serially for the CPU into oracle/_ref) on random cases."""
+OWN kernels (deform_conv_cuda_kernel.cu compiled serially for the CPU into oracle/_ref) on random cases.  The
+reference's results on these cases are stored in tests/golden/oracle_vs_ref/ (oracle/make_golden.py::oracle_vs_ref_case),
+so the comparison needs no reference build."""
+import hashlib
+import os
+
+import numpy as np
 import pytest
 import torch
 
 from oracle import dcn_oracle as O
 
-needs_ref = pytest.mark.skipif(not O.have_ref(), reason='oracle/_ref not built (needs /root/reference)')
+GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'oracle_vs_ref')
 
 CASES = [
     # B, C, H, W, Co, k, stride, pad, dil, groups, dg, sigma, mode
@@ -37,31 +43,42 @@ def _mk(case, dt):
     return x, off, m, w, b, dy, (stride, pad, dil, groups, dg)
 
 
-@needs_ref
+def _golden(case, op, dt=torch.float64):
+    """The inputs of `case` (regenerated, checked against the digest stored with the results) and the reference kernels'
+    results on them for `op` ('dcnv2', 'dcnv1' or 'fp32')."""
+    x, off, m, w, b, dy, cfg = _mk(case, dt)
+    h = hashlib.sha256()
+    for t in (x, off, m, w, b, dy):
+        h.update(t.contiguous().numpy().tobytes())
+    with np.load(os.path.join(GOLD, f'case{CASES.index(case)}_{op}.npz')) as f:
+        assert h.hexdigest() == str(f['inputs_sha256']), 'regenerated inputs differ from those the fixture was made from'
+        ref = {k: torch.from_numpy(f[k]) for k in f.files if k != 'inputs_sha256'}
+    return (x, off, m, w, b, dy, cfg), ref
+
+
 @pytest.mark.parametrize('case', CASES)
 def test_c_restatement_equals_reference_kernels_fp64(case):
-    x, off, m, w, b, dy, cfg = _mk(case, torch.float64)
-    assert torch.equal(O.c_forward(x, off, m, w, b, *cfg), O.ref_forward(x, off, m, w, b, *cfg))  # bit-exact
-    for a, r in zip(O.c_backward(x, off, m, w, dy, True, *cfg), O.ref_backward(x, off, m, w, dy, True, *cfg)):
+    (x, off, m, w, b, dy, cfg), d = _golden(case, 'dcnv2')
+    assert torch.equal(O.c_forward(x, off, m, w, b, *cfg), d['y'])  # bit-exact
+    for a, r in zip(O.c_backward(x, off, m, w, dy, True, *cfg), (d['dx'], d['doffset'], d['dmask'], d['dweight'], d['dbias'])):
         assert (a - r).abs().max().item() <= 1e-13 * max(1.0, r.abs().max().item())
 
 
-@needs_ref
 @pytest.mark.parametrize('case', CASES)
 def test_torch_restatement_autograd_equals_reference_backward(case):
-    x, off, m, w, b, dy, cfg = _mk(case, torch.float64)
+    (x, off, m, w, b, dy, cfg), d = _golden(case, 'dcnv2')
     t = [v.clone().requires_grad_() for v in (x, off, m, w, b)]
     y = O.dcnv2_torch(*t, *cfg)
     y.backward(dy)
-    assert (y.detach() - O.ref_forward(x, off, m, w, b, *cfg)).abs().max().item() < 1e-12
-    for a, r in zip(t, O.ref_backward(x, off, m, w, dy, True, *cfg)):
+    assert (y.detach() - d['y']).abs().max().item() < 1e-12
+    for a, r in zip(t, (d['dx'], d['doffset'], d['dmask'], d['dweight'], d['dbias'])):
         assert (a.grad - r).abs().max().item() <= 1e-12 * max(1.0, r.abs().max().item())
 
 
-@needs_ref
 def test_fp32_paths_agree():
-    x, off, m, w, b, dy, cfg = _mk(CASES[0], torch.float32)
-    assert torch.equal(O.c_forward(x, off, m, w, b, *cfg), O.ref_forward(x, off, m, w, b, *cfg))
+    (x, off, m, w, b, _, cfg), d = _golden(CASES[0], 'fp32', torch.float32)
+    assert x.dtype == d['y'].dtype == torch.float32
+    assert torch.equal(O.c_forward(x, off, m, w, b, *cfg), d['y'])
 
 
 def test_zero_offset_unit_mask_is_conv2d():
@@ -84,16 +101,15 @@ def test_gradcheck_of_the_torch_restatement():
     assert torch.autograd.gradcheck(lambda *a: O.dcnv2_torch(*a, None, 1, 1, 1, 1, 2), (x, off, m, w), eps=1e-6, atol=1e-6)
 
 
-@needs_ref
 @pytest.mark.parametrize('case', CASES)
 def test_dcnv1_oracle_matches_the_references_own_v1_kernels(case):
     """DCNv1: the C oracle run with an all-ones mask equals the reference's deformable_im2col /
     col2im / col2im_coord kernels (.cu:190-465) driven as deform_conv_cuda.cpp:152-488 does - forward and all gradients."""
-    x, off, _, w, _, dy, cfg = _mk(case, torch.float64)
-    y_ref = O.ref_dcn1_forward(x, off, w, *cfg)
+    (x, off, _, w, _, dy, cfg), d = _golden(case, 'dcnv1')
+    y_ref = d['y']
     y_c = O.c_dcn1_forward(x, off, w, *cfg)
     assert torch.equal(y_ref, y_c) or (y_ref - y_c).abs().max().item() <= 1e-13 * max(1.0, y_ref.abs().max().item())
-    g_ref = O.ref_dcn1_backward(x, off, w, dy, *cfg)
+    g_ref = (d['dx'], d['doffset'], d['dweight'])
     g_c = O.c_dcn1_backward(x, off, w, dy, *cfg)
     for name, a, r in zip(('dx', 'doffset', 'dweight'), g_c, g_ref):
         assert (a - r).abs().max().item() <= 1e-12 * max(1.0, r.abs().max().item()), name
