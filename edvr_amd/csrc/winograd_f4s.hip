@@ -341,14 +341,13 @@ __global__ __launch_bounds__(1024, 1) void conv3x3_winograd_f4s_kernel(const Win
     // v_max_f32 would drop a NaN - the host's overflow guard reads these slots (ops.split_guard_submit).
     unsigned amx = 0u;
     auto abits = [](float v) { return __builtin_bit_cast(unsigned, v) & 0x7fffffffu; };
-    // max |.| of one 4x4 output tile.  Y[0][0], Y[0][3], Y[3][0], Y[3][3] together depend on all 36 positions of M (A^T rows 0 and 3
-    // cover columns 0..4 and 1..5), and 0 * (inf or NaN) = NaN: four fmas see an overflow anywhere in the tile's products
-    auto amax16 = [&](const f32x4 (&Y)[4]) {
-      float m = fmaxf(fmaxf(fabsf(Y[0][0]), fabsf(Y[0][1])), fmaxf(fabsf(Y[0][2]), fabsf(Y[0][3])));
+    // max |.| of one 4x4 output tile of a real channel (the padding channels beyond d.co hold copies of channel d.co - 1's residual),
+    // as bit patterns like the scalar path: a NaN anywhere in the tile is kept, also one that entered after the products (a residual)
+    auto amax16 = [&](const f32x4 (&Y)[4], bool real) {
+      unsigned m = 0u;
 #pragma unroll
-      for (int i = 1; i < 4; ++i) m = fmaxf(fmaxf(fmaxf(m, fabsf(Y[i][0])), fmaxf(fabsf(Y[i][1]), fabsf(Y[i][2]))), fabsf(Y[i][3]));
-      const float chk = __builtin_fmaf(Y[0][0], 0.f, __builtin_fmaf(Y[0][3], 0.f, __builtin_fmaf(Y[3][0], 0.f, Y[3][3] * 0.f)));
-      amx = max(max(amx, __builtin_bit_cast(unsigned, m)), abits(chk));
+      for (int i = 0; i < 4; ++i) m = max(m, max(max(abits(Y[i][0]), abits(Y[i][1])), max(abits(Y[i][2]), abits(Y[i][3]))));
+      amx = real ? max(amx, m) : amx;
     };
     F4S_SPAN_BEGIN();
     for (int item = item_first; item < item_end; item += xcd_wgs) {
@@ -456,7 +455,7 @@ __global__ __launch_bounds__(1024, 1) void conv3x3_winograd_f4s_kernel(const Win
           }
           if (SHF) {
             prefetch(min(p + 1, 7));
-            if (d.y_amax) amax16(Y);
+            if (d.y_amax) amax16(Y, co < d.co);
             if ((p & 1) == 0) {
 #pragma unroll
               for (int i = 0; i < 4; ++i) Yprev[i] = Y[i];
@@ -487,7 +486,7 @@ __global__ __launch_bounds__(1024, 1) void conv3x3_winograd_f4s_kernel(const Win
                 for (int jj = 0; jj < 4; ++jj) Y[i][jj] = __builtin_fmaf(Y[i][jj], a.ys, rr[i][jj]);
             }
             prefetch(min(p + 1, 7));
-            if (d.y_amax) amax16(Y);
+            if (d.y_amax) amax16(Y, co < d.co);
             if (co < d.co) {
               float *q = y + (int64_t)co * plane + pix;
 #pragma unroll

@@ -5,6 +5,8 @@ surrounding elementwise ops of the reference graph fused in (activation, residua
 channel concat of a second input, PixelShuffle).  When gradients are required the same
 launches are recorded as autograd Functions (edvr_amd/autograd.py).
 """
+import math
+
 import torch
 
 from . import ops
@@ -104,7 +106,12 @@ def halo_hint_from_stats(absmean, rough, tapwin_ok=True):
     exceptions, both rough fields: white noise of about a pixel, which the zero-centred R = 7 halo covers completely (83 vs 67
     TF/s at sigma 1), and white noise of tens of pixels (every tap of every lane through the fix-up pass: the column-buffer path,
     19 vs 17.5 TF/s at sigma 64).  Layers the tap-window kernel does not take (widths not a multiple of 4, other group sizes) fall
-    back to the zero-centred halo inside the C entry point."""
+    back to the zero-centred halo inside the C entry point.  Non-finite statistics (a clip that held NaN / inf) say nothing about the
+    next clip: unknown, as before the first call (NaN fails every comparison below and would pick the column-buffer class)."""
+    if absmean is not None and not math.isfinite(absmean):
+        absmean = None
+    if rough is not None and not math.isfinite(rough):
+        rough = None
     if not tapwin_ok:  # the C side would fall back to R = 7 whatever the offsets: pick the halo class by magnitude (R = 3 stages half as much)
         return 3 if (absmean is None or absmean < 1.2) else (7 if absmean < 3.0 else -1)
     if absmean is None:

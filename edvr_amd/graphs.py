@@ -16,6 +16,12 @@ buffers and pins them against the training path's in-place re-packing: call `ref
 checks the parameters' version counters and refuses to replay stale weights), and the per-layer
 performance hints (halo class of the fused DCN kernel: a replay keeps the class of capture time, so replays are bit-identical
 to each other; the classes agree with one another to fp32 rounding, not bit for bit - include/edvr_amd.h `halo_hint`).
+
+What a replay does NOT carry over: the magnitude bounds of the split-operand kernels.  The captured launches fold max |y| into
+one-element slots (`y_amax`), which later layers read as operand scales and the overflow guard reads after the replay.  The graph's
+first node zeroes those slots, so every replay starts from the same state as an eager forward: its bits do not depend on the
+clips replayed before it, and a clip with a NaN poisons only its own replay.  The split flags (ops.set_f4s) are recorded at
+capture; a call after they changed (EDVR_SPLIT_GUARD=fallback switches them off) re-captures before it replays.
 """
 import torch
 
@@ -48,14 +54,19 @@ class GraphedEDVR:
             for _ in range(max(1, warmup)):  # on the capture stream: its workspace (ops.workspace is per stream) exists before the capture
                 net(self.static_in)
             net.check_offsets()  # flush: nothing pending may be examined inside the capture
+            ops.split_guard_submit(self.static_in.device)  # (slots of this stream's earlier launches: examined now, not with the replays)
             ops.split_guard_check(wait=True)
-            ops.reserve_amax_slots(self.static_in.device)  # a fresh block of bound slots: no allocation / zero-fill inside the graph
+            ops.reserve_amax_slots(self.static_in.device)  # a fresh block of bound slots: no allocation inside the graph
             arena = ops._arena(self.static_in.device)
+            block = arena.buf
             self.graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(self.graph, stream=s):
+                block.zero_()  # first node: every replay starts from zeroed bounds (the captured launches take their slots from this block)
                 self.static_out = net(self.static_in)
             # the slots the captured launches write: folded into the overflow guard after every replay (nothing inside the graph)
             self._guard_slots = arena.take_unexamined()
+            ops.reserve_amax_slots(self.static_in.device)  # the block stays the graph's own: later launches on this stream take new slots
+        self._f4s = (ops.F4S_INFERENCE, ops.F4S_TRAINING)  # the split flags the captured launches were chosen under
         torch.cuda.current_stream().wait_stream(s)
         # the captured launches read the packed weight layouts of THIS moment: hold them and keep the training path's in-place
         # re-packing (ops.prepack_conv_weights) off them - a later optimizer step then packs into fresh buffers
@@ -77,6 +88,8 @@ class GraphedEDVR:
         from . import ops
         ops.split_guard_check(wait=False)
         self.static_in.copy_(x, non_blocking=True)
+        if (ops.F4S_INFERENCE, ops.F4S_TRAINING) != self._f4s:  # the split kernels were switched (EDVR_SPLIT_GUARD=fallback): re-capture
+            self._capture(1)
         self.graph.replay()
         ops.split_guard_submit(self.static_in.device, list(self._guard_slots))
         return self.static_out.clone() if self.clone else self.static_out

@@ -329,9 +329,10 @@ def set_f4s(inference=None, training=None):
 
 class _AmaxArena:
     """One-element device slots for the `y_amax` epilogue of the split-operand kernels and for the reduction passes: zeroed in blocks of
-    2048, each slot handed out once (a slot captured by a hipGraph keeps accumulating maxima over replays: still a bound).  One
-    arena per (device, stream): a block is zero-filled on the stream that uses it.  The slots handed out since the last
-    guard_submit() are what the overflow guard examines (a non-finite maximum = non-finite values left a split-operand kernel)."""
+    2048, each slot handed out once.  A hipGraph capture (graphs.GraphedEDVR) takes a fresh block, zeroes it in its first node and
+    keeps it to itself: every replay starts from zeroed slots, as an eager forward does.  One arena per (device, stream): a block is
+    zero-filled on the stream that uses it.  The slots handed out since the last guard_submit() are what the overflow guard
+    examines (a non-finite maximum = non-finite values left a split-operand kernel)."""
 
     BLOCK = 2048
 

@@ -141,3 +141,104 @@ def test_graph_keeps_its_packed_weights_through_a_training_step(gpu):
     opt.step()
     net(xg)                                                                # training forward: re-packs, in place again
     assert ops.pack_conv_weight(w).data_ptr() == ptr_now
+
+
+def _drain_guard(ops):
+    """Forget the overflow flags and unexamined bound slots earlier tests left behind (this test asserts its own)."""
+    ops._GUARD_PENDING.clear()
+    for arena in ops._AMAX_ARENAS.values():
+        arena.take_unexamined()
+
+
+def test_graph_replay_does_not_depend_on_earlier_clips(gpu):
+    """The bound slots the captured launches write are zeroed at the start of every replay: a replay of a dim clip after a bright
+    one gives the bits of the eager forward (the split kernels' operand scales follow each clip's own bounds)."""
+    from edvr_amd.graphs import GraphedEDVR
+    net, x, _ = build('M_T5')
+    net = net.to(gpu)
+    a = (torch.rand(x.shape, generator=torch.Generator().manual_seed(31)) / 16).to(gpu)
+    b = torch.rand(x.shape, generator=torch.Generator().manual_seed(32)).to(gpu)
+    with torch.no_grad():
+        want_a, want_b = net(a).clone(), net(b).clone()
+        net.check_offsets()
+    g = GraphedEDVR(net, a)
+    got_a1 = g(a).clone()
+    got_b = g(b).clone()
+    got_a2 = g(a).clone()
+    assert torch.equal(got_a1, want_a)
+    assert torch.equal(got_b, want_b)
+    assert torch.equal(got_a2, got_a1) and torch.equal(got_a2, want_a)
+
+
+@pytest.mark.parametrize('graphed', [True, False], ids=['replay', 'eager'])
+def test_graph_recovers_after_a_nan_clip(gpu, monkeypatch, graphed):
+    """One NaN pixel: the overflow guard raises once; the next clips are finite and bit-equal to eager forwards, and the guard stays
+    quiet.  (The eager forwards are the control: they take fresh slots every call.)"""
+    from edvr_amd import ops
+    from edvr_amd.graphs import GraphedEDVR
+    monkeypatch.setattr(ops, 'SPLIT_GUARD', 'raise')
+    _drain_guard(ops)
+    net, x, _ = build('M_T5')
+    net = net.to(gpu)
+    a = x.to(gpu)
+    bad = a.clone()
+    bad[0, 2, 1, 20, 30] = float('nan')
+    with torch.no_grad():
+        want = net(a).clone()
+        net.check_offsets()
+    ops.split_guard_check(wait=True)
+    if graphed:
+        run = GraphedEDVR(net, a)
+    else:
+        def run(clip):
+            with torch.no_grad():
+                return net(clip)
+    run(bad)
+    with pytest.raises(ops.SplitOperandOverflow):
+        ops.split_guard_check(wait=True)
+    ops.split_guard_check(wait=True)  # exactly once
+    got = run(a)
+    assert torch.isfinite(got).all() and torch.equal(got, want)
+    for _ in range(3):
+        assert torch.equal(run(a), want)
+    ops.split_guard_check(wait=True)
+    if not graphed:
+        net.check_offsets()
+    _drain_guard(ops)  # (on failure above, a poisoned flag may still be in flight: the next test starts clean either way)
+
+
+def test_graph_fallback_mode_recaptures_on_the_fp32_kernels(gpu, monkeypatch):
+    """EDVR_SPLIT_GUARD=fallback: a NaN replay warns and switches the split kernels off; the next call re-captures (the launches
+    captured before still name the split kernels) and replays the fp32 kernels only, with the eager fp32 result."""
+    from edvr_amd import ops
+    from edvr_amd.graphs import GraphedEDVR
+    monkeypatch.setattr(ops, 'SPLIT_GUARD', 'fallback')
+    flags = (ops.F4S_INFERENCE, ops.F4S_TRAINING)
+    try:
+        ops.set_f4s(True, True)
+        net, x, _ = build('M_T5')
+        net = net.to(gpu)
+        a = x.to(gpu)
+        bad = a.clone()
+        bad[0, 1, 0, 7, 9] = float('nan')
+        _drain_guard(ops)
+        g = GraphedEDVR(net, a)
+        g(bad)
+        with pytest.warns(UserWarning, match='fp32 kernels'):
+            ops.split_guard_check(wait=True)
+        assert (ops.F4S_INFERENCE, ops.F4S_TRAINING) == (False, False)
+        seen = []
+        ops.LAUNCH_HOOK = lambda name, flops, launch, *args: (seen.append(name), launch())
+        try:
+            got = g(a).clone()
+        finally:
+            ops.LAUNCH_HOOK = None
+        assert seen, 'the call did not re-capture'
+        assert not [k for k in seen if 'split' in k or 'f4s' in k], sorted(set(seen))
+        with torch.no_grad():
+            want = net(a)
+        assert torch.equal(got, want)
+        ops.split_guard_check(wait=True)
+    finally:
+        ops.set_f4s(*flags)
+        _drain_guard(ops)

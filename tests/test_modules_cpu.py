@@ -107,6 +107,12 @@ def test_kernel_hints_from_offset_statistics():
     assert F_.halo_hint_from_stats(8.0, 0.2) == T and F_.halo_hint_from_stats(3.2, 4.5) == T and F_.halo_hint_from_stats(12.8, 18.0) == T
     assert F_.halo_hint_from_stats(0.8, 1.13) == 7 and F_.halo_hint_from_stats(51.0, 72.0) == -1
     assert F_.halo_hint_from_stats(0.4, None) == 3 and F_.halo_hint_from_stats(8.0, None) == -1
+    # statistics of a clip that held NaN / inf: unknown, as before the first call (not the column buffer NaN comparisons would pick)
+    for bad in (float('nan'), float('inf')):
+        for ok in (True, False):
+            assert F_.halo_hint_from_stats(bad, bad, ok) == F_.halo_hint_from_stats(None, None, ok)
+            assert F_.halo_hint_from_stats(bad, 0.5, ok) == F_.halo_hint_from_stats(None, 0.5, ok)
+        assert F_.halo_hint_from_stats(0.4, bad) == F_.halo_hint_from_stats(0.4, None)
     # backward
     assert F_.scatter_hint_from_stats(8.0, 0.2) == ops.DCN_SCATTER_LDS_WIDE and F_.scatter_hint_from_stats(8.0, 1.5) == ops.DCN_SCATTER_LDS_WIDE  # (>= 4 px: the 6 px margin)
     assert F_.scatter_hint_from_stats(3.9, 0.2) == ops.DCN_SCATTER_LDS
