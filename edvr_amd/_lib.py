@@ -23,6 +23,7 @@ class ConvDesc(ctypes.Structure):
         ('res2', vp), ('res1_img_stride', i64), ('res2_img_stride', i64), ('y', vp), ('y_img_stride', i64),
         ('out_mode', i32), ('algo', i32), ('gate', vp), ('gate_img_stride', i64), ('gate_slope', f32), ('y_scale', f32),
         ('wpk_f4', vp), ('abs_sum', vp), ('abs_sum_channels', i32), ('wpk_f4s', vp), ('x_amax', vp), ('y_amax', vp),
+        ('pre', vp), ('pre_img_stride', i64), ('pre_div', i32), ('pre_mul', i32), ('pre_add', i32), ('pre_n', i32),
     ]
 
 
@@ -46,6 +47,7 @@ PROTOTYPES = {
     'edvr_conv2d_gate_supported': (i32, [ctypes.POINTER(ConvDesc)]),
     'edvr_conv2d_abs_sum_supported': (i32, [ctypes.POINTER(ConvDesc)]),
     'edvr_conv2d_y_amax_supported': (i32, [ctypes.POINTER(ConvDesc)]),
+    'edvr_conv2d_pre_supported': (i32, [ctypes.POINTER(ConvDesc)]),
     'edvr_conv2d_kernel_name': (i32, [ctypes.POINTER(ConvDesc), ctypes.c_char_p, sz]),
     'edvr_conv2d_executed_flops': (i32, [ctypes.POINTER(ConvDesc), ctypes.POINTER(ctypes.c_double)]),
     'edvr_dcnv2_fwd_ws_bytes': (sz, [i32] * 12),

@@ -376,6 +376,21 @@ int conv2d_launch(const edvr_conv2d_desc &d, hipStream_t stream) {
     set_error("conv2d: y_amax is an epilogue of the split-operand kernels only (ask edvr_conv2d_y_amax_supported)");
     return EDVR_ERR_UNSUPPORTED;
   }
+  if (d.pre) {
+    const int64_t last = d.pre_div > 0 ? (int64_t)((d.n - 1) / d.pre_div) * d.pre_mul + d.pre_add : d.n - 1;
+    EDVR_REQUIRE(d.pre_n > 0 && d.pre_div >= 0 && d.pre_mul >= 0 && d.pre_add >= 0 && last < d.pre_n,
+                 "conv2d: pre image map (div=%d mul=%d add=%d) of n=%d images leaves its %d images", d.pre_div, d.pre_mul, d.pre_add, d.n, d.pre_n);
+    EDVR_REQUIRE(d.pre_img_stride >= (int64_t)d.co * d.h * d.w, "conv2d: pre must be (pre_n, co=%d, h=%d, w=%d): image stride %lld", d.co, d.h,
+                 d.w, (long long)d.pre_img_stride);
+    if (d.gate || d.res1 || d.res2 || d.out_mode != EDVR_OUT_NCHW) {
+      set_error("conv2d: pre excludes gate, res1 / res2 and the pixel-shuffle output (it rides in their registers of the NCHW epilogue)");
+      return EDVR_ERR_UNSUPPORTED;
+    }
+    if (conv_small_eligible(d) || !(winograd_f4s_eligible(d) || winograd_f4_eligible(d))) {
+      set_error("conv2d: pre is an epilogue of the F(4x4) Winograd kernels only, 16-byte aligned (ask edvr_conv2d_pre_supported)");
+      return EDVR_ERR_UNSUPPORTED;
+    }
+  }
   if (!d.gate && !scaled && conv_small_eligible(d)) return conv_small_launch(d, stream);
   if (winograd_f4s_eligible(d)) return winograd_f4s_launch(d, stream);
   if (winograd_f4_eligible(d)) return winograd_f4_launch(d, stream);
@@ -462,6 +477,16 @@ int edvr_conv2d_executed_flops(const edvr_conv2d_desc *d, double *flops) {
 int edvr_conv2d_abs_sum_supported(const edvr_conv2d_desc *d) {
   if (!d) return 0;
   return (!edvr::conv_small_eligible(*d) && (edvr::winograd_f4_eligible(*d) || edvr::winograd_f4s_eligible(*d)) && d->out_mode == EDVR_OUT_NCHW) ? 1 : 0;  // (the PixelShuffle store has no such sum)
+}
+
+int edvr_conv2d_pre_supported(const edvr_conv2d_desc *d) {
+  if (!d) return 0;
+  edvr_conv2d_desc q = *d;
+  if (!q.pre) q.pre_img_stride = 0;  // callers probe with the pointer unset: only the eligibility rules are evaluated
+  return (!q.gate && !q.res1 && !q.res2 && q.out_mode == EDVR_OUT_NCHW && !edvr::conv_small_eligible(q) &&
+          (edvr::winograd_f4s_eligible(q) || edvr::winograd_f4_eligible(q)))
+             ? 1
+             : 0;
 }
 
 int edvr_conv2d_y_amax_supported(const edvr_conv2d_desc *d) {

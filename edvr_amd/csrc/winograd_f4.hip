@@ -279,7 +279,9 @@ __global__ __launch_bounds__(1024, 1) void conv3x3_winograd_f4_kernel(const Wino
       const float *r1 = d.res1 ? d.res1 + (int64_t)e_img * d.res1_img_stride : nullptr;
       const float *r2 = d.res2 ? d.res2 + (int64_t)e_img * d.res2_img_stride : nullptr;
       const float *gt = d.gate ? d.gate + (int64_t)e_img * d.gate_img_stride : nullptr;
-      const float *rq = gt ? gt : r1;  // the tensor read per output element (gate and residuals exclude each other)
+      const float *pq = nullptr;  // pre-activation addend (edvr_conv2d_desc.pre) of this image: excludes gate and residuals (host check)
+      if (d.pre) pq = d.pre + (int64_t)(d.pre_div > 0 ? (e_img / d.pre_div) * d.pre_mul + d.pre_add : e_img) * d.pre_img_stride;
+      const float *rq = gt ? gt : (pq ? pq : r1);  // the tensor read per output element (gate, pre and residuals exclude each other)
       const float slope = d.act == EDVR_ACT_LRELU ? 0.1f : (d.act == EDVR_ACT_RELU ? 0.f : 1.f);  // none/relu/lrelu = max(v, slope*v)
       const bool sig = d.act == EDVR_ACT_SIGMOID, shuffle = d.out_mode == EDVR_OUT_PIXEL_SHUFFLE2;
       const bool vec = e_tx0 + BW <= d.w;  // the block is inside the image in x (w % 4 == 0): 16-byte rows, only the ROW is tested
@@ -299,7 +301,7 @@ __global__ __launch_bounds__(1024, 1) void conv3x3_winograd_f4_kernel(const Wino
         f32x4 Yprev[4];
         f32x4 rr[4];
         auto co_of = [&](int p) { return co_t + (p & 3) + 16 * (p >> 2); };
-        auto prefetch = [&](int p) {  // (V) rows oy .. oy + 3 of the residual(s) / gate of channel co_of(p)
+        auto prefetch = [&](int p) {  // (V) rows oy .. oy + 3 of the residual(s) / gate / pre of channel co_of(p)
           const int co = min(co_of(p), d.co - 1);
           if (V && !SHF && rq) {
             const float *q1 = rq + (int64_t)co * plane + pix;
@@ -311,6 +313,10 @@ __global__ __launch_bounds__(1024, 1) void conv3x3_winograd_f4_kernel(const Wino
               for (int i = 0; i < 4; ++i)
                 if (i < rows_in) rr[i] += *reinterpret_cast<const f32x4 *>(q2 + i * d.w);
             }
+          } else if (!V && pq) {  // edge blocks: `pre` enters BEFORE the activation, so it is fetched here too; w % 4 == 0: a tile's row is inside or outside as a whole
+            const float *q1 = pq + (int64_t)co * plane + pix;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) rr[i] = (i < rows_in && ox < d.w) ? *reinterpret_cast<const f32x4 *>(q1 + i * d.w) : f32x4{0.f, 0.f, 0.f, 0.f};
           }
         };
         prefetch(0);
@@ -332,6 +338,10 @@ __global__ __launch_bounds__(1024, 1) void conv3x3_winograd_f4_kernel(const Wino
             Y[1][jj] = __builtin_fmaf(2.f, d2, d1) + b;
             Y[2][jj] = __builtin_fmaf(4.f, s2, s1) + b;
             Y[3][jj] = __builtin_fmaf(8.f, d2, d1) + T[5][jj] + b;
+          }
+          if (pq) {  // pre-activation addend
+#pragma unroll
+            for (int i = 0; i < 4; ++i) Y[i] += rr[i];
           }
           if (sig) {
             if (co >= d.act_from) {
@@ -545,6 +555,7 @@ bool winograd_f4_supported(const edvr_conv2d_desc &d) {
   const bool has_res = d.res1 || d.res2;
   if (d.gate && (has_res || d.act == EDVR_ACT_SIGMOID || d.out_mode != EDVR_OUT_NCHW)) return false;
   if ((d.res2 && !d.res1) || (d.out_mode != EDVR_OUT_NCHW && has_res)) return false;
+  if (d.pre && (d.gate || has_res || d.out_mode != EDVR_OUT_NCHW)) return false;  // `pre` rides in the residual / gate registers of the NCHW epilogue
   if (d.y_scale != 0.f && d.y_scale != 1.f && !d.res1 && !d.gate) return false;  // the scale lives in the residual / gate epilogues
   if (d.c2 > 0 && (d.c1 & 1)) return false;                                      // a staging wave covers two consecutive channels
   if ((int64_t)((d.co + 63) / 64 * 64) * ((d.c1 + d.c2 + 7) / 8 * 8) * 144 >= ((int64_t)1 << 31)) return false;  // the packed weights: 32-bit offsets
@@ -553,7 +564,7 @@ bool winograd_f4_supported(const edvr_conv2d_desc &d) {
   auto aligned = [](const float *p, int64_t img_stride, int a) { return !p || ((reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0 && (img_stride * 4 & (a - 1)) == 0); };
   if (!aligned(d.x1, d.x1_img_stride, 16) || !aligned(d.x2, d.x2_img_stride, 16)) return false;
   if (!aligned(d.y, d.y_img_stride, 16) || !aligned(d.res1, d.res1_img_stride, 16) || !aligned(d.res2, d.res2_img_stride, 16) ||
-      !aligned(d.gate, d.gate_img_stride, 16))
+      !aligned(d.gate, d.gate_img_stride, 16) || !aligned(d.pre, d.pre_img_stride, 16))
     return false;
   return true;
 }

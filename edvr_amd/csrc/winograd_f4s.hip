@@ -379,7 +379,9 @@ __global__ __launch_bounds__(1024, 1) void conv3x3_winograd_f4s_kernel(const Win
       const float *r1 = d.res1 ? d.res1 + (int64_t)e_img * d.res1_img_stride : nullptr;
       const float *r2 = d.res2 ? d.res2 + (int64_t)e_img * d.res2_img_stride : nullptr;
       const float *gt = d.gate ? d.gate + (int64_t)e_img * d.gate_img_stride : nullptr;
-      const float *rq = gt ? gt : r1;  // the tensor read per output element (gate and residuals exclude each other)
+      const float *pq = nullptr;  // pre-activation addend (edvr_conv2d_desc.pre) of this image: excludes gate and residuals (host check)
+      if (d.pre) pq = d.pre + (int64_t)(d.pre_div > 0 ? (e_img / d.pre_div) * d.pre_mul + d.pre_add : e_img) * d.pre_img_stride;
+      const float *rq = gt ? gt : (pq ? pq : r1);  // the tensor read per output element (gate, pre and residuals exclude each other)
       const float slope = d.act == EDVR_ACT_LRELU ? 0.1f : (d.act == EDVR_ACT_RELU ? 0.f : 1.f);  // none/relu/lrelu = max(v, slope*v)
       const bool sig = d.act == EDVR_ACT_SIGMOID, shuffle = d.out_mode == EDVR_OUT_PIXEL_SHUFFLE2;
       const bool vec = e_tx0 + BW <= d.w;  // the block is inside the image in x (w % 4 == 0): 16-byte rows, only the ROW is tested
@@ -389,13 +391,14 @@ __global__ __launch_bounds__(1024, 1) void conv3x3_winograd_f4s_kernel(const Win
       const int pix = oy * d.w + ox;
       const int rows_in = d.h - oy;  // rows of this lane's tile inside the image (>= 4: all of them)
       if (wave == 0) bias_s[lane] = (d.bias && e_co_blk + lane < d.co) ? d.bias[e_co_blk + lane] : 0.f;  // read after the first phase barrier
-      auto column_pass = [&](auto VEC, auto SHUF) {
+      auto column_pass = [&](auto VEC, auto SHUF, auto PREADD) {
+        constexpr bool PRE = decltype(PREADD)::value;  // pre-activation addend: instances of their own, the others stay as they were
         constexpr bool V = decltype(VEC)::value;     // whole 16-byte rows inside the image in x: no per-element tests
         constexpr bool SHF = decltype(SHUF)::value;  // V && PixelShuffle(2)
         f32x4 Yprev[4];
         f32x4 rr[4];
         auto co_of = [&](int p) { return co_t + (p & 3) + 16 * (p >> 2); };
-        auto prefetch = [&](int p) {  // (V) rows oy .. oy + 3 of the residual(s) / gate of channel co_of(p)
+        auto prefetch = [&](int p) {  // (V) rows oy .. oy + 3 of the residual(s) / gate / pre of channel co_of(p)
           const int co = min(co_of(p), d.co - 1);
           if (V && !SHF && rq) {
             const float *q1 = rq + (int64_t)co * plane + pix;
@@ -407,6 +410,10 @@ __global__ __launch_bounds__(1024, 1) void conv3x3_winograd_f4s_kernel(const Win
               for (int i = 0; i < 4; ++i)
                 if (i < rows_in) rr[i] += *reinterpret_cast<const f32x4 *>(q2 + i * d.w);
             }
+          } else if (PRE && !V) {  // edge blocks: `pre` enters BEFORE the activation, so it is fetched here too; w % 4 == 0: a tile's row is inside or outside as a whole
+            const float *q1 = pq + (int64_t)co * plane + pix;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) rr[i] = (i < rows_in && ox < d.w) ? *reinterpret_cast<const f32x4 *>(q1 + i * d.w) : f32x4{0.f, 0.f, 0.f, 0.f};
           }
         };
         prefetch(0);
@@ -433,6 +440,12 @@ __global__ __launch_bounds__(1024, 1) void conv3x3_winograd_f4s_kernel(const Win
             f32x2 y1 = (2.f * d2 + d1) * us + bb;
             f32x2 y2 = (4.f * s2 + s1) * us + bb;
             f32x2 y3 = (8.f * d2 + d1 + t5) * us + bb;
+            if (PRE) {  // pre-activation addend: rows of this tile, columns (2 jp, 2 jp + 1)
+              y0 += f32x2{rr[0][2 * jp], rr[0][2 * jp + 1]};
+              y1 += f32x2{rr[1][2 * jp], rr[1][2 * jp + 1]};
+              y2 += f32x2{rr[2][2 * jp], rr[2][2 * jp + 1]};
+              y3 += f32x2{rr[3][2 * jp], rr[3][2 * jp + 1]};
+            }
             if (!sig) {  // none / relu / lrelu = max(v, slope * v): one packed multiply + two v_max_f32 per pair
               const f32x2 sl2 = f32x2{sl, sl};
               const f32x2 z0 = y0 * sl2, z1 = y1 * sl2, z2 = y2 * sl2, z3 = y3 * sl2;
@@ -448,6 +461,10 @@ __global__ __launch_bounds__(1024, 1) void conv3x3_winograd_f4s_kernel(const Win
           }
           if (sig && co >= d.act_from) {
             if (d.y_amax) amx = max(amx, abits(__builtin_fmaf(Y[0][0], 0.f, __builtin_fmaf(Y[0][3], 0.f, __builtin_fmaf(Y[3][0], 0.f, Y[3][3] * 0.f)))));  // (a sigmoid maps +-inf to finite values)
+            if (PRE && d.y_amax) {  // ... and an infinity of `pre` sits in ONE element, not in a whole tile as an overflown product does
+#pragma unroll
+              for (int i = 0; i < 4; ++i) amx = max(amx, abits(__builtin_fmaf(rr[i][0], 0.f, __builtin_fmaf(rr[i][1], 0.f, __builtin_fmaf(rr[i][2], 0.f, rr[i][3] * 0.f)))));
+            }
 #pragma unroll
             for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -519,9 +536,11 @@ __global__ __launch_bounds__(1024, 1) void conv3x3_winograd_f4s_kernel(const Win
           }
         }
       };
-      if (vec && shuffle) column_pass(std::true_type{}, std::true_type{});
-      else if (vec) column_pass(std::true_type{}, std::false_type{});
-      else column_pass(std::false_type{}, std::false_type{});
+      if (pq && vec) column_pass(std::true_type{}, std::false_type{}, std::true_type{});
+      else if (pq) column_pass(std::false_type{}, std::false_type{}, std::true_type{});
+      else if (vec && shuffle) column_pass(std::true_type{}, std::true_type{}, std::false_type{});
+      else if (vec) column_pass(std::true_type{}, std::false_type{}, std::false_type{});
+      else column_pass(std::false_type{}, std::false_type{}, std::false_type{});
       F4S_SPAN_END(3);
     }
     if (d.abs_sum) asum_flush();
@@ -705,6 +724,7 @@ bool winograd_f4s_supported(const edvr_conv2d_desc &d) {
   const bool has_res = d.res1 || d.res2;
   if (d.gate && (has_res || d.act == EDVR_ACT_SIGMOID || d.out_mode != EDVR_OUT_NCHW)) return false;
   if ((d.res2 && !d.res1) || (d.out_mode != EDVR_OUT_NCHW && has_res)) return false;
+  if (d.pre && (d.gate || has_res || d.out_mode != EDVR_OUT_NCHW)) return false;  // `pre` rides in the residual / gate registers of the NCHW epilogue
   if (d.y_scale != 0.f && d.y_scale != 1.f && !d.res1 && !d.gate) return false;
   if (d.c2 > 0 && (d.c1 & 1)) return false;
   if ((int64_t)((d.co + 63) / 64 * 64) * ((d.c1 + d.c2 + 7) / 8 * 8) * 144 + 64 >= ((int64_t)1 << 31)) return false;
@@ -713,7 +733,7 @@ bool winograd_f4s_supported(const edvr_conv2d_desc &d) {
   auto aligned = [](const void *p, int64_t img_stride, int a) { return !p || ((reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0 && (img_stride * 4 & (a - 1)) == 0); };
   if (!aligned(d.x1, d.x1_img_stride, 16) || !aligned(d.x2, d.x2_img_stride, 16)) return false;
   if (!aligned(d.y, d.y_img_stride, 16) || !aligned(d.res1, d.res1_img_stride, 16) || !aligned(d.res2, d.res2_img_stride, 16) ||
-      !aligned(d.gate, d.gate_img_stride, 16) || !aligned(d.wpk_f4s, 0, 16))
+      !aligned(d.gate, d.gate_img_stride, 16) || !aligned(d.wpk_f4s, 0, 16) || !aligned(d.pre, d.pre_img_stride, 16))
     return false;
   return true;
 }

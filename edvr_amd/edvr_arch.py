@@ -67,7 +67,7 @@ class PCDAlignment(nn.Module):
         up_off = up_feat = feat = None
         for lv in (3, 2, 1):
             key, x = f'l{lv}', nbr[lv - 1]
-            off = F_.conv(self.offset_conv1[key], x, x2=ref[lv - 1], x2_map=ref_map, act=LRELU)
+            off = F_.conv_shared_x2(self.offset_conv1[key], x, ref[lv - 1], ref_map, act=LRELU)  # (the reference half: once per clip)
             if lv == 3:
                 off = F_.conv(self.offset_conv2[key], off, act=LRELU)
             else:
@@ -79,7 +79,7 @@ class PCDAlignment(nn.Module):
             if lv > 1:
                 up_off = F_.upsample2x(off, 2.0)  # offsets double with the resolution (:109)
                 up_feat = F_.upsample2x(feat)
-        off = F_.conv(self.cas_offset_conv1, feat, x2=ref[0], x2_map=ref_map, act=LRELU)
+        off = F_.conv_shared_x2(self.cas_offset_conv1, feat, ref[0], ref_map, act=LRELU)
         off = F_.conv(self.cas_offset_conv2, off, act=LRELU)
         return self.cas_dcnpack(feat, off, act=LRELU)
 

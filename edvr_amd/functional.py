@@ -6,6 +6,7 @@ channel concat of a second input, PixelShuffle).  When gradients are required th
 launches are recorded as autograd Functions (edvr_amd/autograd.py).
 """
 import math
+import os
 
 import torch
 
@@ -27,41 +28,82 @@ def _needs_grad(*ts):
 
 
 def conv(m, x, *, x2=None, x2_map=None, act=ACT_NONE, act_from=0, res1=None, res2=None, out_mode=OUT_NCHW, y_scale=1.0,
-         abs_sum_channels=0):
+         abs_sum_channels=0, ci_range=None, use_bias=True, pre=None, pre_map=None):
     """y_scale * act(conv(cat(x, x2)) + bias) + res1 + res2 with the parameters of nn.Conv2d `m`.
-    abs_sum_channels > 0 (no-grad calls only): returns (y, per-image sums of |y[:, :abs_sum_channels]|), ops.conv2d."""
+    abs_sum_channels > 0 (no-grad calls only): returns (y, per-image sums of |y[:, :abs_sum_channels]|), ops.conv2d.
+    No-grad calls only (conv_shared_x2 is their user): ci_range = (lo, hi) convolves with m.weight[:, lo:hi] alone, use_bias=False leaves
+    the bias out, pre / pre_map add a tensor BEFORE the activation (ops.conv2d)."""
     ks, stride = _conv_geometry(m)
     if x.dim() != 4:
         raise ValueError(f'expected a 4-D input, got {tuple(x.shape)}')
     cin = x.shape[1] + (x2.shape[1] if x2 is not None else 0)
-    if cin != m.in_channels:
-        raise RuntimeError(f'expected {m.in_channels} input channels, got {cin}')
+    want = m.in_channels if ci_range is None else ci_range[1] - ci_range[0]
+    if cin != want:
+        raise RuntimeError(f'expected {want} input channels, got {cin}')
     ops.require_gpu(x, x2, m.weight)
-    if _needs_grad(x, x2, m.weight, m.bias, res1, res2):
+    if _needs_grad(x, x2, m.weight, m.bias, res1, res2, pre):
         from . import autograd as ag
         assert abs_sum_channels == 0
+        if ci_range is not None or not use_bias or pre is not None:
+            raise NotImplementedError('ci_range / use_bias / pre are inference-only arguments of conv()')
         return ag.conv(m, x, x2, x2_map, act, act_from, res1, res2, out_mode, ks, stride, y_scale)
-    wpk = ops.pack_conv_weight(m.weight)
+    wpk = ops.pack_conv_weight(m.weight, ci_range=ci_range)
     # the F(4x4,3x3) Winograd weights let the C side pick that kernel where it is the fastest (2.25 instead of 4 multiplies per
     # output, rounding ~1e-6 of the output scale instead of ~2e-7; EDVR_WINOGRAD_F4=0 switches it off here,
     # EDVR_WINOGRAD_F4_TRAIN=0 in the training path above)
-    f4 = ops.F4_INFERENCE and ks == 3 and stride == 1 and m.in_channels >= 32 and m.out_channels >= 48
+    f4 = ops.F4_INFERENCE and ks == 3 and stride == 1 and cin >= 32 and m.out_channels >= 48
     # ... and the split-operand form of the same algorithm (csrc/winograd_f4s.hip: fp32 operands as f16 (hi, lo) pairs on the f16
     # matrix pipe, all four cross products, fp32 accumulation - the fp32 kernel's accuracy at 1.3-1.5x its speed; the bound of the
     # input's magnitude it needs travels with the tensors, ops.set_bound / input_bound); EDVR_WINOGRAD_F4S=0 keeps the fp32 kernel
     f4s = f4 and ops.F4S_INFERENCE and x.shape[3] % 4 == 0
-    wf4 = ops.pack_conv_weight(m.weight, f4=True) if (f4 and not f4s) else None
-    wf4s = ops.pack_conv_weight(m.weight, f4s=True) if f4s else None
+    wf4 = ops.pack_conv_weight(m.weight, f4=True, ci_range=ci_range) if (f4 and not f4s) else None
+    wf4s = ops.pack_conv_weight(m.weight, f4s=True, ci_range=ci_range) if f4s else None
     if ops.F4S_INFERENCE and ks == 1 and stride == 1 and cin >= 320 and x.shape[1] % 8 == 0 and cin % 8 == 0:
-        wf4s = ops.pack_conv_weight(m.weight, f4s=True)  # the streaming 1x1 kernel's split form (csrc/conv1x1_s.hip; the C side decides)
-    bias = m.bias.detach() if m.bias is not None else None
+        wf4s = ops.pack_conv_weight(m.weight, f4s=True, ci_range=ci_range)  # the streaming 1x1 kernel's split form (csrc/conv1x1_s.hip; the C side decides)
+    bias = m.bias.detach() if (m.bias is not None and use_bias) else None
     r = ops.conv2d(x, wpk, bias, m.out_channels, ks, x2=x2, x2_map=x2_map, stride=stride, act=act, act_from=act_from,
                    res1=res1, res2=res2, out_mode=out_mode, y_scale=y_scale, wpk_f4=wf4, abs_sum_channels=abs_sum_channels,
-                   wpk_f4s=wf4s)
+                   wpk_f4s=wf4s, pre=pre, pre_map=pre_map)
     y = r[0] if abs_sum_channels > 0 else r
     if ops.F4S_INFERENCE and ops.get_bound(y) is None:  # a kernel without the y_amax epilogue: the bound from the weights' norms
-        ops.linear_bound(y, m.weight, m.bias, (x, x2), (res1, res2), scale=y_scale, floor=1.0 if act == ACT_SIGMOID else 0.0)
+        # (of the WHOLE weight also where a channel range of it ran: a sum over more channels, still a bound)
+        ops.linear_bound(y, m.weight, m.bias, (x, x2), (res1, res2, pre), scale=y_scale, floor=1.0 if act == ACT_SIGMOID else 0.0)
     return r
+
+
+PRE_SPLIT = os.environ.get('EDVR_CONV_PRE', '1') != '0'  # conv_shared_x2 convolves a shared second input once per shared image (tests flip it)
+PRE_SPLIT_MIN_ITEMS = None  # ... only from this many work items of the two-input launch on (None: the device's CU count; tests set 0)
+
+
+def _conv_items(n, h, w, co):
+    """Work items of an F(4x4) conv launch: 64 output channels x one block of 8 x 64 or 16 x 32 pixels, whichever shape pads the image
+    less (csrc/winograd_f4s.hip f4s_geometry).  One persistent workgroup per CU walks them."""
+    return n * -(-co // 64) * min(-(-w // 64) * -(-h // 8), -(-w // 32) * -(-h // 16))
+
+
+def conv_shared_x2(m, x, x2, x2_map, act=ACT_NONE):
+    """conv(m, x, x2=x2, x2_map=x2_map, act=act) for a second input whose images are SHARED by several images of x
+    (x2_map = (div, mul, add): image i of x reads image (i // div) * mul + add of x2 - PCDAlignment's reference features, one per
+    clip of t frames).  A convolution is linear in its input channels: conv(cat(x, x2), W) = conv(x, W[:, :c1]) + conv(x2, W[:, c1:]).
+    Without gradients, and where the layer runs on a kernel with the pre-activation addend (edvr_conv2d_desc.pre), the second
+    term is computed once per shared image, without bias or activation, and added in the first conv's epilogue before bias and
+    activation: 1 / div of the second half's multiplies.  Each half scales its operands by its own input's magnitude bound.
+    It pays only where the two-input launch has more work items than the device has CUs: below that every workgroup holds at most
+    one item, the launch lasts as long as ONE item's walk over its input channels, and two launches that walk half of them each
+    (plus a second epilogue and a launch gap) cannot be faster - small layers keep the single launch.
+    Everything else - training, no map, a kernel without the operand, EDVR_CONV_PRE=0 - is the one two-input launch too."""
+    if PRE_SPLIT and x2_map is not None and x2_map[0] > 1 and not _needs_grad(x, x2, m.weight, m.bias):
+        ks, stride = _conv_geometry(m)
+        (n, c1, h, w), c2, co = x.shape, x2.shape[1], m.out_channels
+        f4 = ops.F4_INFERENCE and ks == 3 and stride == 1 and min(c1, c2) >= 32 and co >= 48
+        min_items = PRE_SPLIT_MIN_ITEMS if PRE_SPLIT_MIN_ITEMS is not None else torch.cuda.get_device_properties(x.device).multi_processor_count
+        if f4 and _conv_items(n, h, w, co) > min_items and ops.conv_pre_supported(n, c1, h, w, co, ops.F4S_INFERENCE and w % 4 == 0):
+            div, mul, add = x2_map
+            shared = (n - 1) // div + 1  # images of x2 the map reaches: add, add + mul, ...
+            sel = x2[add:add + 1] if (mul == 0 or shared == 1) else x2[add:add + (shared - 1) * mul + 1:mul]
+            p = conv(m, ops.carry_bound(sel, x2), ci_range=(c1, c1 + c2), use_bias=False)
+            return conv(m, x, act=act, ci_range=(0, c1), pre=p, pre_map=(div, 0 if sel.shape[0] == 1 else 1, 0))
+    return conv(m, x, x2=x2, x2_map=x2_map, act=act)
 
 
 def offset_mask_conv_stats(conv_offset, feat):

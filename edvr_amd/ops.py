@@ -91,13 +91,18 @@ def workspace(nbytes, device):
 _PACKED = {}  # id(parameter) -> (weakref, {transpose_flip: (version, packed, data_ptr)})
 
 
-def pack_conv_weight(weight, transpose_flip=False, f4=False, f4s=False):
+def pack_conv_weight(weight, transpose_flip=False, f4=False, f4s=False, ci_range=None):
     """(co, ci, k, k) parameter -> MFMA-friendly [ci_pad][k*k][co_pad] array, cached per parameter version.
+    ci_range = (lo, hi): the packing of weight[:, lo:hi] alone - one half of a two-input conv whose other half is convolved apart
+    (conv2d's `pre`); cached in a slot of its own under the same parameter, version and pointer, so it is invalidated and pinned with the rest.
     f4: the F(4x4,3x3) Winograd weights of a 3x3 kernel instead (conv2d's `wpk_f4`), a separate buffer with its own cache slot.
     f4s: the same weights for the split-operand kernel (conv2d's `wpk_f4s`: scaled, split into f16 (hi, lo) pairs; int32 buffer); of a
     1x1 kernel: the split-operand packing of the streaming 1x1 kernel (csrc/conv1x1_s.hip), same field."""
     require_gpu(weight)
     key, wid, ver = (bool(transpose_flip), 2 if f4s else bool(f4)), id(weight), weight._version
+    if ci_range is not None:
+        assert not transpose_flip, 'input-channel ranges serve forward convs'
+        key = key + ((int(ci_range[0]), int(ci_range[1])),)
     ent = _PACKED.get(wid)
     if ent is not None and ent[0]() is weight:
         hit = ent[1].get(key)
@@ -108,6 +113,8 @@ def pack_conv_weight(weight, transpose_flip=False, f4=False, f4s=False):
         _PACKED[wid] = ent
     L = _lib.lib()
     w = weight.detach()
+    if ci_range is not None:
+        w = w[:, ci_range[0]:ci_range[1]]
     if not w.is_contiguous():
         w = w.contiguous()
     o, i, k, k2 = w.shape
@@ -564,8 +571,10 @@ def amax(x, out=None):
 
 def conv2d(x1, wpk, bias, co, ks, *, x2=None, x2_map=None, stride=1, act=ACT_NONE, act_from=0, res1=None, res2=None,
            out_mode=OUT_NCHW, out=None, algo=None, gate=None, gate_slope=0.0, y_scale=1.0, wpk_f4=None, abs_sum_channels=0,
-           wpk_f4s=None, x_amax=None, want_y_amax=True):
-    """y = y_scale * act(conv(cat(x1, x2)) + bias) + res1 + res2 on the fp32 MFMA kernel.
+           wpk_f4s=None, x_amax=None, want_y_amax=True, pre=None, pre_map=None):
+    """y = y_scale * act(conv(cat(x1, x2)) + bias [+ pre]) + res1 + res2 on the fp32 MFMA kernel.
+    pre (n_pre, co, h, w), pre_map = (div, mul, add) as x2_map: a pre-activation addend, image i of x1 takes image (i // div) * mul + add
+    of it (edvr_conv2d_desc.pre: the F(4x4) Winograd kernels only, no gate / residuals / PixelShuffle - the C side rejects the rest).
     algo: CONV_AUTO (default; module-level CONV_ALGO overrides it, used by tests), CONV_DIRECT, CONV_WINOGRAD or CONV_WINOGRAD_F4.
     wpk_f4: pack_conv_weight(w, f4=True) - allows the F(4x4,3x3) Winograd kernel (inference; ~1e-6 relative rounding error).
 
@@ -617,6 +626,14 @@ def conv2d(x1, wpk, bias, co, ks, *, x2=None, x2_map=None, stride=1, act=ACT_NON
         gate = _as_planes(gate)
         assert tuple(gate.shape) == (n, co, ho, wo), f'gate shape {tuple(gate.shape)}'
         d.gate, d.gate_img_stride, d.gate_slope = _ptr(gate), _img_stride(gate), float(gate_slope)
+    if pre is not None:
+        require_gpu(pre)
+        pre = _as_planes(pre)
+        if tuple(pre.shape[1:]) != (co, ho, wo):
+            raise RuntimeError(f'pre shape {tuple(pre.shape)}: expected (n_pre, {co}, {ho}, {wo})')
+        d.pre, d.pre_img_stride, d.pre_n = _ptr(pre), _img_stride(pre), pre.shape[0]
+        if pre_map is not None:
+            d.pre_div, d.pre_mul, d.pre_add = pre_map
     d.y, d.y_img_stride, d.out_mode = _ptr(out), _img_stride(out), out_mode
     d.y_scale = float(y_scale)
     if wpk_f4 is not None:
@@ -659,8 +676,8 @@ def conv2d(x1, wpk, bias, co, ks, *, x2=None, x2_map=None, stride=1, act=ACT_NON
         if L.edvr_conv2d_executed_flops(ctypes.byref(d), ctypes.byref(ex)) == 0:
             executed = ex.value
         flops = 2.0 * n * ho * wo * co * (c1 + d.c2) * ks * ks
-        # algorithmic HBM bytes: every input / residual / gate / output element once, plus the weights
-        nbytes = 4.0 * (n * (c1 + d.c2) * h * w + n * co * ho * wo * (1 + (res1 is not None) + (res2 is not None) + (gate is not None))
+        # algorithmic HBM bytes: every input / residual / gate / pre / output element once, plus the weights
+        nbytes = 4.0 * (n * (c1 + d.c2) * h * w + n * co * ho * wo * (1 + (res1 is not None) + (res2 is not None) + (gate is not None) + (pre is not None))
                         + co * (c1 + d.c2) * ks * ks)
     _run(name, lambda: _lib.check(L.edvr_conv2d_f32(ctypes.byref(d), _stream()), 'edvr_conv2d_f32'), flops, nbytes, executed)
     if y_bound is not None:
@@ -679,6 +696,21 @@ def conv2d(x1, wpk, bias, co, ks, *, x2=None, x2_map=None, stride=1, act=ACT_NON
         sums[1, ::step] = r[1] * (float(n) / sel.shape[0])
         return out, sums
     return out
+
+
+def conv_pre_supported(n, c, h, w, co, f4s, algo=None):
+    """Would conv2d(..., pre=...) of a 3x3 / stride-1 conv on (n, c, h, w) -> co channels run on a kernel whose epilogue takes the
+    pre-activation addend?  f4s: the call would carry the split-operand weights (and a bound), else the fp32 F(4x4) ones.  (C-side rules:
+    sizes, algorithm request, environment switches.)"""
+    d = _lib.ConvDesc()
+    d.c1, d.n, d.h, d.w, d.co, d.ks, d.stride = c, n, h, w, co, 3, 1
+    d.algo = CONV_ALGO if algo is None else algo
+    any_ptr = ctypes.addressof(d) & ~15  # (any non-null, 16-byte aligned value: only the eligibility rules are evaluated)
+    if f4s:
+        d.wpk_f4s = d.x_amax = any_ptr
+    else:
+        d.wpk_f4 = any_ptr
+    return bool(_lib.lib().edvr_conv2d_pre_supported(ctypes.byref(d)))
 
 
 def conv_gate_supported(n, c, h, w, co, algo=None):

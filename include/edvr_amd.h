@@ -77,7 +77,7 @@ int edvr_check_device(void);
 #define EDVR_OUT_PIXEL_SHUFFLE2 1 /* y[n, co/4, 2h+(co%4)/2, 2w+co%2]  (nn.PixelShuffle(2)) */
 
 /* ------------------------------------------------------------------ conv2d (fp32 MFMA implicit GEMM)
- * y = act(conv(cat(x1, x2), W) + bias) + res1 + res2, kernel ks in {1,3}, pad = ks/2,
+ * y = act(conv(cat(x1, x2), W) + bias [+ pre]) + res1 + res2, kernel ks in {1,3}, pad = ks/2,
  * stride in {1,2}, dilation 1, groups 1.  Weights come pre-packed by
  * edvr_conv2d_pack_weight_f32 (layout [ci_pad][ks*ks][co_pad], co fastest; for 3x3 kernels followed by the
  * Winograd-transformed weights G g G^T as [ci_pad][16][co_pad64]).  3x3 / stride-1 layers with >= 48 output channels
@@ -147,6 +147,19 @@ typedef struct edvr_conv2d_desc {
                            * wave at the end - the `x_amax` of the next conv of a chain for free.  The caller zeroes it (or folds bounds).
                            * The maximum is kept as a BIT PATTERN (non-negative floats order as integers, every NaN above +inf): a
                            * non-finite output is sticky in the slot - an overflow sentinel the host can read (edvr_amd/ops.py split_guard_*). */
+  const float *pre;       /* optional PRE-ACTIVATION addend (pre_n, co, h, w), plane-contiguous: y = act(conv + bias + pre[map(i)]) on every
+                           * output channel, then y_scale / y_amax / abs_sum as without it (both statistics are taken from the final value,
+                           * so a NaN or an infinity in `pre` reaches y, the y_amax slot and the host's guard as one in res1 does).  A
+                           * convolution is linear in its input channels: conv(cat(a, b), W) = conv(a, W[:, :ca]) + conv(b, W[:, ca:]), so
+                           * the half of a two-input conv whose x2 is shared by several images (x2_div / x2_mul / x2_add) can be convolved
+                           * ONCE per shared image, without bias or activation, and enter here (PCDAlignment's offset convs: the reference
+                           * frame's features are shared by the t frames of a clip, edvr_arch.py:64-86).  Only the two F(4x4) Winograd kernels
+                           * implement it (csrc/winograd_f4s.hip, csrc/winograd_f4.hip: it rides in the registers and the prefetch slot of the
+                           * residual / gate, which it therefore excludes), NCHW output only, 16-byte aligned: ask edvr_conv2d_pre_supported;
+                           * EDVR_ERR_UNSUPPORTED otherwise.  NULL: every launch is what it was without this operand, bit for bit. */
+  int64_t pre_img_stride; /* elements between consecutive images of pre (>= co*h*w) */
+  int pre_div, pre_mul, pre_add; /* image map of pre, as x2's: ip = (i / pre_div) * pre_mul + pre_add; pre_div = 0 -> ip = i */
+  int pre_n;              /* images in pre: the map of the last image, n - 1, must stay below it (EDVR_ERR_ARG) */
 } edvr_conv2d_desc;
 
 size_t edvr_conv2d_packed_weight_elems(int co, int ci, int ks);
@@ -196,6 +209,9 @@ int edvr_conv2d_gate_supported(const edvr_conv2d_desc *d);
 int edvr_conv2d_y_amax_supported(const edvr_conv2d_desc *d);
 /* 1 if edvr_conv2d_f32 would run `d` on a kernel whose epilogue takes `abs_sum` (the F(4x4) Winograd kernel), else 0. */
 int edvr_conv2d_abs_sum_supported(const edvr_conv2d_desc *d);
+/* 1 if edvr_conv2d_f32 would run `d` WITH a `pre` operand on a kernel whose epilogue takes it (an F(4x4) Winograd kernel, NCHW output, no
+ * gate, no residuals), else 0.  Of the pointers of `d` only those that select the kernel need to be set (wpk_f4 / wpk_f4s, x_amax). */
+int edvr_conv2d_pre_supported(const edvr_conv2d_desc *d);
 /* Name of the kernel template instantiation edvr_conv2d_f32 would launch for `d` (as rocprofv3 prints it),
  * written to buf; returns 0 or EDVR_ERR_*.  Measurement aid only. */
 int edvr_conv2d_kernel_name(const edvr_conv2d_desc *d, char *buf, size_t buf_len);
