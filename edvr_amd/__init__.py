@@ -3,6 +3,7 @@ hand-written HIP for AMD MI355X (gfx950), behind the module API of xinntao/EDVR.
 
     from edvr_amd import EDVR, PCDAlignment, TSAFusion, PredeblurModule
     from edvr_amd import DCNv2Pack, ModulatedDeformConv, ModulatedDeformConvPack, modulated_deform_conv
+    from edvr_amd import VideoRestorer, window_table   # whole videos: every frame's features extracted once (edvr_amd/video.py)
 
 The kernels live in edvr_amd/lib/libedvr_amd.so (C ABI: include/edvr_amd.h; build with
 `python -m edvr_amd.build`).  There is no CPU or stock-PyTorch fallback: CPU tensors raise
@@ -13,5 +14,6 @@ from .arch_util import DCNv2Pack, ResidualBlockNoBN, default_init_weights, make_
 from .dcn import (DeformConv, DeformConvFunction, DeformConvPack, ModulatedDeformConv,  # noqa: F401
                   ModulatedDeformConvFunction, ModulatedDeformConvPack, deform_conv, modulated_deform_conv)
 from .edvr_arch import EDVR, PCDAlignment, PredeblurModule, TSAFusion  # noqa: F401
+from .video import VideoRestorer, WindowSchedule, window_table  # noqa: F401
 
 __version__ = '0.1.0'

@@ -53,8 +53,11 @@ class ResidualBlockNoBN(nn.Module):
         if not pytorch_init:
             default_init_weights([self.conv1, self.conv2], 0.1)
 
-    def forward(self, x):
+    def forward(self, x, out=None):
+        """out (no-grad calls only): a caller's buffer the second conv writes the block's result into (functional.conv)."""
         c = self.conv1.out_channels
+        if out is not None:
+            return F_.conv(self.conv2, F_.conv(self.conv1, x, act=F_.ACT_RELU), res1=x, y_scale=float(self.res_scale), out=out)
         if (torch.is_grad_enabled() and (x.requires_grad or self.conv1.weight.requires_grad) and x.dim() == 4
                 and self.conv1.in_channels == c and F_.ops.conv_gate_supported(x.shape[0], c, x.shape[2], x.shape[3], c)):
             from . import autograd as ag  # where the Winograd kernel applies: the fused ReLU-backward gate lives in its epilogue

@@ -10,6 +10,7 @@
 // All of them are bandwidth-bound: lanes run along the contiguous pixel axis, 16 B per lane
 // where the shape allows, one pass over each operand.
 #include "common.h"
+#include "pixel.h"
 
 namespace edvr {
 
@@ -72,25 +73,7 @@ __global__ __launch_bounds__(256) void pool_maxavg_kernel(const float *__restric
   }
 }
 
-// ---- bilinear upsampling, align_corners=False: src = (dst + 0.5) / S - 0.5, clamped at 0
-template <int S>
-__device__ __forceinline__ void src_index(int dst, int in, int &i0, int &i1, float &l) {
-  float s = ((float)dst + 0.5f) * (1.f / S) - 0.5f;
-  if (s < 0.f) s = 0.f;
-  i0 = (int)s;
-  i1 = i0 + ((i0 < in - 1) ? 1 : 0);
-  l = s - (float)i0;
-}
-
-// One bilinear sample with the rounding order written out (three fused multiply-adds on two products): every upsampling kernel
-// below calls this, so that their results are bit-identical whichever one a shape / alignment selects - left to -ffp-contract the
-// compiler picks which product of `a * b + c * d` goes into the fma kernel by kernel.
-__device__ __forceinline__ float bilerp(float v00, float v01, float v10, float v11, float lx, float ly) {
-  const float top = __builtin_fmaf(lx, v01, (1.f - lx) * v00);
-  const float bot = __builtin_fmaf(lx, v11, (1.f - lx) * v10);
-  return __builtin_fmaf(ly, bot, (1.f - ly) * top);
-}
-
+// ---- bilinear upsampling, align_corners=False (src_index, bilerp, upsample_at: pixel.h)
 template <int S, bool ADD>
 __global__ __launch_bounds__(256) void upsample_kernel(const float *__restrict__ x, float *__restrict__ y, int nc, int h, int w,
                                                        float scale) {
@@ -100,12 +83,7 @@ __global__ __launch_bounds__(256) void upsample_kernel(const float *__restrict__
     const int ox = (int)(idx % wo);
     const int oy = (int)((idx / wo) % ho);
     const int64_t pl = idx / ((int64_t)wo * ho);
-    int y0, y1, x0, x1;
-    float ly, lx;
-    src_index<S>(oy, h, y0, y1, ly);
-    src_index<S>(ox, w, x0, x1, lx);
-    const float *src = x + pl * h * w;
-    const float v = bilerp(src[y0 * w + x0], src[y0 * w + x1], src[y1 * w + x0], src[y1 * w + x1], lx, ly);
+    const float v = upsample_at<S>(x + pl * h * w, h, w, oy, ox);
     if (ADD)
       y[idx] += v;
     else

@@ -9,10 +9,9 @@
 #include <cmath>
 
 #include "common.h"
+#include "pixel.h"  // to_u8: clamp, x255, np.round (half to even)
 
 namespace edvr {
-
-__device__ __forceinline__ float to_u8(float v) { return rintf(fminf(fmaxf(v, 0.f), 1.f) * 255.f); }  // np.round: half to even
 
 // Y of one pixel as to_y_channel computes it: BGR image of the reference = channels (2, 1, 0) of the RGB tensor; float32 / 255,
 // dot with the BT.601 row in double, + 16, / 255 -> float32, x 255 in float32.  NOT inlined: the two images must run the very

@@ -1,0 +1,40 @@
+// Per-pixel expressions shared by several translation units.  Kernels that must agree BIT FOR BIT - the float and the uint8 form of
+// the network's last step, the PSNR kernel's and the output kernels' byte conversion - call these instead of restating them.
+#pragma once
+#include <hip/hip_runtime.h>
+
+namespace edvr {
+
+// tensor2img (basicsr/utils/img_util.py:36-98) of one value: clamp to [0, 1], x 255, np.round (half to even); an integer in [0, 255]
+__device__ __forceinline__ float to_u8(float v) { return rintf(fminf(fmaxf(v, 0.f), 1.f) * 255.f); }
+
+// ---- bilinear upsampling, align_corners=False: src = (dst + 0.5) / S - 0.5, clamped at 0
+template <int S>
+__device__ __forceinline__ void src_index(int dst, int in, int &i0, int &i1, float &l) {
+  float s = ((float)dst + 0.5f) * (1.f / S) - 0.5f;
+  if (s < 0.f) s = 0.f;
+  i0 = (int)s;
+  i1 = i0 + ((i0 < in - 1) ? 1 : 0);
+  l = s - (float)i0;
+}
+
+// One bilinear sample with the rounding order written out (three fused multiply-adds on two products): every upsampling kernel
+// calls this, so that their results are bit-identical whichever one a shape / alignment selects - left to -ffp-contract the
+// compiler picks which product of `a * b + c * d` goes into the fma kernel by kernel.
+__device__ __forceinline__ float bilerp(float v00, float v01, float v10, float v11, float lx, float ly) {
+  const float top = __builtin_fmaf(lx, v01, (1.f - lx) * v00);
+  const float bot = __builtin_fmaf(lx, v11, (1.f - lx) * v10);
+  return __builtin_fmaf(ly, bot, (1.f - ly) * top);
+}
+
+// Output pixel (oy, ox) of the xS bilinear enlargement of one h x w plane (S = 4: the value edvr_upsample4x_add_f32 adds to y there).
+template <int S>
+__device__ __forceinline__ float upsample_at(const float *__restrict__ src, int h, int w, int oy, int ox) {
+  int y0, y1, x0, x1;
+  float ly, lx;
+  src_index<S>(oy, h, y0, y1, ly);
+  src_index<S>(ox, w, x0, x1, lx);
+  return bilerp(src[y0 * w + x0], src[y0 * w + x1], src[y1 * w + x0], src[y1 * w + x1], lx, ly);
+}
+
+}  // namespace edvr

@@ -244,19 +244,45 @@ class EDVR(nn.Module):
                 first = self.predeblur.conv_first if self.with_predeblur else self.conv_first
                 self._conv_meta = [(m.stride[0] == 1, m is not first) for m in convs]
             F_.ops.prepack_conv_weights(self._conv_weights, self._conv_meta)
-        frames = x.view(b * t, c, h, w)
+        pyr = self.extract_features(x.view(b * t, c, h, w))
+        return self.restore_from_features(pyr, x[:, ctr], b, t)
+
+    def extract_features(self, frames, out=None):
+        """The PER-FRAME stage: frames (n, c, H, W) -> the feature pyramid [f1, f2, f3] ((n, C, h, w), half and quarter size; (h, w) =
+        (H, W), or (H / 4, W / 4) with hr_in).  Nothing here looks at another frame, so a whole-video run computes it once per frame
+        (edvr_amd/video.py) where `forward` computes it once per frame of every window.
+        out (no-grad calls only): three buffers of those shapes with dense images (slices of a feature bank) that the last conv of each
+        level writes in place - no copy; the returned tensors are `out`'s, with their magnitude bounds attached."""
         if F_.ops.F4S_INFERENCE or F_.ops.F4S_TRAINING:
             F_.ops.input_bound(frames)  # max |input| (one pass over 3-channel frames): the first link of the chain of magnitude bounds
+        o1, o2, o3 = out if out is not None else (None, None, None)
+        blocks = list(self.feature_extraction) if out is not None else []
+        head = None if blocks else o1  # (a network without extraction blocks: the first conv is level 1's producer)
         if self.with_predeblur:
-            f1 = F_.conv(self.conv_1x1, self.predeblur(frames))
-            if self.hr_in:
-                h, w = h // 4, w // 4
+            f1 = F_.conv(self.conv_1x1, self.predeblur(frames), out=head)
         else:
-            f1 = F_.conv(self.conv_first, frames, act=LRELU)
-        f1 = self.feature_extraction(f1)
-        f2 = F_.conv(self.conv_l2_2, F_.conv(self.conv_l2_1, f1, act=LRELU), act=LRELU)
-        f3 = F_.conv(self.conv_l3_2, F_.conv(self.conv_l3_1, f2, act=LRELU), act=LRELU)
+            f1 = F_.conv(self.conv_first, frames, act=LRELU, out=head)
+        if out is None:
+            f1 = self.feature_extraction(f1)
+        else:
+            for i, blk in enumerate(blocks):
+                f1 = blk(f1, out=o1 if i == len(blocks) - 1 else None)
+        f2 = F_.conv(self.conv_l2_2, F_.conv(self.conv_l2_1, f1, act=LRELU), act=LRELU, out=o2)
+        f3 = F_.conv(self.conv_l3_2, F_.conv(self.conv_l3_1, f2, act=LRELU), act=LRELU, out=o3)
+        return [f1, f2, f3]
 
+    def restore_from_features(self, pyr, x_center, b, t, out_dtype=torch.float32):
+        """Everything after the per-frame stage.  pyr = [f1, f2, f3]: the b * t window images of each level, clip after clip (image
+        i * t + j = frame j of output frame i's window), x_center (b, c, H, W): the input frames the outputs are residuals of.
+        out_dtype=torch.uint8 (no-grad calls only): the result as (b, H', W', 3) bytes with tensor2img semantics (clamp, x 255, round
+        half to even) - the last step writes them instead of the float tensor."""
+        if out_dtype not in (torch.float32, torch.uint8):
+            raise ValueError(f'out_dtype must be torch.float32 or torch.uint8, got {out_dtype}')
+        if out_dtype == torch.uint8 and torch.is_grad_enabled():
+            raise RuntimeError('the uint8 output of EDVR.restore_from_features has no backward: call it under torch.no_grad()')
+        f1, f2, f3 = pyr
+        ctr = self.center_frame_idx
+        h, w = f1.shape[2], f1.shape[3]
         # all b*t frames aligned in one pass; frame i pairs with the centre frame of its clip
         sink = []
         dcns = self.pcd_align.dcn_modules()
@@ -280,13 +306,16 @@ class EDVR(nn.Module):
         out = F_.conv(self.upconv1, out, act=LRELU, out_mode=F_.OUT_PIXEL_SHUFFLE2)
         out = F_.conv(self.upconv2, out, act=LRELU, out_mode=F_.OUT_PIXEL_SHUFFLE2)
         out = F_.conv(self.conv_hr, out, act=LRELU)
-        x_center = x[:, ctr]
         if self.hr_in:
             out = F_.conv(self.conv_last, out, res1=x_center)
+            if out_dtype == torch.uint8:
+                out = F_.ops.f32_to_u8_hwc(out)
+        elif out_dtype == torch.uint8:
+            out = F_.ops.upsample4x_add_u8(F_.conv(self.conv_last, out), x_center)
         else:
             out = F_.upsample4x_add(F_.conv(self.conv_last, out), x_center)
         self._queue_offset_check(sink, b, t)
-        F_.ops.split_guard_submit(x.device)
+        F_.ops.split_guard_submit(f1.device)
         return out
 
     def _queue_offset_check(self, sink, b, t):

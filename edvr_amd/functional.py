@@ -28,11 +28,12 @@ def _needs_grad(*ts):
 
 
 def conv(m, x, *, x2=None, x2_map=None, act=ACT_NONE, act_from=0, res1=None, res2=None, out_mode=OUT_NCHW, y_scale=1.0,
-         abs_sum_channels=0, ci_range=None, use_bias=True, pre=None, pre_map=None):
+         abs_sum_channels=0, ci_range=None, use_bias=True, pre=None, pre_map=None, out=None):
     """y_scale * act(conv(cat(x, x2)) + bias) + res1 + res2 with the parameters of nn.Conv2d `m`.
     abs_sum_channels > 0 (no-grad calls only): returns (y, per-image sums of |y[:, :abs_sum_channels]|), ops.conv2d.
     No-grad calls only (conv_shared_x2 is their user): ci_range = (lo, hi) convolves with m.weight[:, lo:hi] alone, use_bias=False leaves
-    the bias out, pre / pre_map add a tensor BEFORE the activation (ops.conv2d)."""
+    the bias out, pre / pre_map add a tensor BEFORE the activation (ops.conv2d); out = a caller's buffer the kernel writes in place
+    (dense images, any image stride - a slice of a feature bank, edvr_amd/video.py), returned with its new magnitude bound attached."""
     ks, stride = _conv_geometry(m)
     if x.dim() != 4:
         raise ValueError(f'expected a 4-D input, got {tuple(x.shape)}')
@@ -44,8 +45,8 @@ def conv(m, x, *, x2=None, x2_map=None, act=ACT_NONE, act_from=0, res1=None, res
     if _needs_grad(x, x2, m.weight, m.bias, res1, res2, pre):
         from . import autograd as ag
         assert abs_sum_channels == 0
-        if ci_range is not None or not use_bias or pre is not None:
-            raise NotImplementedError('ci_range / use_bias / pre are inference-only arguments of conv()')
+        if ci_range is not None or not use_bias or pre is not None or out is not None:
+            raise NotImplementedError('ci_range / use_bias / pre / out are inference-only arguments of conv()')
         return ag.conv(m, x, x2, x2_map, act, act_from, res1, res2, out_mode, ks, stride, y_scale)
     wpk = ops.pack_conv_weight(m.weight, ci_range=ci_range)
     # the F(4x4,3x3) Winograd weights let the C side pick that kernel where it is the fastest (2.25 instead of 4 multiplies per
@@ -63,7 +64,7 @@ def conv(m, x, *, x2=None, x2_map=None, act=ACT_NONE, act_from=0, res1=None, res
     bias = m.bias.detach() if (m.bias is not None and use_bias) else None
     r = ops.conv2d(x, wpk, bias, m.out_channels, ks, x2=x2, x2_map=x2_map, stride=stride, act=act, act_from=act_from,
                    res1=res1, res2=res2, out_mode=out_mode, y_scale=y_scale, wpk_f4=wf4, abs_sum_channels=abs_sum_channels,
-                   wpk_f4s=wf4s, pre=pre, pre_map=pre_map)
+                   wpk_f4s=wf4s, pre=pre, pre_map=pre_map, out=out)
     y = r[0] if abs_sum_channels > 0 else r
     if ops.F4S_INFERENCE and ops.get_bound(y) is None:  # a kernel without the y_amax epilogue: the bound from the weights' norms
         # (of the WHOLE weight also where a channel range of it ran: a sum over more channels, still a bound)

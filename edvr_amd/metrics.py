@@ -105,3 +105,18 @@ def validate_clip(net, lq, gt=None, num_frame=5, padding='reflection_circle', ba
         if gt is not None:
             scores += calculate_psnr(out, gt[s0:s0 + out.shape[0]], crop_border, test_y_channel)
     return torch.cat(outs, 0), (scores if gt is not None else None)
+
+
+@torch.no_grad()
+def validate_video(net, lq, gt=None, num_frame=5, padding='reflection_circle', chunk=8, crop_border=0, test_y_channel=False):
+    """validate_clip with every frame's features extracted once (edvr_amd/video.py: VideoRestorer) instead of once per window it
+    appears in; `chunk` output frames per alignment / fusion / reconstruction pass.  Same arguments otherwise, same return value:
+    (outputs (t, c, H, W), [PSNR per frame] or None)."""
+    from .video import VideoRestorer
+    outs, scores, s0 = [], [], 0
+    for out in VideoRestorer(net, num_frame=num_frame, padding=padding, chunk=chunk).restore_chunks(lq.split(chunk), length=lq.shape[0]):
+        outs.append(out)
+        if gt is not None:
+            scores += calculate_psnr(out, gt[s0:s0 + out.shape[0]], crop_border, test_y_channel)
+        s0 += out.shape[0]
+    return torch.cat(outs, 0), (scores if gt is not None else None)

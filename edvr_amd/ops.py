@@ -607,11 +607,12 @@ def conv2d(x1, wpk, bias, co, ks, *, x2=None, x2_map=None, stride=1, act=ACT_NON
     d.act, d.act_from = act, act_from
     pad = ks // 2
     ho, wo = (h + 2 * pad - ks) // stride + 1, (w + 2 * pad - ks) // stride + 1
+    shape = (n, co // 4, 2 * ho, 2 * wo) if out_mode == OUT_PIXEL_SHUFFLE2 else (n, co, ho, wo)
     if out is None:
-        shape = (n, co // 4, 2 * ho, 2 * wo) if out_mode == OUT_PIXEL_SHUFFLE2 else (n, co, ho, wo)
         out = torch.empty(shape, dtype=torch.float32, device=x1.device)
     else:
-        assert _plane_contig(out)
+        require_gpu(out)
+        assert _plane_contig(out) and tuple(out.shape) == shape, f'out {tuple(out.shape)} / strides {out.stride()}: expected dense images of shape {shape}'
     for name, r in (('res1', res1), ('res2', res2)):
         if r is not None:
             r = _as_planes(r)
@@ -1246,4 +1247,71 @@ def frames_u8_to_f32(frames_u8, flags=None, swap_rb=False):
     if n:
         _lib.check(_lib.lib().edvr_frames_u8_to_f32(_ptr(frames_u8), _ptr(out), n, f, h, w, fl, int(bool(swap_rb)), _stream()),
                    'edvr_frames_u8_to_f32')
+    return out
+
+
+# ------------------------------------------------------------------------------------------------ whole-video path (edvr_amd/video.py)
+GATHER_MAX_LEVELS = 3  # EDVR_GATHER_MAX_LEVELS
+
+
+def gather_images(srcs, table, outs=None):
+    """outs[l][j] = srcs[l][table[j]] for up to three tensors in ONE launch (edvr_gather_images_f32): srcs[l] (n_src, c_l, h_l, w_l)
+    with dense images and any image stride (slices / ring positions of a larger bank), table a DEVICE int32 vector (stream-ordered, no
+    host synchronisation), outs[l] contiguous (len(table), c_l, h_l, w_l) - allocated when None.  A gather cannot enlarge anything:
+    each destination takes its source's magnitude bound (set_bound on the bank tensor)."""
+    srcs = list(srcs)
+    require_gpu(*srcs)
+    if not 1 <= len(srcs) <= GATHER_MAX_LEVELS:
+        raise ValueError(f'gather_images takes 1..{GATHER_MAX_LEVELS} tensors, got {len(srcs)}')
+    if not table.is_cuda:
+        raise NotImplementedError('edvr_amd ops run on the GPU only (HIP/gfx950); got a CPU tensor')
+    if table.dtype != torch.int32 or table.dim() != 1 or not table.is_contiguous() or table.numel() == 0:
+        raise ValueError(f'table must be a non-empty contiguous int32 vector, got {table.dtype} {tuple(table.shape)}')
+    n_src, n_out = srcs[0].shape[0], table.numel()
+    for s in srcs:
+        if s.dim() != 4 or s.shape[0] != n_src or not _plane_contig(s):
+            raise ValueError(f'gather_images: sources must be (n_src, c, h, w) tensors with dense images and one n_src, got {tuple(s.shape)} / strides {s.stride()}')
+    if outs is None:
+        outs = [torch.empty((n_out,) + tuple(s.shape[1:]), dtype=torch.float32, device=s.device) for s in srcs]
+    else:
+        outs = list(outs)
+        require_gpu(*outs)
+        assert len(outs) == len(srcs) and all(o.is_contiguous() and tuple(o.shape) == (n_out,) + tuple(s.shape[1:]) for o, s in zip(outs, srcs))
+    k = len(srcs)
+    P, I = ctypes.c_void_p * k, ctypes.c_int64 * k
+    per = [s.shape[1] * s.shape[2] * s.shape[3] for s in srcs]
+    a_src, a_dst = P(*[s.data_ptr() for s in srcs]), P(*[o.data_ptr() for o in outs])
+    a_str, a_per = I(*[_img_stride(s) for s in srcs]), I(*per)
+    _run('gather_images', lambda: _lib.check(_lib.lib().edvr_gather_images_f32(a_src, a_dst, a_str, a_per, k, _ptr(table), n_out, n_src, _stream()),
+                                             'edvr_gather_images_f32'), 0, 8.0 * n_out * sum(per))
+    for o, s in zip(outs, srcs):
+        void_bound(o)
+        carry_bound(o, s)
+    return outs
+
+
+def upsample4x_add_u8(y, base):
+    """tensor2img(y + bilinear_x4(base)) as (n, 4h, 4w, 3) uint8: the bytes of upsample4x_add_'s float result, without storing it."""
+    require_gpu(y, base)
+    base = base.contiguous()
+    n, c, h, w = base.shape
+    if c != 3:
+        raise NotImplementedError(f'the uint8 output is interleaved RGB: 3 channels, got {c}')
+    assert y.is_contiguous() and tuple(y.shape) == (n, c, 4 * h, 4 * w)
+    out = torch.empty(n, 4 * h, 4 * w, 3, dtype=torch.uint8, device=y.device)
+    _run('upsample4x_add_u8', lambda: _lib.check(_lib.lib().edvr_upsample4x_add_u8(_ptr(y), _ptr(base), _ptr(out), n, h, w, _stream()),
+                                                 'edvr_upsample4x_add_u8'), 0, _nb(base, y) + out.numel())
+    return out
+
+
+def f32_to_u8_hwc(x):
+    """tensor2img semantics on the device: (n, 3, h, w) float32 -> (n, h, w, 3) uint8 = round-half-even(clamp(x, 0, 1) * 255)."""
+    require_gpu(x)
+    x = _as_planes(x)
+    n, c, h, w = x.shape
+    if c != 3:
+        raise NotImplementedError(f'the uint8 output is interleaved RGB: 3 channels, got {c}')
+    out = torch.empty(n, h, w, 3, dtype=torch.uint8, device=x.device)
+    _run('f32_to_u8_hwc', lambda: _lib.check(_lib.lib().edvr_f32_to_u8_hwc(_ptr(x), _ptr(out), n, h, w, _img_stride(x), _stream()),
+                                             'edvr_f32_to_u8_hwc'), 0, _nb(x) + out.numel())
     return out

@@ -1,0 +1,295 @@
+"""Whole-video restoration: every frame's features are extracted ONCE.
+
+`EDVR.forward` takes a window of `num_frame` neighbours per output frame, and `metrics.validate_clip` restores a video by building
+one window per frame (generate_frame_indices, basicsr/data/data_util.py:35-88) - as the reference does (video_base_model.py:44-98).
+The network's per-frame stage (`EDVR.extract_features`: conv_first / predeblur, the extraction blocks, the two pyramid convs) then runs
+num_frame times on every frame although its result depends on the frame alone.  `VideoRestorer` runs it once per frame into a bounded
+feature BANK and builds each chunk of windows by one gather launch (ops.gather_images) over the bank; alignment, fusion and
+reconstruction (`EDVR.restore_from_features`) see exactly the tensors a `forward` of `chunk` windows would compute.
+
+No-grad inference only: there is no backward through the bank.
+"""
+import torch
+
+from . import ops
+from .metrics import generate_frame_indices
+
+_CIRCLE = ('reflection_circle', 'circle')
+
+
+def window_table(n_frames, num_frame, padding='reflection_circle'):
+    """(n_frames, num_frame) int32 table (CPU): row i = generate_frame_indices(i, n_frames, num_frame, padding), the frames of output
+    frame i's window.  A video too short for the padding mode (an index outside [0, n_frames)) is a ValueError."""
+    rows = [generate_frame_indices(i, n_frames, num_frame, padding) for i in range(n_frames)]
+    if any(not 0 <= f < n_frames for r in rows for f in r):
+        raise ValueError(f"a video of {n_frames} frame(s) is too short for windows of {num_frame} with '{padding}' padding")
+    return torch.tensor(rows, dtype=torch.int32).reshape(n_frames, num_frame)
+
+
+class WindowSchedule:
+    """Which frames to extract and which output frames to restore, as frames of a video of UNKNOWN length arrive (pure Python).
+
+    push(k) - k more frames have arrived - and finish() generate steps in execution order (the state below advances with them):
+        ('extract', first, count)   run the per-frame stage on frames [first, first + count) (each frame exactly once, in order)
+        ('restore', first, rows)    restore output frames first, first + 1, ...; rows[j] = the window of output frame first + j
+    After a step, frames below `lo` are dead.  A window whose far end lies `num_frame // 2` frames ahead is known as soon as that frame
+    has arrived (the padding of the first frames reads forward only: up to frame num_frame - 1 in the circle modes); the last
+    num_frame // 2 windows depend on the length and come from finish().  Output frames leave in groups of `chunk` (what is left at the
+    end in up to two smaller ones), so the launches of a group have the shapes of a forward with b = chunk.
+
+    What stays alive: the frames the next group's windows reach back to (num_frame // 2 behind its first frame) and - the video may end
+    with the latest frame, and the circle modes then reach num_frame - 1 frames back from it - the latest num_frame extracted frames.
+    `capacity` is the largest number of live frames any length produces (found by running the schedule itself over short and long
+    videos; it never exceeds chunk + 2 * (num_frame - 1)): the size of the ring the bank is kept in."""
+
+    def __init__(self, num_frame, padding='reflection_circle', chunk=8, _probe=True):
+        if num_frame < 1 or num_frame % 2 == 0:
+            raise ValueError(f'num_frame must be odd, got {num_frame}')
+        if padding not in ('replicate', 'reflection', 'reflection_circle', 'circle'):
+            raise ValueError(f'Wrong padding mode: {padding}.')
+        if chunk < 1:
+            raise ValueError(f'chunk must be at least 1, got {chunk}')
+        self.t, self.p, self.padding, self.chunk = num_frame, num_frame // 2, padding, int(chunk)
+        self.back = num_frame - 1 if (padding in _CIRCLE and num_frame > 1) else self.p  # how far the last windows reach back from the last frame
+        self.arrived = self.ext = self.out = self.lo = 0
+        self.peak = 0
+        if _probe:
+            limit = self.chunk + 2 * (num_frame - 1)
+            self.capacity = max(self._peak_of(n) for n in range(num_frame, 3 * (self.chunk + num_frame) + 2))
+            assert self.capacity <= max(limit, 1), (self.capacity, limit)
+
+    def _peak_of(self, n):
+        s = WindowSchedule(self.t, self.padding, self.chunk, _probe=False)
+        for _ in range(n):
+            for _step in s.push(1):
+                pass
+        for _step in s.finish():
+            pass
+        return s.peak
+
+    def _complete(self, i):
+        """Is the window of output frame i known and present (without knowing the length)?"""
+        need = i + self.p
+        if i < self.p and self.padding in _CIRCLE:
+            need = max(need, self.t - 1)
+        return need <= self.arrived - 1
+
+    def _group(self, first, rows):
+        hi = max(max(r) for r in rows)
+        if hi >= self.ext:
+            step = ('extract', self.ext, hi + 1 - self.ext)
+            self.ext = hi + 1
+            self.peak = max(self.peak, self.ext - self.lo)
+            yield step
+        assert min(min(r) for r in rows) >= self.lo, 'a window reaches behind the live frames'
+        yield ('restore', first, rows)
+        self.out = first + len(rows)
+        keep = self.out - self.p
+        if self.back > self.p:
+            keep = min(keep, self.ext - 1 - self.back)
+        self.lo = max(self.lo, min(keep, self.ext))
+
+    def push(self, k=1):
+        """k more frames have arrived: a generator of the steps that have become possible (the state advances as it is consumed)."""
+        self.arrived += int(k)
+        while self._complete(self.out + self.chunk - 1):
+            first = self.out
+            rows = [generate_frame_indices(i, self.arrived, self.t, self.padding) for i in range(first, first + self.chunk)]
+            yield from self._group(first, rows)
+
+    def finish(self):
+        """The input has ended: the steps for the output frames still owed."""
+        n = self.arrived
+        if self.out < n:
+            table = window_table(n, self.t, self.padding).tolist()
+            while self.out < n:
+                first = self.out
+                yield from self._group(first, table[first:min(first + self.chunk, n)])
+
+
+class VideoRestorer:
+    """Restore whole videos with `net` (an EDVR in eval mode, on the GPU), extracting every frame's features once.
+
+        vr = VideoRestorer(net, padding='reflection_circle', chunk=8)
+        out = vr.restore(lq)                       # (N, 3, H, W) float32 in [0, 1] or (N, H, W, 3) uint8 -> all N restored frames
+        for frame in vr.restore_iter(frames): ...  # streaming: frames (or small batches of them) in, restored frames out, in order
+
+    num_frame: the network's window (None: read from its fusion layer); padding: generate_frame_indices' mode for the first and last
+    frames; chunk: output frames per alignment / fusion / reconstruction pass (= `validate_clip`'s batch);
+    out_dtype: torch.float32 -> (N, 3, H', W') as `forward` returns them, torch.uint8 -> (N, H', W', 3) bytes with tensor2img
+    semantics (clamp, x 255, round half to even), written by the network's last kernel.
+
+    The bank holds the three pyramid levels of at most `capacity` <= chunk + 2 * (num_frame - 1) frames whatever the length of the
+    video; the input frames are kept (as views of what the caller handed in, or as the converted uint8 pieces) until no window's
+    centre needs them.  Around every chunk the bookkeeping of a forward happens: offset statistics and overflow flags of earlier
+    chunks that have reached the host are examined before, this chunk's are sent after; nothing waits for the GPU -
+    `net.check_offsets()` after the last chunk evaluates what is still on its way, as after a run of forwards."""
+
+    def __init__(self, net, num_frame=None, padding='reflection_circle', chunk=8, out_dtype=torch.float32):
+        if out_dtype not in (torch.float32, torch.uint8):
+            raise ValueError(f'out_dtype must be torch.float32 or torch.uint8, got {out_dtype}')
+        self.net, self.padding, self.chunk, self.out_dtype = net, padding, int(chunk), out_dtype
+        self.num_feat = net.conv_l2_1.in_channels
+        if num_frame is None:
+            fusion = net.fusion.feat_fusion if getattr(net, 'with_tsa', True) else net.fusion
+            num_frame = fusion.in_channels // self.num_feat
+        self.num_frame = int(num_frame)
+        ctr = getattr(net, 'center_frame_idx', self.num_frame // 2)
+        if ctr != self.num_frame // 2:
+            raise ValueError(f'windows are centred on the frame they restore: center_frame_idx {ctr} != num_frame // 2 = {self.num_frame // 2}')
+        self.capacity = WindowSchedule(self.num_frame, padding, self.chunk).capacity
+        self.bank = None        # [f1, f2, f3] rings of `slots` images; frame f lives in image f % slots
+        self.slots = 0
+        self.schedule = None    # the WindowSchedule of the running restore
+        self._groups = []       # (first frame, count, [bound or None per level], [depth per level]) of every extract call with live frames
+        self._pieces = []       # (first frame, float32 (k, 3, H, W)) input frames not dead yet
+
+    # ---- device primitives (the schedule test replaces them by CPU stand-ins)
+    def _check_input(self, t):
+        if not t.is_cuda:
+            raise NotImplementedError('edvr_amd ops run on the GPU only (HIP/gfx950); got a CPU tensor')
+
+    def _slot_table(self, slots, device):
+        host = torch.tensor(slots, dtype=torch.int32).pin_memory()  # (pinned + non_blocking: the host does not wait for the stream)
+        return host.to(device, non_blocking=True)
+
+    def _gather(self, srcs, table):
+        return ops.gather_images(srcs, table)
+
+    # ---- input
+    def _check_mode(self):
+        if self.net.training:
+            raise RuntimeError('VideoRestorer is an inference path: put the network in eval() mode')
+        if torch.is_grad_enabled():
+            raise RuntimeError('VideoRestorer has no backward (features are written into a bank in place): call it under torch.no_grad()')
+
+    def _as_frames(self, item):
+        """One frame or a batch of frames, float32 CHW in [0, 1] or uint8 HWC -> float32 (k, 3, H, W)."""
+        self._check_input(item)
+        if item.dtype == torch.uint8:
+            if item.dim() == 3:
+                item = item[None]
+            if item.dim() != 4 or item.shape[-1] != 3:
+                raise ValueError(f'uint8 frames are (H, W, 3) or (k, H, W, 3), got {tuple(item.shape)}')
+            return ops.frames_u8_to_f32(item[None])[0]
+        if item.dtype != torch.float32:
+            raise NotImplementedError(f'edvr_amd: {item.dtype} frames are not supported here (float32 CHW in [0, 1] or uint8 HWC)')
+        if item.dim() == 3:
+            item = item[None]
+        if item.dim() != 4:
+            raise ValueError(f'float32 frames are (3, H, W) or (k, 3, H, W), got {tuple(item.shape)}')
+        return item
+
+    def _frames(self, a, b):
+        """Input frames [a, b) as one (b - a, 3, H, W) tensor: a view where one piece holds them all."""
+        parts = []
+        for first, piece in self._pieces:
+            lo, hi = max(a, first), min(b, first + piece.shape[0])
+            if lo < hi:
+                parts.append(piece[lo - first:hi - first])
+        assert sum(p.shape[0] for p in parts) == b - a, f'input frames [{a}, {b}) are not all held'
+        return parts[0] if len(parts) == 1 else torch.cat(parts, 0)
+
+    # ---- bank
+    def _pyramid_shapes(self, h, w):
+        net = self.net
+        if net.hr_in:
+            assert h % 16 == 0 and w % 16 == 0, 'The height and width must be multiple of 16.'
+        else:
+            assert h % 4 == 0 and w % 4 == 0, 'The height and width must be multiple of 4.'
+        if net.hr_in and net.with_predeblur:
+            h, w = h // 4, w // 4
+        h2, w2 = (h - 1) // 2 + 1, (w - 1) // 2 + 1
+        return [(self.num_feat, h, w), (self.num_feat, h2, w2), (self.num_feat, (h2 - 1) // 2 + 1, (w2 - 1) // 2 + 1)]
+
+    @property
+    def bank_frames(self):
+        """Frames the bank holds right now (extracted and not dead)."""
+        return 0 if self.schedule is None else self.schedule.ext - self.schedule.lo
+
+    def _extract(self, first, count, length):
+        frames = self._frames(first, first + count)
+        if self.bank is None:
+            self.slots = self.capacity if length is None else max(1, min(self.capacity, length))
+            self.bank = [torch.empty((self.slots,) + s, dtype=torch.float32, device=frames.device)
+                         for s in self._pyramid_shapes(frames.shape[2], frames.shape[3])]
+        if self.schedule.ext - self.schedule.lo > self.slots:
+            raise RuntimeError(f'VideoRestorer: {self.schedule.ext - self.schedule.lo} live frames do not fit the bank of {self.slots}')
+        done = 0
+        while done < count:  # a group that crosses the end of the ring is extracted in two parts
+            slot = (first + done) % self.slots
+            m = min(count - done, self.slots - slot)
+            pyr = self.net.extract_features(frames[done:done + m], out=[lv[slot:slot + m] for lv in self.bank])
+            bounds = [ops.get_bound(f) for f in pyr]
+            self._groups.append((first + done, m, bounds, [ops._bound_depth(f) if b is not None else 0 for f, b in zip(pyr, bounds)]))
+            done += m
+
+    def _bank_bounds(self):
+        """The bank's magnitude bound per level = the largest bound of the live extract groups (none where a group has none)."""
+        lo = self.schedule.lo
+        self._groups = [g for g in self._groups if g[0] + g[1] > lo]
+        for lv, bank in enumerate(self.bank):
+            bs = [g[2][lv] for g in self._groups]
+            ops.void_bound(bank)
+            if bs and all(b is not None for b in bs):
+                b = bs[0]
+                for o in bs[1:]:
+                    b = torch.maximum(b, o)
+                ops.set_bound(bank, b, max(g[3][lv] for g in self._groups))
+
+    def _restore(self, first, rows):
+        net, t = self.net, self.num_frame
+        net.check_offsets(wait=False)  # what a forward does before its launches: statistics / overflow flags that have landed
+        if self.bank[0].is_cuda:
+            ops.split_guard_check(wait=False)
+        self._bank_bounds()
+        table = self._slot_table([f % self.slots for r in rows for f in r], self.bank[0].device)
+        pyr = self._gather(self.bank, table)
+        return net.restore_from_features(pyr, self._frames(first, first + len(rows)), len(rows), t, out_dtype=self.out_dtype)
+
+    # ---- public
+    def _run(self, steps, length):
+        for kind, first, arg in steps:
+            self._check_mode()
+            if kind == 'extract':
+                self._extract(first, arg, length)
+            else:
+                out = self._restore(first, arg)
+                nxt = first + len(arg)  # input frames are read by their extraction and as their own output's residual base
+                self._pieces = [(f, p) for f, p in self._pieces if f + p.shape[0] > nxt]
+                yield out
+
+    def restore_chunks(self, frames, length=None):
+        """restore_iter that yields each chunk's output tensor ((b, 3, H', W') or (b, H', W', 3)) instead of single frames.
+        length: the number of frames if known - a video shorter than `capacity` then gets a smaller bank."""
+        self._check_mode()
+        self.schedule = sched = WindowSchedule(self.num_frame, self.padding, self.chunk, _probe=False)
+        self.bank, self._groups, self._pieces = None, [], []
+        try:
+            for item in frames:
+                piece = self._as_frames(item)
+                if piece.shape[0] == 0:
+                    continue
+                self._pieces.append((sched.arrived, piece))
+                yield from self._run(sched.push(piece.shape[0]), length)
+            yield from self._run(sched.finish(), length)
+        finally:
+            self.bank, self._groups, self._pieces = None, [], []  # (the schedule stays for inspection)
+
+    def restore_iter(self, frames, length=None):
+        """Streaming form: `frames` is an iterable of frames ((3, H, W) float32 / (H, W, 3) uint8) or of small batches of them, of
+        unknown length; yields the restored frames in order, each as soon as its chunk of windows is complete - the last
+        num_frame // 2 (whose padding depends on the length) when the input ends."""
+        for out in self.restore_chunks(frames, length):
+            yield from out.unbind(0)
+
+    def restore(self, lq):
+        """lq: (N, 3, H, W) float32 in [0, 1] or (N, H, W, 3) uint8, on the GPU -> all N restored frames."""
+        self._check_mode()
+        self._check_input(lq)
+        if lq.dim() != 4:
+            raise ValueError(f'expected (N, 3, H, W) float32 or (N, H, W, 3) uint8 frames, got {tuple(lq.shape)}')
+        if lq.shape[0] == 0:
+            raise ValueError('restore: no frames')
+        outs = list(self.restore_chunks(lq.split(self.chunk), length=lq.shape[0]))
+        return outs[0] if len(outs) == 1 else torch.cat(outs, 0)

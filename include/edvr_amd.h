@@ -468,6 +468,23 @@ int edvr_ssim_f32(const float *a, const float *b, double *partial, int n, int c,
 int edvr_frames_u8_to_f32(const uint8_t *src, float *dst, int n_clips, int frames_per_clip, int h, int w,
                           const uint8_t *clip_flags, int swap_rb, edvr_stream_t stream);
 
+/* Whole-video restoration (edvr_amd/video.py): every frame's feature pyramid is computed once and kept in a bank; the window of an
+ * output frame (generate_frame_indices, basicsr/data/data_util.py:35-88) is a gather of bank images.
+ * One launch, for `levels` (1..EDVR_GATHER_MAX_LEVELS) tensors at once: image j of dst[l] (contiguous, per_img[l] floats per image)
+ * = image table[j] of src[l] (src_img_stride[l] floats between images: slices and ring positions of a larger bank work), j < n_out.
+ * src / dst / src_img_stride / per_img: HOST arrays of `levels` entries; table: DEVICE int32 array of n_out indices into the n_src
+ * images of the sources - stream-ordered, no host synchronisation.  An index outside [0, n_src) is never followed: that destination
+ * image is filled with NaN.  16-byte accesses where pointers, stride and image size allow, scalar ones otherwise. */
+#define EDVR_GATHER_MAX_LEVELS 3
+int edvr_gather_images_f32(const float *const *src, float *const *dst, const int64_t *src_img_stride, const int64_t *per_img, int levels,
+                           const int *table, int n_out, int n_src, edvr_stream_t stream);
+/* The network's last step with the output in the form it is stored or encoded: out (n, 4h, 4w, 3) uint8, interleaved, =
+ * tensor2img (basicsr/utils/img_util.py:36-98: clamp to [0, 1], x 255, round half to even) of y + bilinear x4 of base, y (n, 3, 4h, 4w),
+ * base (n, 3, h, w), both contiguous - bit for bit the bytes of the float result of the y += form above. */
+int edvr_upsample4x_add_u8(const float *y, const float *base, uint8_t *out, int n, int h, int w, edvr_stream_t stream);
+/* out (n, h, w, 3) uint8 = tensor2img of x (n, 3, h, w), x_img_stride floats between images (>= 3 * h * w). */
+int edvr_f32_to_u8_hwc(const float *x, uint8_t *out, int n, int h, int w, int64_t x_img_stride, edvr_stream_t stream);
+
 /* Multi-tensor Adam step <- torch.optim.Adam.step() as the reference builds it (basicsr/models/edvr_model.py:21-53, parameter
  * groups with dcn_lr_mul; stepped in sr_model.py:112).  `chunk_table` is a DEVICE array of n_chunks records of
  * edvr_adam_chunk_bytes() = 64 bytes: { float *p; const float *g; float *m; float *v; int32 n (<= 65536 elements of one tensor);
