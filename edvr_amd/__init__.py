@@ -14,6 +14,6 @@ from .arch_util import DCNv2Pack, ResidualBlockNoBN, default_init_weights, make_
 from .dcn import (DeformConv, DeformConvFunction, DeformConvPack, ModulatedDeformConv,  # noqa: F401
                   ModulatedDeformConvFunction, ModulatedDeformConvPack, deform_conv, modulated_deform_conv)
 from .edvr_arch import EDVR, PCDAlignment, PredeblurModule, TSAFusion  # noqa: F401
-from .video import VideoRestorer, WindowSchedule, window_table  # noqa: F401
+from .video import VideoRestorer, WindowSchedule, tile_grid, window_table  # noqa: F401
 
 __version__ = '0.1.0'

@@ -13,6 +13,7 @@
 #include <algorithm>
 
 #include "common.h"
+#include "pixel.h"
 
 namespace edvr {
 
@@ -24,15 +25,6 @@ struct FramesArgs {
   int n, frames_per_clip, h, w, swap_rb, clip0;
   uint8_t flags[256];  // per clip, relative to clip0: EDVR_AUG_HFLIP | EDVR_AUG_VFLIP | EDVR_AUG_ROT90
 };
-
-// byte / 255 in float32, correctly rounded (== numpy's float32 division for all 256 inputs, checked exhaustively by
-// tests/test_gpu_data.py::test_division_is_numpy_division): q = u * fl(1/255), one Newton correction with the exact remainder.
-// 3 VALU instructions instead of the ~10 of the IEEE division sequence - the kernel converts 3 values per 15 bytes of traffic.
-__device__ __forceinline__ float div255(unsigned u) {
-  const float r = 1.f / 255.f, f = (float)u;
-  const float q = __fmul_rn(f, r);
-  return __fmaf_rn(__fmaf_rn(-q, 255.f, f), r, q);
-}
 
 // FAST: w % 4 == 0 (every REDS / Vimeo size and every training patch) - each 32-pixel row segment of a tile is then 96 bytes at
 // a 4-byte aligned address: dword loads, dword LDS traffic, one 16-byte store per channel for 4 pixels of a row.  The generic

@@ -271,16 +271,24 @@ class EDVR(nn.Module):
         f3 = F_.conv(self.conv_l3_2, F_.conv(self.conv_l3_1, f2, act=LRELU), act=LRELU, out=o3)
         return [f1, f2, f3]
 
-    def restore_from_features(self, pyr, x_center, b, t, out_dtype=torch.float32):
+    def restore_from_features(self, pyr, x_center, b, t, out_dtype=torch.float32, out=None, keep=None):
         """Everything after the per-frame stage.  pyr = [f1, f2, f3]: the b * t window images of each level, clip after clip (image
         i * t + j = frame j of output frame i's window), x_center (b, c, H, W): the input frames the outputs are residuals of.
         out_dtype=torch.uint8 (no-grad calls only): the result as (b, H', W', 3) bytes with tensor2img semantics (clamp, x 255, round
-        half to even) - the last step writes them instead of the float tensor."""
+        half to even) - the last step writes them instead of the float tensor.
+        out (no-grad calls only): a view (b, c, kh, kw) float32 / (b, kh, kw, 3) uint8 of a larger (full-frame) tensor; the last kernel
+        stores the rectangle of the result whose first pixel is keep = (ky, kx) (output pixels; default (0, 0)) there and nothing else -
+        the tiles and the edge padding of edvr_amd/video.py.  Returns `out` then."""
         if out_dtype not in (torch.float32, torch.uint8):
             raise ValueError(f'out_dtype must be torch.float32 or torch.uint8, got {out_dtype}')
         if out_dtype == torch.uint8 and torch.is_grad_enabled():
             raise RuntimeError('the uint8 output of EDVR.restore_from_features has no backward: call it under torch.no_grad()')
+        if out is None and keep is not None:
+            raise ValueError('keep= names a rectangle of the result to store into out=: it needs out')
+        if out is not None and torch.is_grad_enabled():
+            raise RuntimeError('EDVR.restore_from_features(out=) writes in place and has no backward: call it under torch.no_grad()')
         f1, f2, f3 = pyr
+        dst = out
         ctr = self.center_frame_idx
         h, w = f1.shape[2], f1.shape[3]
         # all b*t frames aligned in one pass; frame i pairs with the centre frame of its clip
@@ -306,7 +314,15 @@ class EDVR(nn.Module):
         out = F_.conv(self.upconv1, out, act=LRELU, out_mode=F_.OUT_PIXEL_SHUFFLE2)
         out = F_.conv(self.upconv2, out, act=LRELU, out_mode=F_.OUT_PIXEL_SHUFFLE2)
         out = F_.conv(self.conv_hr, out, act=LRELU)
-        if self.hr_in:
+        if dst is not None:  # the same values, the last kernel storing the kept rectangle into the caller's tensor
+            ky, kx = keep if keep is not None else (0, 0)
+            if self.hr_in:
+                tail = F_.ops.f32_to_u8_hwc_rect if out_dtype == torch.uint8 else F_.ops.copy_rect
+                out = tail(F_.conv(self.conv_last, out, res1=x_center), dst, ky, kx)
+            else:
+                tail = F_.ops.upsample4x_add_u8_rect if out_dtype == torch.uint8 else F_.ops.upsample4x_add_rect
+                out = tail(F_.conv(self.conv_last, out), x_center, dst, ky, kx)
+        elif self.hr_in:
             out = F_.conv(self.conv_last, out, res1=x_center)
             if out_dtype == torch.uint8:
                 out = F_.ops.f32_to_u8_hwc(out)

@@ -108,13 +108,16 @@ def validate_clip(net, lq, gt=None, num_frame=5, padding='reflection_circle', ba
 
 
 @torch.no_grad()
-def validate_video(net, lq, gt=None, num_frame=5, padding='reflection_circle', chunk=8, crop_border=0, test_y_channel=False):
+def validate_video(net, lq, gt=None, num_frame=5, padding='reflection_circle', chunk=8, crop_border=0, test_y_channel=False, pad_mode=None,
+                   tile=None, tile_overlap=None):
     """validate_clip with every frame's features extracted once (edvr_amd/video.py: VideoRestorer) instead of once per window it
     appears in; `chunk` output frames per alignment / fusion / reconstruction pass.  Same arguments otherwise, same return value:
-    (outputs (t, c, H, W), [PSNR per frame] or None)."""
+    (outputs (t, c, H, W), [PSNR per frame] or None).  pad_mode / tile / tile_overlap: VideoRestorer's, for frames of any size - the
+    outputs and `gt` are (s H, s W) for LQ frames of (H, W), whatever they were padded to."""
     from .video import VideoRestorer
     outs, scores, s0 = [], [], 0
-    for out in VideoRestorer(net, num_frame=num_frame, padding=padding, chunk=chunk).restore_chunks(lq.split(chunk), length=lq.shape[0]):
+    vr = VideoRestorer(net, num_frame=num_frame, padding=padding, chunk=chunk, pad_mode=pad_mode, tile=tile, tile_overlap=tile_overlap)
+    for out in vr.restore_chunks(lq.split(chunk), length=lq.shape[0]):
         outs.append(out)
         if gt is not None:
             scores += calculate_psnr(out, gt[s0:s0 + out.shape[0]], crop_border, test_y_channel)

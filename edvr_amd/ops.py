@@ -1315,3 +1315,128 @@ def f32_to_u8_hwc(x):
     _run('f32_to_u8_hwc', lambda: _lib.check(_lib.lib().edvr_f32_to_u8_hwc(_ptr(x), _ptr(out), n, h, w, _img_stride(x), _stream()),
                                              'edvr_f32_to_u8_hwc'), 0, _nb(x) + out.numel())
     return out
+
+
+PAD_MODES = {'reflect': 0, 'replicate': 1}  # EDVR_PAD_REFLECT, EDVR_PAD_REPLICATE
+
+
+def crop_pad_frames(frames, y0, x0, th, tw, pad_mode=None):
+    """The (th, tw) rectangle at (y0, x0) of `frames` extended at the bottom and right - F.pad(x, (0, .., 0, ..), mode=pad_mode) and a slice
+    in one launch - as a dense float32 (n, 3, th, tw) tensor.  frames: uint8 (n, H, W, 3) (converted as frames_u8_to_f32 does: byte / 255)
+    or float32 (n, 3, H, W) with dense images (a slice of a longer video works).  pad_mode 'reflect' | 'replicate'; None: the rectangle
+    must lie inside the frames.  A rectangle the mode cannot fill ('reflect' reaches H - 1 rows beyond the frame) is a ValueError."""
+    if not frames.is_cuda:
+        raise NotImplementedError('edvr_amd ops run on the GPU only (HIP/gfx950); got a CPU tensor')
+    if pad_mode is not None and pad_mode not in PAD_MODES:
+        raise ValueError(f"pad_mode must be None, 'reflect' or 'replicate', got {pad_mode!r}")
+    u8 = frames.dtype == torch.uint8
+    if u8:
+        if frames.dim() != 4 or frames.shape[-1] != 3:
+            raise ValueError(f'uint8 frames are (n, H, W, 3), got {tuple(frames.shape)}')
+        frames = frames.contiguous()
+        n, H, W, _ = frames.shape
+    else:
+        require_gpu(frames)
+        if frames.dim() != 4 or frames.shape[1] != 3:
+            raise ValueError(f'float32 frames are (n, 3, H, W), got {tuple(frames.shape)}')
+        frames = _as_planes(frames)
+        n, _, H, W = frames.shape
+    y0, x0, th, tw = int(y0), int(x0), int(th), int(tw)
+    if n == 0 or th <= 0 or tw <= 0 or not (0 <= y0 < H and 0 <= x0 < W):
+        raise ValueError(f'crop_pad_frames: a {th} x {tw} rectangle at ({y0}, {x0}) of {n} frame(s) of {H} x {W}')
+    reach = (H - 1, W - 1) if pad_mode is None else (2 * (H - 1), 2 * (W - 1)) if pad_mode == 'reflect' else None
+    if reach is not None and (y0 + th - 1 > reach[0] or x0 + tw - 1 > reach[1]):
+        raise ValueError(f'crop_pad_frames: a {th} x {tw} rectangle at ({y0}, {x0}) reaches beyond what pad_mode={pad_mode!r} makes of a {H} x {W} frame')
+    mode = PAD_MODES[pad_mode or 'replicate']
+    out = torch.empty(n, 3, th, tw, dtype=torch.float32, device=frames.device)
+    if u8:
+        _run('crop_pad_frames', lambda: _lib.check(_lib.lib().edvr_crop_pad_frames_u8(_ptr(frames), _ptr(out), n, H, W, y0, x0, th, tw, mode, _stream()),
+                                                   'edvr_crop_pad_frames_u8'), 0, 5.0 * out.numel())
+    else:
+        _run('crop_pad_frames', lambda: _lib.check(_lib.lib().edvr_crop_pad_frames_f32(_ptr(frames), _ptr(out), n, H, W, _img_stride(frames), y0, x0, th, tw,
+                                                                                       mode, _stream()), 'edvr_crop_pad_frames_f32'), 0, 8.0 * out.numel())
+    return out
+
+
+def _rect_dst(out, n, hy, wy, ky, kx, u8):
+    """Checks a rectangle destination: `out` a view (n, 3, kh, kw) float32 / (n, kh, kw, 3) uint8 of a full-frame tensor (unit stride
+    along a row, any row / plane / image strides) -> (kh, kw, row, plane, image strides in elements)."""
+    if not out.is_cuda:
+        raise NotImplementedError('edvr_amd ops run on the GPU only (HIP/gfx950); got a CPU tensor')
+    if out.dtype != (torch.uint8 if u8 else torch.float32) or out.dim() != 4 or out.shape[0] != n or out.shape[3 if u8 else 1] != 3:
+        raise ValueError(f'rectangle destination: expected {"(n, kh, kw, 3) uint8" if u8 else "(n, 3, kh, kw) float32"} with n = {n}, got {out.dtype} {tuple(out.shape)}')
+    kh, kw = (out.shape[1], out.shape[2]) if u8 else (out.shape[2], out.shape[3])
+    ky, kx = int(ky), int(kx)
+    if kh <= 0 or kw <= 0 or ky < 0 or kx < 0 or ky + kh > hy or kx + kw > wy:
+        raise ValueError(f'a {kh} x {kw} rectangle at ({ky}, {kx}) does not lie inside a {hy} x {wy} result')
+    st = out.stride()
+    if u8:
+        ok = st[3] == 1 and st[2] == 3 and st[1] >= 3 * kw and (n == 1 or st[0] >= (kh - 1) * st[1] + 3 * kw)
+        row, plane, img = st[1], 0, st[0]
+    else:
+        ok = st[3] == 1 and st[2] >= kw and st[1] >= (kh - 1) * st[2] + kw and (n == 1 or st[0] >= 2 * st[1] + (kh - 1) * st[2] + kw)
+        row, plane, img = st[2], st[1], st[0]
+    if not ok:
+        raise ValueError(f'rectangle destination: a view of a full-frame {"(N, H, W, 3)" if u8 else "(N, 3, H, W)"} tensor is expected, got strides {st}')
+    if n == 1:
+        img = max(img, (0 if u8 else 2 * plane) + (kh - 1) * row + (3 if u8 else 1) * kw)
+    return kh, kw, row, plane, img
+
+
+def upsample4x_add_rect(y, base, out, ky=0, kx=0):
+    """out[...] = (y + bilinear_x4(base))[:, :, ky:ky + kh, kx:kx + kw] - the values upsample4x_add_ stores there - for a view `out`
+    (n, 3, kh, kw) of a full-frame float32 tensor; y is left as it is.  Returns out."""
+    require_gpu(y, base)
+    base = base.contiguous()
+    n, c, h, w = base.shape
+    if c != 3:
+        raise NotImplementedError(f'the rectangle stores are for RGB images: 3 channels, got {c}')
+    assert y.is_contiguous() and tuple(y.shape) == (n, c, 4 * h, 4 * w)
+    kh, kw, row, plane, img = _rect_dst(out, n, 4 * h, 4 * w, ky, kx, False)
+    _run('upsample4x_add_rect', lambda: _lib.check(_lib.lib().edvr_upsample4x_add_rect_f32(_ptr(y), _ptr(base), _ptr(out), n, h, w, int(ky), int(kx), kh, kw,
+                                                                                           row, plane, img, _stream()), 'edvr_upsample4x_add_rect_f32'),
+         0, _nb(base) + 24.0 * n * kh * kw)
+    void_bound(out)
+    return out
+
+
+def upsample4x_add_u8_rect(y, base, out, ky=0, kx=0):
+    """out[...] = upsample4x_add_u8(y, base)[:, ky:ky + kh, kx:kx + kw] for a view `out` (n, kh, kw, 3) of a full-frame uint8 tensor."""
+    require_gpu(y, base)
+    base = base.contiguous()
+    n, c, h, w = base.shape
+    if c != 3:
+        raise NotImplementedError(f'the uint8 output is interleaved RGB: 3 channels, got {c}')
+    assert y.is_contiguous() and tuple(y.shape) == (n, c, 4 * h, 4 * w)
+    kh, kw, row, _, img = _rect_dst(out, n, 4 * h, 4 * w, ky, kx, True)
+    _run('upsample4x_add_u8_rect', lambda: _lib.check(_lib.lib().edvr_upsample4x_add_rect_u8(_ptr(y), _ptr(base), _ptr(out), n, h, w, int(ky), int(kx), kh, kw,
+                                                                                             row, img, _stream()), 'edvr_upsample4x_add_rect_u8'),
+         0, _nb(base) + 15.0 * n * kh * kw)
+    return out
+
+
+def f32_to_u8_hwc_rect(x, out, ky=0, kx=0):
+    """out[...] = f32_to_u8_hwc(x)[:, ky:ky + kh, kx:kx + kw] for a view `out` (n, kh, kw, 3) of a full-frame uint8 tensor."""
+    require_gpu(x)
+    x = _as_planes(x)
+    n, c, h, w = x.shape
+    if c != 3:
+        raise NotImplementedError(f'the uint8 output is interleaved RGB: 3 channels, got {c}')
+    kh, kw, row, _, img = _rect_dst(out, n, h, w, ky, kx, True)
+    _run('f32_to_u8_hwc_rect', lambda: _lib.check(_lib.lib().edvr_f32_to_u8_hwc_rect(_ptr(x), _ptr(out), n, h, w, _img_stride(x), int(ky), int(kx), kh, kw,
+                                                                                     row, img, _stream()), 'edvr_f32_to_u8_hwc_rect'), 0, 15.0 * n * kh * kw)
+    return out
+
+
+def copy_rect(x, out, ky=0, kx=0):
+    """out[...] = x[:, :, ky:ky + kh, kx:kx + kw] for a view `out` (n, 3, kh, kw) of a full-frame float32 tensor (the hr_in float tail)."""
+    require_gpu(x)
+    x = _as_planes(x)
+    n, c, h, w = x.shape
+    if c != 3:
+        raise NotImplementedError(f'the rectangle stores are for RGB images: 3 channels, got {c}')
+    kh, kw, row, plane, img = _rect_dst(out, n, h, w, ky, kx, False)
+    _run('copy_rect', lambda: _lib.check(_lib.lib().edvr_copy_rect_f32(_ptr(x), _ptr(out), n, h, w, _img_stride(x), int(ky), int(kx), kh, kw,
+                                                                       row, plane, img, _stream()), 'edvr_copy_rect_f32'), 0, 24.0 * n * kh * kw)
+    void_bound(out)
+    return out

@@ -7,8 +7,16 @@ num_frame times on every frame although its result depends on the frame alone.  
 feature BANK and builds each chunk of windows by one gather launch (ops.gather_images) over the bank; alignment, fusion and
 reconstruction (`EDVR.restore_from_features`) see exactly the tensors a `forward` of `chunk` windows would compute.
 
+Frames of ANY size (`pad_mode`, `tile`): the frame is extended at the bottom and right to the network's size multiple and covered by
+equal tiles (`tile_grid`); the per-frame stage reads tiles straight from the caller's frames (ops.crop_pad_frames: crop, pad and the
+byte conversion in one launch), every tile has a bank of its own, and the last kernel of each tile's restore pass stores the KEPT
+rectangle of its result into the chunk's full-frame output (the `*_rect` tails of csrc/video.hip).  No blending: inside its kept
+rectangle a tile's result is final, and equals what the plain path computes on that tile's crop.
+
 No-grad inference only: there is no backward through the bank.
 """
+from collections import namedtuple
+
 import torch
 
 from . import ops
@@ -24,6 +32,54 @@ def window_table(n_frames, num_frame, padding='reflection_circle'):
     if any(not 0 <= f < n_frames for r in rows for f in r):
         raise ValueError(f"a video of {n_frames} frame(s) is too short for windows of {num_frame} with '{padding}' padding")
     return torch.tensor(rows, dtype=torch.int32).reshape(n_frames, num_frame)
+
+
+Tile = namedtuple('Tile', 'src keep dst')
+Tile.__doc__ = """src = (y0, x0, th, tw): the tile in padded-frame coordinates; keep = (ky, kx, kh, kw): the rectangle inside the tile whose
+result is final; dst = (oy, ox): where that rectangle lies in the frame (= (y0 + ky, x0 + kx)).  Input pixels throughout."""
+
+
+def _round_up(v, m):
+    return (v + m - 1) // m * m
+
+
+def _tile_axis(size, padded, tile, overlap, m):
+    """One axis: [(origin, first kept, kept count)] of equal tiles of `tile` covering [0, padded), kept parts partitioning [0, size)."""
+    if tile >= padded:
+        return [(0, 0, size)]
+    stride = tile - overlap
+    count = -(-(padded - tile) // stride) + 1
+    origins = [min(i * stride, padded - tile) for i in range(count)]  # the last tile is shifted inwards, not padded further
+    # neighbours share [origins[i + 1], origins[i] + tile) (>= overlap, more for the shifted last tile): cut in its middle, on a multiple of m
+    cuts = [0] + [origins[i + 1] + (origins[i] + tile - origins[i + 1]) // (2 * m) * m for i in range(count - 1)] + [size]
+    return [(o, cuts[i] - o, cuts[i + 1] - cuts[i]) for i, o in enumerate(origins)]
+
+
+def tile_grid(H, W, tile=None, overlap=None, multiple=4):
+    """Equal tiles covering a frame of (H, W) extended at the bottom and right to the next multiples of `multiple` (pure Python).
+    tile = (th, tw) in input pixels, multiples of `multiple`, clamped to the padded frame (None: one tile = the padded frame);
+    overlap: input pixels neighbouring tiles share at least - a multiple of 2 * multiple, smaller than the tile (None: 8 * multiple).
+    Returns a list of Tile, row by row.  Every source rectangle has the (clamped) tile shape and lies inside the padded frame; the kept rectangles cover the (H, W) frame exactly once; a kept pixel is at least
+    overlap / 2 away from every tile edge that is not an edge of the padded frame; origins and cuts are multiples of `multiple`."""
+    m = int(multiple)
+    if H < 1 or W < 1 or m < 1:
+        raise ValueError(f'tile_grid: a frame of {H} x {W}, multiple {m}')
+    Hp, Wp = _round_up(H, m), _round_up(W, m)
+    if tile is None:
+        tile, overlap = (Hp, Wp), 0 if overlap is None else overlap
+    th, tw = int(tile[0]), int(tile[1])
+    if th < m or tw < m or th % m or tw % m:
+        raise ValueError(f'tile {(th, tw)} must be positive multiples of {m}')
+    if overlap is None:
+        overlap = 8 * m
+    overlap = int(overlap)
+    if overlap < 0 or overlap % (2 * m):
+        raise ValueError(f'tile_overlap {overlap} must be a multiple of {2 * m}')
+    if overlap >= min(th, tw):
+        raise ValueError(f'tile {(th, tw)} must be larger than tile_overlap {overlap}')
+    th, tw = min(th, Hp), min(tw, Wp)
+    return [Tile((y0, x0, th, tw), (ky, kx, kh, kw), (y0 + ky, x0 + kx))
+            for y0, ky, kh in _tile_axis(H, Hp, th, overlap, m) for x0, kx, kw in _tile_axis(W, Wp, tw, overlap, m)]
 
 
 class WindowSchedule:
@@ -123,11 +179,32 @@ class VideoRestorer:
     video; the input frames are kept (as views of what the caller handed in, or as the converted uint8 pieces) until no window's
     centre needs them.  Around every chunk the bookkeeping of a forward happens: offset statistics and overflow flags of earlier
     chunks that have reached the host are examined before, this chunk's are sent after; nothing waits for the GPU -
-    `net.check_offsets()` after the last chunk evaluates what is still on its way, as after a run of forwards."""
+    `net.check_offsets()` after the last chunk evaluates what is still on its way, as after a run of forwards.
 
-    def __init__(self, net, num_frame=None, padding='reflection_circle', chunk=8, out_dtype=torch.float32):
+    Frames of any size - opt-in; with the defaults the size must be a multiple of m = 4 (16 with hr_in) and nothing above changes:
+    pad_mode 'reflect' | 'replicate': frames of (H, W) are extended at the bottom and right to the next multiples of m with
+    torch.nn.functional.pad's rule, the output is the first (s H, s W) pixels (s = 4, or 1 with hr_in) of the network's result.
+    tile (th, tw), tile_overlap (input pixels; None: 8 m): the padded frame is covered by equal tiles (`tile_grid`), each with a bank of
+    its own (same ring, same capacity); an extract step runs the per-frame stage tile by tile, a restore step everything else tile by
+    tile, each tile's last kernel storing its kept rectangle into the chunk's full-frame output - bit for bit what this class computes on
+    that tile's crop of the padded frames.  Near the cuts the result differs from the untiled one (the network's receptive field is
+    larger than any sensible overlap); what shrinks is the memory of everything after the gather, by about the tiles' share of the frame.
+    Either argument turns the tiled path on: uint8 frames then stay bytes (no full-frame float copy), all pieces must share one dtype."""
+
+    def __init__(self, net, num_frame=None, padding='reflection_circle', chunk=8, out_dtype=torch.float32, pad_mode=None, tile=None,
+                 tile_overlap=None):
         if out_dtype not in (torch.float32, torch.uint8):
             raise ValueError(f'out_dtype must be torch.float32 or torch.uint8, got {out_dtype}')
+        if pad_mode not in (None, 'reflect', 'replicate'):
+            raise ValueError(f"pad_mode must be None, 'reflect' or 'replicate', got {pad_mode!r}")
+        self.multiple, self.scale = (16, 1) if net.hr_in else (4, 4)
+        if tile is not None:
+            tile_grid(self.multiple, self.multiple, tile, tile_overlap, self.multiple)  # argument errors now, not at the first frame
+            tile = (int(tile[0]), int(tile[1]))
+        elif tile_overlap is not None:
+            raise ValueError('tile_overlap without tile')
+        self.pad_mode, self.tile, self.tile_overlap = pad_mode, tile, tile_overlap
+        self.tiled = pad_mode is not None or tile is not None
         self.net, self.padding, self.chunk, self.out_dtype = net, padding, int(chunk), out_dtype
         self.num_feat = net.conv_l2_1.in_channels
         if num_frame is None:
@@ -142,7 +219,10 @@ class VideoRestorer:
         self.slots = 0
         self.schedule = None    # the WindowSchedule of the running restore
         self._groups = []       # (first frame, count, [bound or None per level], [depth per level]) of every extract call with live frames
-        self._pieces = []       # (first frame, float32 (k, 3, H, W)) input frames not dead yet
+        self._pieces = []       # (first frame, float32 (k, 3, H, W)) input frames not dead yet (tiled path: as they came, uint8 (k, H, W, 3) too)
+        self.grid = None        # tiled path: [Tile] of the running restore, and per tile ...
+        self.banks = None       # ... its [f1, f2, f3] rings
+        self._tile_groups = None  # ... and its _groups
 
     # ---- device primitives (the schedule test replaces them by CPU stand-ins)
     def _check_input(self, t):
@@ -155,6 +235,10 @@ class VideoRestorer:
 
     def _gather(self, srcs, table):
         return ops.gather_images(srcs, table)
+
+    def _crop(self, frames, y0, x0, th, tw):
+        """The tile at (y0, x0) of `frames` (uint8 HWC or float32 CHW) extended by pad_mode, as float32 (k, 3, th, tw)."""
+        return ops.crop_pad_frames(frames, y0, x0, th, tw, self.pad_mode)
 
     # ---- input
     def _check_mode(self):
@@ -171,6 +255,8 @@ class VideoRestorer:
                 item = item[None]
             if item.dim() != 4 or item.shape[-1] != 3:
                 raise ValueError(f'uint8 frames are (H, W, 3) or (k, H, W, 3), got {tuple(item.shape)}')
+            if self.tiled:
+                return item  # the tiles are read from the bytes (ops.crop_pad_frames): no full-frame float copy
             return ops.frames_u8_to_f32(item[None])[0]
         if item.dtype != torch.float32:
             raise NotImplementedError(f'edvr_amd: {item.dtype} frames are not supported here (float32 CHW in [0, 1] or uint8 HWC)')
@@ -213,29 +299,33 @@ class VideoRestorer:
             self.slots = self.capacity if length is None else max(1, min(self.capacity, length))
             self.bank = [torch.empty((self.slots,) + s, dtype=torch.float32, device=frames.device)
                          for s in self._pyramid_shapes(frames.shape[2], frames.shape[3])]
+        self._extract_into(self.bank, self._groups, frames, first, count)
+
+    def _extract_into(self, bank, groups, frames, first, count):
         if self.schedule.ext - self.schedule.lo > self.slots:
             raise RuntimeError(f'VideoRestorer: {self.schedule.ext - self.schedule.lo} live frames do not fit the bank of {self.slots}')
         done = 0
         while done < count:  # a group that crosses the end of the ring is extracted in two parts
             slot = (first + done) % self.slots
             m = min(count - done, self.slots - slot)
-            pyr = self.net.extract_features(frames[done:done + m], out=[lv[slot:slot + m] for lv in self.bank])
+            pyr = self.net.extract_features(frames[done:done + m], out=[lv[slot:slot + m] for lv in bank])
             bounds = [ops.get_bound(f) for f in pyr]
-            self._groups.append((first + done, m, bounds, [ops._bound_depth(f) if b is not None else 0 for f, b in zip(pyr, bounds)]))
+            groups.append((first + done, m, bounds, [ops._bound_depth(f) if b is not None else 0 for f, b in zip(pyr, bounds)]))
             done += m
 
-    def _bank_bounds(self):
+    def _bank_bounds(self, bank=None, groups=None):
         """The bank's magnitude bound per level = the largest bound of the live extract groups (none where a group has none)."""
+        bank, groups = (self.bank, self._groups) if bank is None else (bank, groups)
         lo = self.schedule.lo
-        self._groups = [g for g in self._groups if g[0] + g[1] > lo]
-        for lv, bank in enumerate(self.bank):
-            bs = [g[2][lv] for g in self._groups]
-            ops.void_bound(bank)
+        groups[:] = [g for g in groups if g[0] + g[1] > lo]
+        for lv, level in enumerate(bank):
+            bs = [g[2][lv] for g in groups]
+            ops.void_bound(level)
             if bs and all(b is not None for b in bs):
                 b = bs[0]
                 for o in bs[1:]:
                     b = torch.maximum(b, o)
-                ops.set_bound(bank, b, max(g[3][lv] for g in self._groups))
+                ops.set_bound(level, b, max(g[3][lv] for g in groups))
 
     def _restore(self, first, rows):
         net, t = self.net, self.num_frame
@@ -247,14 +337,59 @@ class VideoRestorer:
         pyr = self._gather(self.bank, table)
         return net.restore_from_features(pyr, self._frames(first, first + len(rows)), len(rows), t, out_dtype=self.out_dtype)
 
+    # ---- frames of any size: edge padding and tiles
+    def _frame_size(self, frames):
+        return tuple(frames.shape[1:3]) if frames.dtype == torch.uint8 else tuple(frames.shape[2:4])
+
+    def _setup_tiles(self, frames, length):
+        H, W = self._frame_size(frames)
+        m = self.multiple
+        if self.pad_mode is None:  # tiles alone: the size rule of the plain path
+            assert H % m == 0 and W % m == 0, f'The height and width must be multiple of {m}.'
+        Hp, Wp = _round_up(H, m), _round_up(W, m)
+        if self.pad_mode == 'reflect' and (Hp - H > H - 1 or Wp - W > W - 1):
+            raise ValueError(f"pad_mode='reflect' mirrors without repeating the edge: a frame of {H} x {W} is too small to be extended to {Hp} x {Wp}")
+        self.grid = tile_grid(H, W, self.tile, self.tile_overlap, m)
+        th, tw = self.grid[0].src[2:]
+        self.slots = self.capacity if length is None else max(1, min(self.capacity, length))
+        self.banks = [[torch.empty((self.slots,) + s, dtype=torch.float32, device=frames.device) for s in self._pyramid_shapes(th, tw)]
+                      for _ in self.grid]
+        self._tile_groups = [[] for _ in self.grid]
+
+    def _extract_tiled(self, first, count, length):
+        frames = self._frames(first, first + count)
+        if self.banks is None:
+            self._setup_tiles(frames, length)
+        for tile, bank, groups in zip(self.grid, self.banks, self._tile_groups):
+            self._extract_into(bank, groups, self._crop(frames, *tile.src), first, count)
+
+    def _restore_tiled(self, first, rows):
+        net, t, s, b = self.net, self.num_frame, self.scale, len(rows)
+        centre = self._frames(first, first + b)
+        H, W = self._frame_size(centre)
+        u8 = self.out_dtype == torch.uint8
+        out = torch.empty((b, s * H, s * W, 3) if u8 else (b, 3, s * H, s * W), dtype=self.out_dtype, device=centre.device)
+        table = self._slot_table([f % self.slots for r in rows for f in r], centre.device)
+        for tile, bank, groups in zip(self.grid, self.banks, self._tile_groups):
+            net.check_offsets(wait=False)  # per tile what a forward does before its launches, as in _restore
+            if bank[0].is_cuda:
+                ops.split_guard_check(wait=False)
+            self._bank_bounds(bank, groups)
+            pyr = self._gather(bank, table)
+            (ky, kx, kh, kw), (oy, ox) = tile.keep, tile.dst
+            ys, xs = slice(s * oy, s * (oy + kh)), slice(s * ox, s * (ox + kw))
+            net.restore_from_features(pyr, self._crop(centre, *tile.src), b, t, out_dtype=self.out_dtype,
+                                      out=out[:, ys, xs] if u8 else out[:, :, ys, xs], keep=(s * ky, s * kx))
+        return out
+
     # ---- public
     def _run(self, steps, length):
         for kind, first, arg in steps:
             self._check_mode()
             if kind == 'extract':
-                self._extract(first, arg, length)
+                (self._extract_tiled if self.tiled else self._extract)(first, arg, length)
             else:
-                out = self._restore(first, arg)
+                out = (self._restore_tiled if self.tiled else self._restore)(first, arg)
                 nxt = first + len(arg)  # input frames are read by their extraction and as their own output's residual base
                 self._pieces = [(f, p) for f, p in self._pieces if f + p.shape[0] > nxt]
                 yield out
@@ -265,16 +400,20 @@ class VideoRestorer:
         self._check_mode()
         self.schedule = sched = WindowSchedule(self.num_frame, self.padding, self.chunk, _probe=False)
         self.bank, self._groups, self._pieces = None, [], []
+        self.grid = self.banks = self._tile_groups = None
         try:
             for item in frames:
                 piece = self._as_frames(item)
                 if piece.shape[0] == 0:
                     continue
+                if self.tiled and self._pieces and piece.dtype != self._pieces[-1][1].dtype:
+                    raise ValueError(f'the frames of one video share one dtype: {piece.dtype} after {self._pieces[-1][1].dtype}')
                 self._pieces.append((sched.arrived, piece))
                 yield from self._run(sched.push(piece.shape[0]), length)
             yield from self._run(sched.finish(), length)
         finally:
-            self.bank, self._groups, self._pieces = None, [], []  # (the schedule stays for inspection)
+            self.bank, self._groups, self._pieces = None, [], []  # (the schedule and the tile grid stay for inspection)
+            self.banks = self._tile_groups = None
 
     def restore_iter(self, frames, length=None):
         """Streaming form: `frames` is an iterable of frames ((3, H, W) float32 / (H, W, 3) uint8) or of small batches of them, of

@@ -485,6 +485,35 @@ int edvr_upsample4x_add_u8(const float *y, const float *base, uint8_t *out, int 
 /* out (n, h, w, 3) uint8 = tensor2img of x (n, 3, h, w), x_img_stride floats between images (>= 3 * h * w). */
 int edvr_f32_to_u8_hwc(const float *x, uint8_t *out, int n, int h, int w, int64_t x_img_stride, edvr_stream_t stream);
 
+/* Frames of any size (edvr_amd/video.py: pad_mode / tile).  One launch replaces torch.nn.functional.pad(x, (0, Wp - W, 0, Hp - H), mode)
+ * of float frames (the reference has no such step: edvr_arch.py:358-366 asserts the size multiple), the slice of a tile out of the padded
+ * frames and, for uint8 frames, the byte -> float conversion ahead of both (img_util.py:101-123): dst (n, 3, th, tw) dense float32 =
+ * the rectangle at (y0, x0) of the frames extended at the bottom and right, rows >= H / columns >= W by the 'reflect' (2 (n - 1) - j; a
+ * rectangle reaching further is EDVR_ERR_ARG) or 'replicate' (n - 1) index rule.  _u8: src (n, H, W, 3) dense bytes, dst = byte / 255
+ * exactly as edvr_frames_u8_to_f32 rounds it; _f32: src (n, 3, H, W), dense images src_img_stride floats apart.  16-byte stores where
+ * tw % 4 == 0 and dst is aligned, aligned wide loads for groups inside the frame, a scalar path otherwise. */
+#define EDVR_PAD_REFLECT 0
+#define EDVR_PAD_REPLICATE 1
+int edvr_crop_pad_frames_u8(const uint8_t *src, float *dst, int n, int H, int W, int y0, int x0, int th, int tw, int pad_mode,
+                            edvr_stream_t stream);
+int edvr_crop_pad_frames_f32(const float *src, float *dst, int n, int H, int W, int64_t src_img_stride, int y0, int x0, int th, int tw,
+                             int pad_mode, edvr_stream_t stream);
+/* The network's last step with a RECTANGLE store: replaces running the whole-tile form and then slicing + copying its result into a
+ * full-frame tensor (out[..., oy:oy + kh, ox:ox + kw] = tile_result[..., ky:ky + kh, kx:kx + kw] in ATen).  Pixel (ky + r, kx + q) of what
+ * edvr_upsample4x_add_f32 / edvr_upsample4x_add_u8 / edvr_f32_to_u8_hwc would store for y (n, 3, 4h, 4w) + base (n, 3, h, w), both
+ * contiguous - or for x (n, 3, h, w), x_img_stride floats between images - goes to (r, q) of dst, r < kh, q < kw, bit for bit.  dst
+ * points at the rectangle's first element in the full-frame output; strides in elements of dst: float (n, 3, ., .) destinations have
+ * row / plane / image strides, byte (n, ., ., 3) destinations row / image strides.  Wide loads and stores where kx, kw, the pointers
+ * and the strides allow, scalar ones otherwise. */
+int edvr_upsample4x_add_rect_f32(const float *y, const float *base, float *dst, int n, int h, int w, int ky, int kx, int kh, int kw,
+                                 int64_t dst_row_stride, int64_t dst_plane_stride, int64_t dst_img_stride, edvr_stream_t stream);
+int edvr_upsample4x_add_rect_u8(const float *y, const float *base, uint8_t *dst, int n, int h, int w, int ky, int kx, int kh, int kw,
+                                int64_t dst_row_stride, int64_t dst_img_stride, edvr_stream_t stream);
+int edvr_f32_to_u8_hwc_rect(const float *x, uint8_t *dst, int n, int h, int w, int64_t x_img_stride, int ky, int kx, int kh, int kw,
+                            int64_t dst_row_stride, int64_t dst_img_stride, edvr_stream_t stream);
+int edvr_copy_rect_f32(const float *x, float *dst, int n, int h, int w, int64_t x_img_stride, int ky, int kx, int kh, int kw,
+                       int64_t dst_row_stride, int64_t dst_plane_stride, int64_t dst_img_stride, edvr_stream_t stream);
+
 /* Multi-tensor Adam step <- torch.optim.Adam.step() as the reference builds it (basicsr/models/edvr_model.py:21-53, parameter
  * groups with dcn_lr_mul; stepped in sr_model.py:112).  `chunk_table` is a DEVICE array of n_chunks records of
  * edvr_adam_chunk_bytes() = 64 bytes: { float *p; const float *g; float *m; float *v; int32 n (<= 65536 elements of one tensor);

@@ -9,6 +9,14 @@ VideoRestorer (once per frame), same seeded video, same chunk / batch, one proce
 Per arm: frames/s (median over the repeats) with the spread, peak device memory, and the per-kernel table of ONE restore (events
 around every launch through ops.LAUNCH_HOOK: the gather's and the uint8 tail's share is a number).  Prints one JSON line and merges
 it into --json (default profiles/video/bench_video.json) under the configuration's name.
+
+Frames of any size (VideoRestorer pad_mode / tile), same method, merged into profiles/video/bench_video_tiles.json:
+
+    python scripts/bench_video.py --leg pad --config L_T5 [--out-dtype uint8]   # 270x480: pad_mode='reflect' against host F.pad + slice
+    python scripts/bench_video.py --leg pad --config L_deblur                   # 1080x1920
+    python scripts/bench_video.py --leg tiles --config L_T5                     # 544x960 untiled against 2x2 tiles, time and peak memory
+    python scripts/bench_video.py --leg seam --config L_T5                      # |tiled - untiled| near and away from the cuts, per overlap
+    python scripts/bench_video.py --leg large --config L_T5                     # peak memory against frame area, extrapolated
 """
 import argparse
 import json
@@ -59,6 +67,212 @@ def kernel_table(run):
             'kernels': [{'name': k, 'launches': d[0], 'ms': round(d[1], 3), 'share': round(d[1] / total, 4)} for k, d in rows]}
 
 
+RECT_KERNELS = ('crop_pad_frames', 'upsample4x_add_rect', 'upsample4x_add_u8_rect', 'f32_to_u8_hwc_rect', 'copy_rect')
+LEG_HW = {'pad': {'L_T5': (270, 480), 'L_T7': (270, 480), 'L_deblur': (1080, 1920), 'toy': (30, 46)},
+          'tiles': {'L_T5': (544, 960), 'L_T7': (544, 960), 'L_deblur': (2176, 3840), 'toy': (64, 96)}}
+
+
+def _build_net(kwargs, dev):
+    from edvr_amd import EDVR
+    torch.manual_seed(10)
+    net = EDVR(**kwargs).eval()
+    g = torch.Generator().manual_seed(123)
+    with torch.no_grad():  # sub-pixel offsets instead of the all-zero default init (as main() below)
+        for name, p in net.named_parameters():
+            if name.endswith('conv_offset.weight'):
+                p.copy_(torch.randn(p.shape, generator=g) * 0.02)
+            elif name.endswith('conv_offset.bias'):
+                p.copy_(torch.randn(p.shape, generator=g) * 0.5)
+    return net.to(dev)
+
+
+def _two_arms(arms, frames, repeats, net):
+    """The measurement of main() for two callables: warm-up, peak memory of one run, `repeats` alternated timed runs, kernel tables."""
+    res = {k: {'s': []} for k in arms}
+    outs = {}
+    for k, fn in arms.items():
+        fn()
+        torch.cuda.synchronize()
+        torch.cuda.empty_cache()
+        torch.cuda.reset_peak_memory_stats()
+        outs[k] = fn()
+        torch.cuda.synchronize()
+        res[k]['peak_mem_mb'] = round(torch.cuda.max_memory_allocated() / 2 ** 20, 1)
+    for _ in range(repeats):
+        for k, fn in arms.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            e0.record()
+            fn()
+            e1.record()
+            e1.synchronize()
+            res[k]['s'].append(e0.elapsed_time(e1) * 1e-3)
+    net.check_offsets()
+    for k, fn in arms.items():
+        tab = kernel_table(fn)
+        res[k]['kernel_ms'] = tab['kernel_ms']
+        res[k]['crop_and_rect_store_ms'] = round(sum(r['ms'] for r in tab['kernels'] if r['name'] in RECT_KERNELS), 3)
+        res[k]['crop_and_rect_store_share'] = round(res[k]['crop_and_rect_store_ms'] / tab['kernel_ms'], 5)
+        res[k]['gather_share'] = round(sum(r['ms'] for r in tab['kernels'] if r['name'] == 'gather_images') / tab['kernel_ms'], 5)
+        res[k]['launches'] = sum(r['launches'] for r in tab['kernels'])
+    net.check_offsets()
+    for r in res.values():
+        sec = r.pop('s')
+        r['seconds'] = [round(v, 4) for v in sec]
+        r['frames_per_s'] = round(frames / statistics.median(sec), 3)
+        r['spread'] = round((max(sec) - min(sec)) / statistics.median(sec), 4)
+    return res, outs
+
+
+def leg_pad(args, net, kwargs, dev, frames, chunk):
+    """pad_mode='reflect' against the caller-side way: F.pad of the float frames, the plain restore, slice + .contiguous()."""
+    import torch.nn.functional as F
+    from edvr_amd import VideoRestorer
+    h, w = LEG_HW['pad'][args.config]
+    m, s = (16, 1) if kwargs.get('hr_in') else (4, 4)
+    hp, wp = -(-h // m) * m, -(-w // m) * m
+    dt = getattr(torch, args.out_dtype)
+    lq = torch.rand(frames, 3, h, w, generator=torch.Generator().manual_seed(0)).to(dev)
+    plain = VideoRestorer(net, padding=args.padding, chunk=chunk, out_dtype=dt)
+    padded = VideoRestorer(net, padding=args.padding, chunk=chunk, out_dtype=dt, pad_mode='reflect')
+
+    def host_pad():
+        out = plain.restore(F.pad(lq, (0, wp - w, 0, hp - h), mode='reflect'))
+        return (out[:, :s * h, :s * w] if dt == torch.uint8 else out[..., :s * h, :s * w]).contiguous()
+
+    res, outs = _two_arms({'host_pad': host_pad, 'pad_mode': lambda: padded.restore(lq)}, frames, args.repeats, net)
+    ratio = res['pad_mode']['frames_per_s'] / res['host_pad']['frames_per_s']
+    return {'leg': 'pad', 'hw': [h, w], 'padded_hw': [hp, wp], 'bit_identical': bool(torch.equal(outs['host_pad'], outs['pad_mode'])),
+            'ratio_pad_mode_over_host_pad': round(ratio, 4), 'not_slower_beyond_parent_spread': bool(ratio >= 1.0 - res['host_pad']['spread']),
+            **res}
+
+
+def _default_2x2(h, w, m):
+    """Tile of a 2 x 2 grid at the default overlap of 8 m: two tiles per axis sharing exactly the overlap."""
+    ov = 8 * m
+    return (-(-(h + ov) // (2 * m)) * m, -(-(w + ov) // (2 * m)) * m), ov
+
+
+def leg_tiles(args, net, kwargs, dev, frames, chunk):
+    from edvr_amd import VideoRestorer, tile_grid
+    h, w = LEG_HW['tiles'][args.config]
+    m = 16 if kwargs.get('hr_in') else 4
+    tile, ov = _default_2x2(h, w, m)
+    grid = tile_grid(h, w, tile, None, m)
+    assert len(grid) == 4, grid
+    dt = getattr(torch, args.out_dtype)
+    lq = torch.rand(frames, 3, h, w, generator=torch.Generator().manual_seed(0)).to(dev)
+    plain = VideoRestorer(net, padding=args.padding, chunk=chunk, out_dtype=dt)
+    tiled = VideoRestorer(net, padding=args.padding, chunk=chunk, out_dtype=dt, tile=tile)
+    # (the tiled arm first: the kernels' grow-only workspaces (ops.workspace) stay allocated, and the untiled arm's larger ones would
+    # otherwise be booked on the tiled arm's peak)
+    res, outs = _two_arms({'tiled': lambda: tiled.restore(lq), 'untiled': lambda: plain.restore(lq)}, frames, args.repeats, net)
+    area = sum(t.src[2] * t.src[3] for t in grid) / float(-(-h // m) * m * (-(-w // m) * m))
+    t_ratio = res['untiled']['frames_per_s'] / res['tiled']['frames_per_s']
+    return {'leg': 'tiles', 'hw': [h, w], 'tile': list(tile), 'tile_overlap': ov, 'tiles': len(grid),
+            'derived_time_ratio_sum_of_tile_areas_over_frame_area': round(area, 4), 'measured_time_ratio_tiled_over_untiled': round(t_ratio, 4),
+            'kernel_time_ratio_tiled_over_untiled': round(res['tiled']['kernel_ms'] / res['untiled']['kernel_ms'], 4),
+            'peak_memory_ratio_tiled_over_untiled': round(res['tiled']['peak_mem_mb'] / res['untiled']['peak_mem_mb'], 4), **res}
+
+
+def leg_seam(args, net, kwargs, dev, frames, chunk):
+    """max / mean |tiled - untiled| relative to the output scale inside a band of `overlap` output pixels around the cuts and outside
+    it, per overlap.  Weights: random init with sub-pixel offsets - NOT a trained model's; input: structured synthetic motion."""
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..', 'tests'))
+    from util_edvr import motion_frames
+    from edvr_amd import VideoRestorer, tile_grid
+    m, s = (16, 1) if kwargs.get('hr_in') else (4, 4)
+    h, w = (256, 384) if args.config != 'toy' else (96, 128)
+    frames = min(frames, 12)
+    lq = motion_frames(1, (frames, 3, h, w), seed=0)[0].to(dev)
+    ref = VideoRestorer(net, padding=args.padding, chunk=chunk).restore(lq)
+    scale = ref.abs().max().item()
+    rows = []
+    for ov in (0, 2 * m, 8 * m, 16 * m):
+        tile = (-(-(h + ov) // (2 * m)) * m, -(-(w + ov) // (2 * m)) * m)
+        grid = tile_grid(h, w, tile, ov, m)
+        out = VideoRestorer(net, padding=args.padding, chunk=chunk, tile=tile, tile_overlap=ov).restore(lq)
+        d = (out - ref).abs() / scale
+        band = torch.zeros(s * h, s * w, dtype=torch.bool, device=dev)
+        width = max(ov, 2 * m) * s  # (overlap 0: a band of 2 m, or there would be nothing to report)
+        for t in grid:
+            oy, ox = t.dst
+            if oy > 0:
+                band[max(s * oy - width, 0):s * oy + width] = True
+            if ox > 0:
+                band[:, max(s * ox - width, 0):s * ox + width] = True
+        inside, outside = d[..., band], d[..., ~band]
+        rows.append({'overlap': ov, 'tile': list(tile), 'tiles': len(grid), 'band_output_pixels': width,
+                     'band_max': inside.max().item(), 'band_mean': inside.mean().item(),
+                     'outside_max': outside.max().item() if outside.numel() else None,  # (a toy frame can be all band)
+                     'outside_mean': outside.mean().item() if outside.numel() else None})
+    net.check_offsets()
+    return {'leg': 'seam', 'hw': [h, w], 'frames': frames, 'weights': 'random init, conv_offset N(0, 0.02) / bias N(0, 0.5): not a trained model',
+            'input': 'util_edvr.motion_frames', 'output_scale': scale, 'overlaps': rows}
+
+
+def leg_large(args, net, kwargs, dev, frames, chunk):
+    """Peak memory of a chunk-1 restore of 7 frames against the frame area, untiled and 2 x 2 tiles, on sizes far from the limit; a
+    line through the points gives the largest frame that fits.  Nothing is run near the limit."""
+    from edvr_amd import VideoRestorer
+    m = 16 if kwargs.get('hr_in') else 4
+    sizes = [(180, 320), (360, 640), (544, 960)] if args.config != 'toy' else [(64, 96), (96, 144), (128, 192)]
+    total = torch.cuda.get_device_properties(dev).total_memory
+    pts = {'untiled': [], 'tiled': []}
+    for h, w in sizes:
+        lq = torch.rand(7, 3, h, w, generator=torch.Generator().manual_seed(0)).to(dev)
+        for key in pts:
+            kw = {'tile': _default_2x2(h, w, m)[0]} if key == 'tiled' else {}
+            vr = VideoRestorer(net, padding=args.padding, chunk=1, out_dtype=torch.uint8, **kw)
+            vr.restore(lq)
+            torch.cuda.synchronize()
+            torch.cuda.empty_cache()
+            torch.cuda.reset_peak_memory_stats()
+            vr.restore(lq)
+            torch.cuda.synchronize()
+            pts[key].append([h * w, round(torch.cuda.max_memory_allocated() / 2 ** 20, 1)])
+        del lq
+    net.check_offsets()
+
+    def line(p):  # through the two largest points: MB = a + b * area
+        (x0, y0), (x1, y1) = p[-2], p[-1]
+        b = (y1 - y0) / (x1 - x0)
+        return y0 - b * x0, b
+    out = {'leg': 'large', 'frames': 7, 'chunk': 1, 'device_memory_mb': round(total / 2 ** 20, 1), 'points_area_peak_mb': pts}
+    budget = 0.85 * total / 2 ** 20
+    for key in pts:
+        a, b = line(pts[key])
+        out[key + '_mb_per_megapixel'] = round(b * 1e6, 1)
+        out[key + '_largest_lq_megapixels_at_85_percent_of_memory_extrapolated'] = round((budget - a) / b * 1e-6, 3)
+    a, b = line(pts['tiled'])
+    area4 = 4e6 * out['untiled_largest_lq_megapixels_at_85_percent_of_memory_extrapolated']
+    out['tiled_2x2_peak_mb_at_4x_the_largest_untiled_area_extrapolated'] = round(a + b * area4, 1)
+    out['fits'] = bool(a + b * area4 < budget)
+    return out
+
+
+def main_leg(args):
+    from edvr_amd import _lib
+    from edvr_amd.build import source_hash
+    kwargs, _, frames, chunk, _ = CONFIGS[args.config]
+    frames, chunk = args.frames or frames, args.chunk or chunk
+    dev = torch.device('cuda:0')
+    net = _build_net(kwargs, dev)
+    with torch.no_grad():
+        result = {'pad': leg_pad, 'tiles': leg_tiles, 'seam': leg_seam, 'large': leg_large}[args.leg](args, net, kwargs, dev, frames, chunk)
+    result = {'config': args.config, 'edvr': dict(kwargs), 'frames': frames, 'chunk': chunk, 'padding': args.padding, 'out_dtype': args.out_dtype,
+              'repeats': args.repeats, **result, 'csrc_sha16': source_hash(), 'library': _lib.lib().edvr_version().decode(),
+              'device': torch.cuda.get_device_name(0)}
+    path = os.path.abspath(args.json or os.path.join(os.path.dirname(os.path.abspath(__file__)), '..', 'profiles', 'video', 'bench_video_tiles.json'))
+    os.makedirs(os.path.dirname(path), exist_ok=True)
+    merged = json.load(open(path)) if os.path.exists(path) else {}
+    merged[f'{args.leg}_{args.config}' + ('' if args.out_dtype == 'float32' else '_' + args.out_dtype)] = result
+    with open(path, 'w') as f:
+        json.dump(merged, f, indent=1, sort_keys=True)
+        f.write('\n')
+    print(json.dumps(result))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--config', default='L_T5', choices=sorted(CONFIGS))
@@ -67,10 +281,14 @@ def main():
     ap.add_argument('--repeats', type=int, default=5)
     ap.add_argument('--padding', default='reflection_circle')
     ap.add_argument('--out-dtype', default='float32', choices=['float32', 'uint8'])
-    ap.add_argument('--json', default=os.path.join(os.path.dirname(os.path.abspath(__file__)), '..', 'profiles', 'video', 'bench_video.json'))
+    ap.add_argument('--json', default=None, help='default: profiles/video/bench_video.json (bench_video_tiles.json with --leg)')
+    ap.add_argument('--leg', default=None, choices=['pad', 'tiles', 'seam', 'large'], help='frames of any size: pad_mode / tile measurements')
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit('bench_video.py measures on the GPU: none found')
+    if args.leg:
+        return main_leg(args)
+    args.json = args.json or os.path.join(os.path.dirname(os.path.abspath(__file__)), '..', 'profiles', 'video', 'bench_video.json')
     from edvr_amd import EDVR, VideoRestorer, _lib, metrics
     from edvr_amd.build import source_hash
     kwargs, (h, w), frames, chunk, share = CONFIGS[args.config]

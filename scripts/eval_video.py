@@ -1,7 +1,7 @@
 """scripts/test_reds.py for the folder datasets (REDS4 / Vid4 layout) with every frame's features extracted ONCE per clip
 (metrics.validate_video on edvr_amd/video.py: VideoRestorer) instead of once per window the frame appears in.  Same options, same
 sharding of the clips over the ranks, same per-folder and overall averages; `--batch` is the number of output frames per alignment /
-fusion / reconstruction pass.
+fusion / reconstruction pass.  `--pad-mode reflect` admits frames of any size, `--tile TH TW` bounds the memory of large ones.
 
     python scripts/eval_video.py --lq datasets/REDS4/sharp_bicubic --gt datasets/REDS4/GT --weights EDVR_L_x4_SR_REDS_official.pth
 
@@ -30,11 +30,13 @@ def evaluate(args, log=print):
         load_network(net, args.weights, strict=True)
     ds = VideoTestClips(dict(dataroot_gt=args.gt, dataroot_lq=args.lq, io_backend=dict(type='disk'), num_frame=args.num_frame,
                              padding=args.padding, name=args.name, cache_data=True), device=device)
+    # frames of any size (--pad-mode / --tile / --tile-overlap): passed on only where given
+    any_size = {k: (tuple(v) if k == 'tile' else v) for k in ('pad_mode', 'tile', 'tile_overlap') for v in [getattr(args, k, None)] if v is not None}
     results = {}
     for folder in ds.folders[rank::world]:
         lq, gt = ds.clip(folder)
         _, psnr = metrics.validate_video(net, lq, gt, num_frame=args.num_frame, padding=args.padding, chunk=args.batch,
-                                         crop_border=args.crop_border, test_y_channel=args.test_y_channel)
+                                         crop_border=args.crop_border, test_y_channel=args.test_y_channel, **any_size)
         results[folder] = (sum(psnr), len(psnr))
         ds._cache.pop(folder, None)  # one clip resident at a time
     if world > 1:
@@ -70,6 +72,10 @@ def main():
     ap.add_argument('--crop-border', type=int, default=0)
     ap.add_argument('--test-y-channel', action='store_true')
     ap.add_argument('--batch', type=int, default=8, help='output frames per pass (VideoRestorer chunk)')
+    ap.add_argument('--pad-mode', default=None, choices=['reflect', 'replicate'],
+                    help='frames of any size: extend them at the bottom and right to the size multiple (4; 16 with --hr-in), crop the output')
+    ap.add_argument('--tile', type=int, nargs=2, default=None, metavar=('TH', 'TW'), help='restore tile by tile (input pixels, multiples of the size multiple)')
+    ap.add_argument('--tile-overlap', type=int, default=None, help='input pixels neighbouring tiles share (default 8 x the size multiple)')
     evaluate(ap.parse_args())
 
 
