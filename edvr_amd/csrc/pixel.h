@@ -47,4 +47,22 @@ __device__ __forceinline__ float upsample_at(const float *__restrict__ src, int 
   return bilerp(src[y0 * w + x0], src[y0 * w + x1], src[y1 * w + x0], src[y1 * w + x1], lx, ly);
 }
 
+// 4 consecutive pixels of an interleaved (h, w, 3) byte row: v[c][i] = channel c of pixel i, already an integer in [0, 255] (to_u8); three
+// dword stores where `o` is 4-byte aligned, twelve byte stores otherwise.  Shared by the byte tails of video.hip and resize.hip.
+__device__ __forceinline__ void store_px4(uint8_t *__restrict__ o, const float (&v)[3][4], bool aligned) {
+  uint8_t b[12];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int c = 0; c < 3; ++c) b[3 * i + c] = (uint8_t)(unsigned)v[c][i];
+  if (aligned) {
+    uint32_t *o32 = reinterpret_cast<uint32_t *>(o);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) o32[k] = (uint32_t)b[4 * k] | ((uint32_t)b[4 * k + 1] << 8) | ((uint32_t)b[4 * k + 2] << 16) | ((uint32_t)b[4 * k + 3] << 24);
+  } else {
+#pragma unroll
+    for (int k = 0; k < 12; ++k) o[k] = b[k];
+  }
+}
+
 }  // namespace edvr

@@ -53,22 +53,6 @@ __global__ __launch_bounds__(256) void gather_images_kernel(const GatherArgs a) 
 
 // thread = 4 consecutive pixels of one output row (the output width 4w is always a multiple of 4): three 16-byte loads of y (one per
 // channel) where it is aligned, twelve bilinear samples of base, twelve bytes = three dword stores where out is aligned.
-__device__ __forceinline__ void store_px4(uint8_t *__restrict__ o, const float (&v)[3][4], bool aligned) {
-  uint8_t b[12];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int c = 0; c < 3; ++c) b[3 * i + c] = (uint8_t)(unsigned)v[c][i];
-  if (aligned) {
-    uint32_t *o32 = reinterpret_cast<uint32_t *>(o);
-#pragma unroll
-    for (int k = 0; k < 3; ++k) o32[k] = (uint32_t)b[4 * k] | ((uint32_t)b[4 * k + 1] << 8) | ((uint32_t)b[4 * k + 2] << 16) | ((uint32_t)b[4 * k + 3] << 24);
-  } else {
-#pragma unroll
-    for (int k = 0; k < 12; ++k) o[k] = b[k];
-  }
-}
-
 __global__ __launch_bounds__(256) void upsample4x_add_u8_kernel(const float *__restrict__ y, const float *__restrict__ base, uint8_t *__restrict__ out,
                                                                 int n, int h, int w, int aligned) {
   const int ho = 4 * h, wo = 4 * w;

@@ -322,6 +322,61 @@ def read_img_seq(paths, device='cuda', require_mod_crop=False, scale=1, num_thre
     return frames_to_device(np.stack(imgs)[None], None, device)[0]
 
 
+# ------------------------------------------------------------------------------------------------ bicubic imresize (csrc/resize.hip)
+IMRESIZE_SCALE_RANGE = (1 / 8, 8)
+
+
+def _imresize_reach(n_in, n_out, scale, aa_down):
+    """How many samples the taps of one axis reach before the first / beyond the last sample of the frame (sym_len_s / sym_len_e of
+    calculate_weights_indices, matlab_functions.py:81-82): weights are non-zero strictly inside (u - kw / 2, u + kw / 2)."""
+    kw = 4.0 / scale if aa_down else 4.0
+    shift = 0.5 * (1.0 - 1.0 / scale)
+    first = math.floor(1 / scale + shift - kw / 2) + 1  # 1-based
+    last = math.ceil(n_out / scale + shift + kw / 2) - 1
+    return max(0, 1 - first), max(0, last - n_in)
+
+
+def imresize_shape(h, w, scale, antialiasing=True):
+    """(h', w') = (ceil(h * scale), ceil(w * scale)) of imresize (matlab_functions.py:113).  ValueError for a scale outside [1/8, 8] and for
+    a frame shorter on an axis than the symmetric extension reaches there (the reference indexes past its mirrored patch then): the
+    check every caller of the kernel goes through before a launch.  Pure Python."""
+    scale = float(scale)
+    if not IMRESIZE_SCALE_RANGE[0] <= scale <= IMRESIZE_SCALE_RANGE[1]:
+        raise ValueError(f'imresize: scale {scale} is outside [1/8, 8]')
+    h, w = int(h), int(w)
+    if h <= 0 or w <= 0:
+        raise ValueError(f'imresize: empty {h} x {w} frame')
+    out = math.ceil(h * scale), math.ceil(w * scale)
+    aa_down = bool(antialiasing) and scale < 1
+    for n_in, n_out, axis in ((h, out[0], 'rows'), (w, out[1], 'columns')):
+        reach = _imresize_reach(n_in, n_out, scale, aa_down)
+        if max(reach) > n_in:
+            raise ValueError(f'imresize: {n_in} {axis} are fewer than the symmetric extension reaches at scale {scale} ({reach[0]} before, {reach[1]} after)')
+    return out
+
+
+def imresize(img, scale, antialiasing=True):
+    """imresize (basicsr/utils/matlab_functions.py:88-170; MATLAB's antialiased bicubic, "BI") on the device: img (c, h, w) float32 in [0, 1]
+    on the GPU -> (c, h', w') float32, not rounded or clamped.  Also batches: float32 (n, 3, h, w) -> (n, 3, h', w') and uint8 (n, h, w, 3)
+    -> float32 (n, 3, h', w').  c = 3 (ops.imresize; its out_dtype=torch.uint8 gives the bytes a stored dataset holds).  CPU tensors raise
+    NotImplementedError: there is no fallback."""
+    from . import ops
+    if not torch.is_tensor(img):
+        raise NotImplementedError('edvr_amd.data.imresize takes device tensors (the numpy form of the reference runs on the host)')
+    if img.dim() == 3 and img.dtype != torch.uint8:
+        return ops.imresize(img[None], scale, antialiasing)[0]
+    return ops.imresize(img, scale, antialiasing)
+
+
+def lq_from_gt(gt, scale, quantize=True):
+    """The x`scale` LQ frames of GT frames (t, 3, H, W) float32 on the device, H and W multiples of `scale`: imresize by 1 / scale,
+    rounded to 8 bits when `quantize` (what a stored PNG dataset contains) - generate_bicubic_img.m without the files."""
+    from . import ops
+    if not quantize:
+        return ops.imresize(gt, 1 / scale)
+    return ops.frames_u8_to_f32(ops.imresize(gt, 1 / scale, out_dtype=torch.uint8)[None])[0]
+
+
 class VideoTestClips:
     """VideoTestDataset (basicsr/data/video_test_dataset.py:11-147) with the frames kept on the device.
 
@@ -329,7 +384,10 @@ class VideoTestClips:
     `data_info` lists and the same items from __getitem__ ({'lq' (t, c, h, w), 'gt' (c, h, w), 'folder', 'idx', 'border',
     'lq_path'}), except that the tensors live on the GPU: a clip is decoded once on the host (threads), converted by
     edvr_frames_u8_to_f32 and cached there (100 REDS4 frames: 83 MB LQ + 1.1 GB GT in fp32, nothing next to 288 GB), so that
-    metrics.validate_clip can batch the windows of a whole clip.  clip(folder) returns the (lq, gt) pair of one folder."""
+    metrics.validate_clip can batch the windows of a whole clip.  clip(folder) returns the (lq, gt) pair of one folder.
+
+    Without an LQ folder: dataroot_lq None and lq_from_gt = {'scale': 4, 'quantize': True} derive the LQ frames from the decoded GT on
+    the device (lq_from_gt above; GT mod-cropped to a multiple of the scale first, as read_img_seq(require_mod_crop=True) does)."""
 
     def __init__(self, opt, device='cuda'):
         import glob
@@ -339,6 +397,12 @@ class VideoTestClips:
         self.opt, self.device = opt, device
         self.cache_data = opt['cache_data']
         self.gt_root, self.lq_root = opt['dataroot_gt'], opt['dataroot_lq']
+        self.lq_from_gt = dict(opt['lq_from_gt']) if self.lq_root is None and opt.get('lq_from_gt') else None
+        if self.lq_from_gt is not None:
+            self.lq_from_gt = {'scale': int(self.lq_from_gt['scale']), 'quantize': bool(self.lq_from_gt.get('quantize', True))}
+            if not 1 <= self.lq_from_gt['scale'] <= 1 / IMRESIZE_SCALE_RANGE[0]:
+                raise ValueError(f"lq_from_gt: scale {self.lq_from_gt['scale']} is outside 1..8")
+            self.lq_root = self.gt_root  # the 'LQ' files of data_info are the GT files the frames are made from
         assert dict(opt['io_backend'])['type'] != 'lmdb', 'No need to use lmdb during validation/test.'
         self.data_info = {'lq_path': [], 'gt_path': [], 'folder': [], 'idx': [], 'border': []}
         self.imgs_lq, self.imgs_gt, self._cache = {}, {}, {}
@@ -383,10 +447,19 @@ class VideoTestClips:
         """(lq (t, 3, h, w), gt (t, 3, H, W)) of one folder on the device."""
         if folder in self._cache:
             return self._cache[folder]
-        pair = (read_img_seq(self.imgs_lq[folder], self.device), read_img_seq(self.imgs_gt[folder], self.device))
+        pair = self._read(self.imgs_lq[folder], self.imgs_gt[folder])
         if self.cache_data:
             self._cache[folder] = pair
         return pair
+
+    def _read(self, paths_lq, paths_gt):
+        """(lq, gt) frames of the listed files; with lq_from_gt the LQ frames come from the GT files at paths_lq."""
+        if self.lq_from_gt is None:
+            return read_img_seq(paths_lq, self.device), read_img_seq(paths_gt, self.device)
+        scale, quantize = self.lq_from_gt['scale'], self.lq_from_gt['quantize']
+        gt = read_img_seq(paths_gt, self.device, require_mod_crop=True, scale=scale)
+        src = gt if list(paths_lq) == list(paths_gt) else read_img_seq(paths_lq, self.device, require_mod_crop=True, scale=scale)
+        return lq_from_gt(src, scale, quantize), gt
 
     def __getitem__(self, index):
         folder = self.data_info['folder'][index]
@@ -397,8 +470,8 @@ class VideoTestClips:
             imgs_lq = lq.index_select(0, torch.tensor(select_idx, device=lq.device))
             img_gt = gt[idx]
         else:
-            imgs_lq = read_img_seq([self.imgs_lq[folder][i] for i in select_idx], self.device)
-            img_gt = read_img_seq([self.imgs_gt[folder][idx]], self.device)[0]
+            imgs_lq, gts = self._read([self.imgs_lq[folder][i] for i in select_idx], [self.imgs_gt[folder][idx]])
+            img_gt = gts[0]
         return {'lq': imgs_lq, 'gt': img_gt, 'folder': folder, 'idx': self.data_info['idx'][index],
                 'border': self.data_info['border'][index], 'lq_path': self.data_info['lq_path'][index]}
 

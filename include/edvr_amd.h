@@ -514,6 +514,27 @@ int edvr_f32_to_u8_hwc_rect(const float *x, uint8_t *dst, int n, int h, int w, i
 int edvr_copy_rect_f32(const float *x, float *dst, int n, int h, int w, int64_t x_img_stride, int ky, int kx, int kh, int kw,
                        int64_t dst_row_stride, int64_t dst_plane_stride, int64_t dst_img_stride, edvr_stream_t stream);
 
+/* MATLAB-style bicubic imresize on the device <- imresize / calculate_weights_indices (basicsr/utils/matlab_functions.py:88-170 and
+ * 17-84; the Python statement of scripts/matlab_scripts/generate_bicubic_img.m, i.e. of "BI x4"): one launch resamples n frames by one
+ * factor on both axes, rows first, then columns, accumulating in fp32.  Per axis, for the 1-based output x: u = x / scale + 0.5 (1 - 1 /
+ * scale), support 4 (4 / scale and kernel scale * cubic(scale * d) when scale < 1 and antialiasing != 0), first tap floor(u - support / 2),
+ * ceil(support) + 2 taps of the Keys cubic (a = -0.5), normalised to sum 1; a tap outside the frame reads the symmetric extension
+ * (... 1 0 | 0 1 ...).  The weights are computed inside the kernel (per workgroup, in LDS): no table tensors, no allocation, no wait.
+ * (ho, wo) = (ceil(H * scale), ceil(W * scale)) are computed by the caller.  1/8 <= scale <= 8; a frame shorter on an axis than the
+ * symmetric extension reaches there is EDVR_ERR_ARG, as is n > 65535.
+ * _u8: src (n, H, W, 3) dense bytes, each divided by 255 exactly as edvr_frames_u8_to_f32 rounds it; _f32: src (n, 3, H, W), dense images
+ * src_img_stride floats apart.  out_kind EDVR_RESIZE_OUT_F32: dst (n, 3, ho, wo) dense float32, NOT clamped (an enlargement overshoots
+ * [0, 1], as the reference's does); EDVR_RESIZE_OUT_U8: dst (n, ho, wo, 3) dense bytes = tensor2img (clamp, x 255, round half to even) of
+ * that float - bit for bit, and the _u8 source gives bit for bit what the _f32 source holding byte / 255 gives.  16-byte loads where the
+ * source rows start on 16-byte boundaries (3 W % 16 == 0 bytes / W % 4 == 0 floats, aligned pointer and stride), 16-byte float and dword
+ * byte stores where wo % 4 == 0 and dst is aligned; narrower accesses otherwise. */
+#define EDVR_RESIZE_OUT_F32 0
+#define EDVR_RESIZE_OUT_U8 1
+int edvr_imresize_bicubic_u8(const uint8_t *src, void *dst, int n, int H, int W, int ho, int wo, double scale, int antialiasing,
+                             int out_kind, edvr_stream_t stream);
+int edvr_imresize_bicubic_f32(const float *src, void *dst, int n, int H, int W, int64_t src_img_stride, int ho, int wo, double scale,
+                              int antialiasing, int out_kind, edvr_stream_t stream);
+
 /* Multi-tensor Adam step <- torch.optim.Adam.step() as the reference builds it (basicsr/models/edvr_model.py:21-53, parameter
  * groups with dcn_lr_mul; stepped in sr_model.py:112).  `chunk_table` is a DEVICE array of n_chunks records of
  * edvr_adam_chunk_bytes() = 64 bytes: { float *p; const float *g; float *m; float *v; int32 n (<= 65536 elements of one tensor);

@@ -4,6 +4,11 @@ sharding of the clips over the ranks, same per-folder and overall averages; `--b
 fusion / reconstruction pass.  `--pad-mode reflect` admits frames of any size, `--tile TH TW` bounds the memory of large ones.
 
     python scripts/eval_video.py --lq datasets/REDS4/sharp_bicubic --gt datasets/REDS4/GT --weights EDVR_L_x4_SR_REDS_official.pth
+    python scripts/eval_video.py --lq-from-gt 4 --bicubic-baseline --gt my_footage --weights EDVR_L_x4_SR_REDS_official.pth
+
+`--lq-from-gt SCALE` needs no LQ folder: the LQ frames are MATLAB's bicubic reduction of the GT frames, made on the device
+(edvr_amd.data.imresize, 8-bit like a stored dataset).  `--bicubic-baseline` scores the bicubic enlargement of the LQ frames beside the
+model (the LQ frames themselves for --hr-in networks); `--json FILE` writes what is printed.
 
 The Vimeo90K-Test list is one window per item - nothing to reuse: use scripts/test_reds.py --vimeo-meta for it.
 """
@@ -14,6 +19,19 @@ import sys
 import torch
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..'))
+
+
+def bicubic_baseline(lq, gt, hr_in=False, crop_border=0, test_y_channel=False, chunk=8):
+    """PSNR per frame of the bicubic enlargement of `lq` (t, 3, h, w) to the size of `gt` (t, 3, H, W) - the LQ frames themselves when
+    hr_in - scored exactly as the model's output is."""
+    from edvr_amd import metrics
+    from edvr_amd.data import imresize
+    scale = 1 if hr_in else gt.shape[-1] // lq.shape[-1]
+    scores = []
+    for s0 in range(0, lq.shape[0], chunk):
+        part = lq[s0:s0 + chunk]
+        scores += metrics.calculate_psnr(part if scale == 1 else imresize(part, scale), gt[s0:s0 + chunk], crop_border, test_y_channel)
+    return scores
 
 
 def evaluate(args, log=print):
@@ -28,37 +46,63 @@ def evaluate(args, log=print):
                with_predeblur=args.with_predeblur, with_tsa=not args.no_tsa).to(device).eval()
     if args.weights:
         load_network(net, args.weights, strict=True)
-    ds = VideoTestClips(dict(dataroot_gt=args.gt, dataroot_lq=args.lq, io_backend=dict(type='disk'), num_frame=args.num_frame,
-                             padding=args.padding, name=args.name, cache_data=True), device=device)
+    opt = dict(dataroot_gt=args.gt, dataroot_lq=args.lq, io_backend=dict(type='disk'), num_frame=args.num_frame,
+               padding=args.padding, name=args.name, cache_data=True)
+    lq_from_gt, baseline = getattr(args, 'lq_from_gt', None), getattr(args, 'bicubic_baseline', False)
+    if args.lq is None:
+        if not lq_from_gt:
+            raise ValueError('either an LQ folder or lq_from_gt is needed')
+        opt['lq_from_gt'] = dict(scale=lq_from_gt, quantize=True)
+    ds = VideoTestClips(opt, device=device)
     # frames of any size (--pad-mode / --tile / --tile-overlap): passed on only where given
     any_size = {k: (tuple(v) if k == 'tile' else v) for k in ('pad_mode', 'tile', 'tile_overlap') for v in [getattr(args, k, None)] if v is not None}
-    results = {}
+    results, base = {}, {}
     for folder in ds.folders[rank::world]:
         lq, gt = ds.clip(folder)
         _, psnr = metrics.validate_video(net, lq, gt, num_frame=args.num_frame, padding=args.padding, chunk=args.batch,
                                          crop_border=args.crop_border, test_y_channel=args.test_y_channel, **any_size)
         results[folder] = (sum(psnr), len(psnr))
+        if baseline:
+            b = bicubic_baseline(lq, gt, args.hr_in, args.crop_border, args.test_y_channel, args.batch)
+            base[folder] = (sum(b), len(b))
         ds._cache.pop(folder, None)  # one clip resident at a time
-    if world > 1:
-        gathered = [None] * world
-        torch.distributed.all_gather_object(gathered, results)
-        results = {}
-        for part in gathered:
-            for k, (s, n) in part.items():
-                s0, n0 = results.get(k, (0.0, 0))
-                results[k] = (s0 + s, n0 + n)
-    summary = {k: s / max(n, 1) for k, (s, n) in sorted(results.items())}
+
+    def merged(parts):
+        if world > 1:
+            gathered = [None] * world
+            torch.distributed.all_gather_object(gathered, parts)
+            parts = {}
+            for part in gathered:
+                for k, (s, n) in part.items():
+                    s0, n0 = parts.get(k, (0.0, 0))
+                    parts[k] = (s0 + s, n0 + n)
+        return {k: s / max(n, 1) for k, (s, n) in sorted(parts.items())}
+
+    summary, base = merged(results), merged(base) if baseline else {}
     if rank == 0:
+        beside = (lambda v: f' (bicubic {v:.4f} dB)') if baseline else (lambda v: '')
         for k, v in summary.items():
-            log(f'{k}: PSNR {v:.4f} dB')
-        if summary:
-            log(f'average over {len(summary)} folder(s): {sum(summary.values()) / len(summary):.4f} dB')  # the average of the per-folder averages
+            log(f'{k}: PSNR {v:.4f} dB' + beside(base.get(k, float('nan'))))
+        if summary:  # the average of the per-folder averages
+            log(f'average over {len(summary)} folder(s): {sum(summary.values()) / len(summary):.4f} dB' +
+                beside(sum(base.values()) / max(len(base), 1)))
+        if getattr(args, 'json', None):
+            import json
+            record = {'psnr': summary, 'average': sum(summary.values()) / max(len(summary), 1)}
+            if baseline:
+                record.update(bicubic_psnr=base, bicubic_average=sum(base.values()) / max(len(base), 1))
+            with open(args.json, 'w') as f:
+                json.dump(record, f, indent=1)
     return summary
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
-    ap.add_argument('--lq', required=True)
+    ap.add_argument('--lq', default=None, help='LQ folder; optional with --lq-from-gt')
+    ap.add_argument('--lq-from-gt', type=int, default=None, metavar='SCALE',
+                    help='make the LQ frames from the GT frames on the device: MATLAB bicubic reduction by SCALE, 8-bit (GT mod-cropped to SCALE)')
+    ap.add_argument('--bicubic-baseline', action='store_true', help='also report the PSNR of the bicubic enlargement of the LQ frames')
+    ap.add_argument('--json', default=None, metavar='FILE', help='write the per-folder and average results there')
     ap.add_argument('--gt', required=True)
     ap.add_argument('--weights', default=None)
     ap.add_argument('--name', default='REDS4', help='REDS4 | Vid4 | REDSofficial (folder layout of VideoTestDataset)')
@@ -76,7 +120,16 @@ def main():
                     help='frames of any size: extend them at the bottom and right to the size multiple (4; 16 with --hr-in), crop the output')
     ap.add_argument('--tile', type=int, nargs=2, default=None, metavar=('TH', 'TW'), help='restore tile by tile (input pixels, multiples of the size multiple)')
     ap.add_argument('--tile-overlap', type=int, default=None, help='input pixels neighbouring tiles share (default 8 x the size multiple)')
-    evaluate(ap.parse_args())
+    args = ap.parse_args(argv)
+    if (args.lq is None) == (args.lq_from_gt is None):
+        ap.error('give exactly one of --lq and --lq-from-gt')
+    if args.lq_from_gt is not None and not 1 <= args.lq_from_gt <= 8:
+        ap.error('--lq-from-gt takes a scale in 1..8')
+    return args
+
+
+def main():
+    evaluate(parse_args())
 
 
 if __name__ == '__main__':

@@ -1,0 +1,96 @@
+"""The LQ copy of a folder of sharp frames, made on the device: MATLAB's antialiased bicubic imresize ("BI x4") - the replacement for
+the reference's scripts/matlab_scripts/generate_bicubic_img.m.
+
+    python scripts/make_lq.py datasets/REDS4/GT datasets/REDS4/sharp_bicubic --scale 4
+
+GT_ROOT/<clip>/<frame>.png -> LQ_ROOT/<clip>/<frame>.png.  Frames are decoded and encoded on host threads through PIL (as
+edvr_amd/data.py decodes), mod-cropped to a multiple of the scale (as the MATLAB script does), resized by 1 / scale in one launch per
+batch of equal-sized frames (edvr_amd.ops.imresize, uint8 in, uint8 out: the rounding tensor2img applies) and written as 8-bit PNG.
+"""
+import argparse
+import os
+import sys
+from concurrent.futures import ThreadPoolExecutor
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..'))
+
+EXTENSIONS = ('.png', '.jpg', '.jpeg', '.bmp')
+
+
+def walk(gt_root):
+    """[(clip, [frame file names])] of a <clip>/<frame> tree, both sorted; dot files and other file types are skipped."""
+    clips = []
+    for clip in sorted(e.name for e in os.scandir(gt_root) if e.is_dir() and not e.name.startswith('.')):
+        frames = sorted(e.name for e in os.scandir(os.path.join(gt_root, clip))
+                        if e.is_file() and not e.name.startswith('.') and e.name.lower().endswith(EXTENSIONS))
+        if frames:
+            clips.append((clip, frames))
+    return clips
+
+
+def resize_u8(frames_u8, scale, antialiasing, device):
+    """(n, H, W, 3) uint8 host array -> (n, H / scale, W / scale, 3) uint8 host array, resized on the device."""
+    from edvr_amd import ops
+    return ops.imresize(torch.from_numpy(frames_u8).to(device), 1 / scale, antialiasing, out_dtype=torch.uint8).cpu().numpy()
+
+
+def load(path, scale):
+    from edvr_amd.data import decode_image
+    with open(path, 'rb') as f:
+        img = decode_image(f.read())
+    return np.ascontiguousarray(img[:img.shape[0] - img.shape[0] % scale, :img.shape[1] - img.shape[1] % scale])
+
+
+def save(path, rgb_u8):
+    from PIL import Image
+    Image.fromarray(rgb_u8).save(os.path.splitext(path)[0] + '.png', format='PNG')
+
+
+def make_lq(gt_root, lq_root, scale=4, antialiasing=True, batch=16, num_threads=8, device='cuda', log=print):
+    """Returns the number of frames written."""
+    from edvr_amd.data import imresize_shape
+    clips = walk(gt_root)
+    if not clips:
+        raise FileNotFoundError(f'no <clip>/<frame> images under {gt_root}')
+    written = 0
+    with ThreadPoolExecutor(num_threads) as pool:
+        for clip, frames in clips:
+            os.makedirs(os.path.join(lq_root, clip), exist_ok=True)
+            for s0 in range(0, len(frames), batch):
+                names = frames[s0:s0 + batch]
+                imgs = list(pool.map(lambda n: load(os.path.join(gt_root, clip, n), scale), names))
+                for shape in sorted({im.shape for im in imgs}):  # one launch per frame size (a clip normally has one)
+                    sel = [i for i, im in enumerate(imgs) if im.shape == shape]
+                    imresize_shape(shape[0], shape[1], 1 / scale, antialiasing)  # a frame too small for the kernel: ValueError naming it
+                    out = resize_u8(np.stack([imgs[i] for i in sel]), scale, antialiasing, device)
+                    list(pool.map(lambda io: save(os.path.join(lq_root, clip, names[io[0]]), io[1]), zip(sel, out)))
+                written += len(names)
+            log(f'{clip}: {len(frames)} frame(s)')
+    return written
+
+
+def parse_args(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__.split('\n\n')[0])
+    ap.add_argument('gt_root')
+    ap.add_argument('lq_root')
+    ap.add_argument('--scale', type=int, default=4)
+    ap.add_argument('--no-antialias', action='store_true', help="imresize(..., 'Antialiasing', false)")
+    ap.add_argument('--batch', type=int, default=16, help='frames per launch')
+    ap.add_argument('--threads', type=int, default=8, help='host threads decoding and encoding')
+    args = ap.parse_args(argv)
+    if not 1 <= args.scale <= 8:
+        ap.error('--scale must be an integer in 1..8')
+    return args
+
+
+def main():
+    args = parse_args()
+    n = make_lq(args.gt_root, args.lq_root, args.scale, not args.no_antialias, args.batch, args.threads)
+    print(f'{n} frame(s) -> {args.lq_root}')
+
+
+if __name__ == '__main__':
+    main()
