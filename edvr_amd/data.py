@@ -368,13 +368,73 @@ def imresize(img, scale, antialiasing=True):
     return ops.imresize(img, scale, antialiasing)
 
 
-def lq_from_gt(gt, scale, quantize=True):
-    """The x`scale` LQ frames of GT frames (t, 3, H, W) float32 on the device, H and W multiples of `scale`: imresize by 1 / scale,
-    rounded to 8 bits when `quantize` (what a stored PNG dataset contains) - generate_bicubic_img.m without the files."""
+def lq_from_gt(gt, scale, quantize=None, degradation='bi'):
+    """The x`scale` LQ frames of GT frames (t, 3, H, W) float32 on the device, H and W multiples of `scale`.  degradation 'bi': imresize
+    by 1 / scale, rounded to 8 bits when `quantize` (the default; what a stored PNG dataset contains) - generate_bicubic_img.m without
+    the files.  'bd': duf_downsample, NOT rounded unless `quantize` is given as True - VideoTestDUFDataset feeds the float result to the
+    network."""
     from . import ops
+    if degradation not in DEGRADATIONS:
+        raise ValueError(f'degradation must be one of {DEGRADATIONS}, got {degradation!r}')
+    if quantize is None:
+        quantize = degradation == 'bi'
+    down = (lambda **kw: ops.imresize(gt, 1 / scale, **kw)) if degradation == 'bi' else (lambda **kw: ops.bd_downsample(gt, scale, **kw))
     if not quantize:
-        return ops.imresize(gt, 1 / scale)
-    return ops.frames_u8_to_f32(ops.imresize(gt, 1 / scale, out_dtype=torch.uint8)[None])[0]
+        return down()
+    return ops.frames_u8_to_f32(down(out_dtype=torch.uint8)[None])[0]
+
+
+# ------------------------------------------------------------------------------------------------ BD downsampling (csrc/bd.hip)
+DEGRADATIONS = ('bi', 'bd')
+BD_SCALES = (2, 3, 4)
+BD_KERNEL_SIZE = 13
+
+
+def bd_weights(scale):
+    """The 13 float64 weights g of duf_downsample's separable form: the 1-D kernel scipy.ndimage.gaussian_filter applies per axis at
+    sigma = 0.4 * scale (generate_gaussian_kernel, data_util.py:281-296), truncated at int(4 sigma + 0.5) samples = 3, 5, 6 (7, 11, 13
+    non-zero taps) and normalised; np.outer(g, g) is the reference's 13 x 13 filter exactly.  Written as scipy writes it, so that the
+    float64 values are the same; scipy is not needed."""
+    if scale not in BD_SCALES or isinstance(scale, bool):
+        raise ValueError(f'duf_downsample: scale must be one of {BD_SCALES}, got {scale!r}')
+    sigma = 0.4 * int(scale)
+    radius = int(4.0 * sigma + 0.5)
+    x = np.arange(-radius, radius + 1)
+    phi = np.exp(-0.5 / (sigma * sigma) * x ** 2)
+    phi = phi / phi.sum()
+    g = np.zeros(BD_KERNEL_SIZE)
+    g[BD_KERNEL_SIZE // 2 - radius:BD_KERNEL_SIZE // 2 + radius + 1] = phi
+    return g
+
+
+def bd_shape(h, w, scale):
+    """(h', w') = (ceil(h / scale), ceil(w / scale)) of duf_downsample (pad 6 + 2 scale, stride scale, crop 2 per side).  ValueError for a
+    scale outside {2, 3, 4} and for a frame of fewer than 7 rows or columns (one reflection must cover the kernel's reach of 6; the
+    reference itself needs more than 6 + 2 scale): the check every caller of the kernel goes through before a launch.  Pure Python."""
+    if isinstance(scale, bool) or scale not in BD_SCALES or int(scale) != scale:
+        raise ValueError(f'duf_downsample: scale must be one of {BD_SCALES}, got {scale!r}')
+    h, w, scale = int(h), int(w), int(scale)
+    if min(h, w) < BD_KERNEL_SIZE // 2 + 1:
+        raise ValueError(f'duf_downsample: a {h} x {w} frame has fewer than {BD_KERNEL_SIZE // 2 + 1} rows or columns, the reach of the kernel\'s one reflection')
+    return -(-h // scale), -(-w // scale)
+
+
+def duf_downsample(x, kernel_size=13, scale=4):
+    """duf_downsample (basicsr/data/data_util.py:299-331; the "BD" degradation of the DUF code) on the device: x (t, c, h, w) or
+    (b, t, c, h, w) float32 in [0, 1] on the GPU -> the same with (ceil(h / scale), ceil(w / scale)), float32, not rounded or clamped; also
+    uint8 (n, h, w, 3) -> float32 (n, 3, h', w').  c = 3, scale in {2, 3, 4}, kernel_size 13 (the only size anything uses; the
+    reference's other sizes change where sigma is truncated).  CPU tensors raise NotImplementedError: there is no fallback."""
+    from . import ops
+    if kernel_size != BD_KERNEL_SIZE:
+        raise ValueError(f'duf_downsample: kernel_size must be {BD_KERNEL_SIZE}, got {kernel_size}')
+    if not torch.is_tensor(x):
+        raise NotImplementedError('edvr_amd.data.duf_downsample takes device tensors')
+    if x.dim() == 5 and x.dtype != torch.uint8:
+        bd_shape(x.shape[-2], x.shape[-1], scale)
+        b, t = x.shape[:2]
+        out = ops.bd_downsample(x.reshape(b * t, *x.shape[2:]), scale)
+        return out.view(b, t, *out.shape[1:])
+    return ops.bd_downsample(x, scale)
 
 
 class VideoTestClips:
@@ -387,7 +447,8 @@ class VideoTestClips:
     metrics.validate_clip can batch the windows of a whole clip.  clip(folder) returns the (lq, gt) pair of one folder.
 
     Without an LQ folder: dataroot_lq None and lq_from_gt = {'scale': 4, 'quantize': True} derive the LQ frames from the decoded GT on
-    the device (lq_from_gt above; GT mod-cropped to a multiple of the scale first, as read_img_seq(require_mod_crop=True) does)."""
+    the device (lq_from_gt above; GT mod-cropped to a multiple of the scale first, as read_img_seq(require_mod_crop=True) does);
+    lq_from_gt = {'scale': 4, 'degradation': 'bd'} makes them with duf_downsample instead (not quantised unless 'quantize' says so)."""
 
     def __init__(self, opt, device='cuda'):
         import glob
@@ -399,8 +460,15 @@ class VideoTestClips:
         self.gt_root, self.lq_root = opt['dataroot_gt'], opt['dataroot_lq']
         self.lq_from_gt = dict(opt['lq_from_gt']) if self.lq_root is None and opt.get('lq_from_gt') else None
         if self.lq_from_gt is not None:
-            self.lq_from_gt = {'scale': int(self.lq_from_gt['scale']), 'quantize': bool(self.lq_from_gt.get('quantize', True))}
-            if not 1 <= self.lq_from_gt['scale'] <= 1 / IMRESIZE_SCALE_RANGE[0]:
+            degradation = self.lq_from_gt.get('degradation', 'bi')
+            if degradation not in DEGRADATIONS:
+                raise ValueError(f'lq_from_gt: degradation must be one of {DEGRADATIONS}, got {degradation!r}')
+            self.lq_from_gt = {'scale': int(self.lq_from_gt['scale']), 'quantize': bool(self.lq_from_gt.get('quantize', degradation == 'bi')),
+                               'degradation': degradation}
+            if degradation == 'bd':
+                if self.lq_from_gt['scale'] not in BD_SCALES:
+                    raise ValueError(f"lq_from_gt: scale {self.lq_from_gt['scale']} is not one of {BD_SCALES} (degradation 'bd')")
+            elif not 1 <= self.lq_from_gt['scale'] <= 1 / IMRESIZE_SCALE_RANGE[0]:
                 raise ValueError(f"lq_from_gt: scale {self.lq_from_gt['scale']} is outside 1..8")
             self.lq_root = self.gt_root  # the 'LQ' files of data_info are the GT files the frames are made from
         assert dict(opt['io_backend'])['type'] != 'lmdb', 'No need to use lmdb during validation/test.'
@@ -459,7 +527,7 @@ class VideoTestClips:
         scale, quantize = self.lq_from_gt['scale'], self.lq_from_gt['quantize']
         gt = read_img_seq(paths_gt, self.device, require_mod_crop=True, scale=scale)
         src = gt if list(paths_lq) == list(paths_gt) else read_img_seq(paths_lq, self.device, require_mod_crop=True, scale=scale)
-        return lq_from_gt(src, scale, quantize), gt
+        return lq_from_gt(src, scale, quantize, self.lq_from_gt['degradation']), gt
 
     def __getitem__(self, index):
         folder = self.data_info['folder'][index]
@@ -474,6 +542,27 @@ class VideoTestClips:
             img_gt = gts[0]
         return {'lq': imgs_lq, 'gt': img_gt, 'folder': folder, 'idx': self.data_info['idx'][index],
                 'border': self.data_info['border'][index], 'lq_path': self.data_info['lq_path'][index]}
+
+
+class VideoTestDUFClips(VideoTestClips):
+    """VideoTestDUFDataset (basicsr/data/video_test_dataset.py:231-290): VideoTestClips with the reference's two extra keys.  With
+    opt['use_duf_downsampling'] true the LQ windows are made from the GT frames - mod-cropped to opt['scale'], duf_downsample on the
+    device, not quantised - and dataroot_lq only names the items: data_info['lq_path'] is each GT file's path under dataroot_lq (the
+    folder need not exist; None keeps the GT paths).  With the key false or absent this is VideoTestClips."""
+
+    def __init__(self, opt, device='cuda'):
+        import os.path as osp
+        self.use_duf_downsampling = bool(opt.get('use_duf_downsampling', False))
+        if not self.use_duf_downsampling:
+            super().__init__(opt, device)
+            return
+        if opt.get('scale') not in BD_SCALES:
+            raise ValueError(f"use_duf_downsampling: opt['scale'] must be one of {BD_SCALES}, got {opt.get('scale')!r}")
+        names_root = opt.get('dataroot_lq')
+        super().__init__(dict(opt, dataroot_lq=None, lq_from_gt={'scale': opt['scale'], 'degradation': 'bd', 'quantize': False}), device)
+        self.opt = opt
+        if names_root is not None:
+            self.data_info['lq_path'] = [osp.join(names_root, osp.relpath(p, self.gt_root)) for p in self.data_info['gt_path']]
 
 
 class VideoTestVimeo90KClips:

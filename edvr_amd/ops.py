@@ -1481,3 +1481,44 @@ def imresize(frames, scale, antialiasing=True, out_dtype=torch.float32):
                                                                                  int(bool(antialiasing)), int(u8out), _stream()),
                                             'edvr_imresize_bicubic_f32'), 0, nbytes)
     return out
+
+
+# ------------------------------------------------------------------------------------------------ BD downsampling (csrc/bd.hip)
+def bd_downsample(frames, scale=4, out_dtype=torch.float32):
+    """DUF's "BD" degradation (duf_downsample, basicsr/data/data_util.py:281-331) of a batch of frames in ONE launch: the 13 x 13 Gaussian
+    of sigma 0.4 * scale over the reflected frame, sampled at every scale-th input sample.  frames uint8 (n, H, W, 3) (byte / 255 as
+    frames_u8_to_f32 rounds it) or float32 (n, 3, H, W) with dense images (a slice of a longer video works) -> out_dtype float32
+    (n, 3, H', W'), not clamped, or uint8 (n, H', W', 3) = tensor2img of that float, bit for bit; (H', W') = data.bd_shape(H, W, scale),
+    which also raises the ValueError for a scale outside {2, 3, 4} and for frames of fewer than 7 rows or columns - before anything is
+    launched."""
+    from .data import bd_shape
+    if not frames.is_cuda:
+        raise NotImplementedError('edvr_amd ops run on the GPU only (HIP/gfx950); got a CPU tensor')
+    if out_dtype not in (torch.float32, torch.uint8):
+        raise ValueError(f'out_dtype must be torch.float32 or torch.uint8, got {out_dtype}')
+    u8 = frames.dtype == torch.uint8
+    if u8:
+        if frames.dim() != 4 or frames.shape[-1] != 3:
+            raise ValueError(f'uint8 frames are (n, H, W, 3), got {tuple(frames.shape)}')
+        frames = frames.contiguous()
+        n, H, W, _ = frames.shape
+    else:
+        require_gpu(frames)
+        if frames.dim() != 4 or frames.shape[1] != 3:
+            raise ValueError(f'float32 frames are (n, 3, H, W), got {tuple(frames.shape)}')
+        frames = _as_planes(frames)
+        n, _, H, W = frames.shape
+    if not 0 < n <= 65535:
+        raise ValueError(f'bd_downsample takes 1..65535 frames per call, got {n}')
+    ho, wo = bd_shape(H, W, scale)
+    scale = int(scale)
+    u8out = out_dtype == torch.uint8
+    out = torch.empty((n, ho, wo, 3) if u8out else (n, 3, ho, wo), dtype=out_dtype, device=frames.device)
+    nbytes = 3.0 * n * (H * W * (1 if u8 else 4) + ho * wo * (1 if u8out else 4))  # source + output, each element once
+    if u8:
+        _run('bd_downsample', lambda: _lib.check(_lib.lib().edvr_bd_downsample_u8(_ptr(frames), _ptr(out), n, H, W, ho, wo, scale, int(u8out), _stream()),
+                                                 'edvr_bd_downsample_u8'), 0, nbytes)
+    else:
+        _run('bd_downsample', lambda: _lib.check(_lib.lib().edvr_bd_downsample_f32(_ptr(frames), _ptr(out), n, H, W, _img_stride(frames), ho, wo, scale,
+                                                                                   int(u8out), _stream()), 'edvr_bd_downsample_f32'), 0, nbytes)
+    return out

@@ -535,6 +535,25 @@ int edvr_imresize_bicubic_u8(const uint8_t *src, void *dst, int n, int H, int W,
 int edvr_imresize_bicubic_f32(const float *src, void *dst, int n, int H, int W, int64_t src_img_stride, int ho, int wo, double scale,
                               int antialiasing, int out_kind, edvr_stream_t stream);
 
+/* "BD" downsampling on the device <- duf_downsample / generate_gaussian_kernel (basicsr/data/data_util.py:281-331; the LQ frames of
+ * VideoTestDUFDataset, video_test_dataset.py:231-290): DUF's 13 x 13 Gaussian blur, sigma = 0.4 * scale, sampled at every scale-th
+ * input sample, as ONE launch.  For scale s in {2, 3, 4}:
+ *   out[i, j] = sum_{a, b = 0..12} g[a] g[b] x[R(i s - 6 + a, H), R(j s - 6 + b, W)],  R(p, n) = -p (p < 0), 2 (n - 1) - p (p >= n), p:
+ * the reflection that does not repeat the edge sample (F.pad 'reflect'); taps are centred on input sample i * s.  g is the 1-D kernel of
+ * scipy.ndimage.gaussian_filter at sigma: exp(-d^2 / 2 sigma^2) / sum for |d| <= int(4 sigma + 0.5) (3, 5, 6), 0 beyond - its outer
+ * product is the reference's 2-D filter exactly.  The 13 weights are computed on the host in float64 and passed as kernel arguments;
+ * rows first, then columns, fp32 accumulation: no allocation, no wait.  (ho, wo) = (ceil(H / s), ceil(W / s)), computed by the caller
+ * (the reference pads by 6 + 2 s and crops two outputs per side: the same samples).  EDVR_ERR_ARG for a scale outside {2, 3, 4}, for
+ * min(H, W) < 7 (one reflection must cover the reach of 6; the reference needs min(H, W) > 6 + 2 s), for other (ho, wo), n > 65535.
+ * _u8: src (n, H, W, 3) dense bytes, each divided by 255 exactly as edvr_frames_u8_to_f32 rounds it; _f32: src (n, 3, H, W), dense images
+ * src_img_stride floats apart.  out_u8 == 0: dst (n, 3, ho, wo) dense float32, not clamped; != 0: dst (n, ho, wo, 3) dense bytes =
+ * tensor2img (clamp, x 255, round half to even) of that float - bit for bit, and the _u8 source gives bit for bit what the _f32 source
+ * holding byte / 255 gives.  16-byte loads where the source rows start on 16-byte boundaries (3 W % 16 == 0 bytes / W % 4 == 0 floats,
+ * aligned pointer and stride), 16-byte float and dword byte stores where wo % 4 == 0 and dst is aligned; narrower accesses otherwise. */
+int edvr_bd_downsample_u8(const uint8_t *src, void *dst, int n, int H, int W, int ho, int wo, int scale, int out_u8, edvr_stream_t stream);
+int edvr_bd_downsample_f32(const float *src, void *dst, int n, int H, int W, int64_t src_img_stride, int ho, int wo, int scale, int out_u8,
+                           edvr_stream_t stream);
+
 /* Multi-tensor Adam step <- torch.optim.Adam.step() as the reference builds it (basicsr/models/edvr_model.py:21-53, parameter
  * groups with dcn_lr_mul; stepped in sr_model.py:112).  `chunk_table` is a DEVICE array of n_chunks records of
  * edvr_adam_chunk_bytes() = 64 bytes: { float *p; const float *g; float *m; float *v; int32 n (<= 65536 elements of one tensor);

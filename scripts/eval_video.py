@@ -7,8 +7,10 @@ fusion / reconstruction pass.  `--pad-mode reflect` admits frames of any size, `
     python scripts/eval_video.py --lq-from-gt 4 --bicubic-baseline --gt my_footage --weights EDVR_L_x4_SR_REDS_official.pth
 
 `--lq-from-gt SCALE` needs no LQ folder: the LQ frames are MATLAB's bicubic reduction of the GT frames, made on the device
-(edvr_amd.data.imresize, 8-bit like a stored dataset).  `--bicubic-baseline` scores the bicubic enlargement of the LQ frames beside the
-model (the LQ frames themselves for --hr-in networks); `--json FILE` writes what is printed.
+(edvr_amd.data.imresize, 8-bit like a stored dataset); with `--degradation bd` they are DUF's Gaussian blur and subsampling instead
+(edvr_amd.data.duf_downsample, SCALE 2, 3 or 4, float as the reference's VideoTestDUFDataset feeds them).  `--bicubic-baseline` scores the
+bicubic enlargement of the LQ frames beside the model under either degradation, as the published BI and BD tables do (the LQ frames
+themselves for --hr-in networks); `--json FILE` writes what is printed, and the degradation.
 
 The Vimeo90K-Test list is one window per item - nothing to reuse: use scripts/test_reds.py --vimeo-meta for it.
 """
@@ -49,10 +51,11 @@ def evaluate(args, log=print):
     opt = dict(dataroot_gt=args.gt, dataroot_lq=args.lq, io_backend=dict(type='disk'), num_frame=args.num_frame,
                padding=args.padding, name=args.name, cache_data=True)
     lq_from_gt, baseline = getattr(args, 'lq_from_gt', None), getattr(args, 'bicubic_baseline', False)
+    degradation = getattr(args, 'degradation', None) or 'bi'
     if args.lq is None:
         if not lq_from_gt:
             raise ValueError('either an LQ folder or lq_from_gt is needed')
-        opt['lq_from_gt'] = dict(scale=lq_from_gt, quantize=True)
+        opt['lq_from_gt'] = dict(scale=lq_from_gt, quantize=True) if degradation == 'bi' else dict(scale=lq_from_gt, degradation=degradation)
     ds = VideoTestClips(opt, device=device)
     # frames of any size (--pad-mode / --tile / --tile-overlap): passed on only where given
     any_size = {k: (tuple(v) if k == 'tile' else v) for k in ('pad_mode', 'tile', 'tile_overlap') for v in [getattr(args, k, None)] if v is not None}
@@ -88,7 +91,8 @@ def evaluate(args, log=print):
                 beside(sum(base.values()) / max(len(base), 1)))
         if getattr(args, 'json', None):
             import json
-            record = {'psnr': summary, 'average': sum(summary.values()) / max(len(summary), 1)}
+            record = {'psnr': summary, 'average': sum(summary.values()) / max(len(summary), 1),
+                      'degradation': degradation if args.lq is None else None}  # None: the LQ folder's, whatever made it
             if baseline:
                 record.update(bicubic_psnr=base, bicubic_average=sum(base.values()) / max(len(base), 1))
             with open(args.json, 'w') as f:
@@ -101,6 +105,8 @@ def parse_args(argv=None):
     ap.add_argument('--lq', default=None, help='LQ folder; optional with --lq-from-gt')
     ap.add_argument('--lq-from-gt', type=int, default=None, metavar='SCALE',
                     help='make the LQ frames from the GT frames on the device: MATLAB bicubic reduction by SCALE, 8-bit (GT mod-cropped to SCALE)')
+    ap.add_argument('--degradation', choices=('bi', 'bd'), default='bi',
+                    help="with --lq-from-gt: bi = MATLAB bicubic, 8-bit; bd = DUF's Gaussian blur and subsampling, float (SCALE 2, 3 or 4)")
     ap.add_argument('--bicubic-baseline', action='store_true', help='also report the PSNR of the bicubic enlargement of the LQ frames')
     ap.add_argument('--json', default=None, metavar='FILE', help='write the per-folder and average results there')
     ap.add_argument('--gt', required=True)
@@ -125,6 +131,8 @@ def parse_args(argv=None):
         ap.error('give exactly one of --lq and --lq-from-gt')
     if args.lq_from_gt is not None and not 1 <= args.lq_from_gt <= 8:
         ap.error('--lq-from-gt takes a scale in 1..8')
+    if args.degradation == 'bd' and args.lq_from_gt not in (2, 3, 4):
+        ap.error('--degradation bd needs --lq-from-gt 2, 3 or 4')
     return args
 
 

@@ -1,11 +1,14 @@
 """The LQ copy of a folder of sharp frames, made on the device: MATLAB's antialiased bicubic imresize ("BI x4") - the replacement for
-the reference's scripts/matlab_scripts/generate_bicubic_img.m.
+the reference's scripts/matlab_scripts/generate_bicubic_img.m - or, with --degradation bd, DUF's Gaussian blur and subsampling ("BD",
+the reference's duf_downsample; scales 2, 3, 4).
 
     python scripts/make_lq.py datasets/REDS4/GT datasets/REDS4/sharp_bicubic --scale 4
+    python scripts/make_lq.py datasets/Vid4/GT datasets/Vid4/BDx4 --scale 4 --degradation bd
 
 GT_ROOT/<clip>/<frame>.png -> LQ_ROOT/<clip>/<frame>.png.  Frames are decoded and encoded on host threads through PIL (as
 edvr_amd/data.py decodes), mod-cropped to a multiple of the scale (as the MATLAB script does), resized by 1 / scale in one launch per
-batch of equal-sized frames (edvr_amd.ops.imresize, uint8 in, uint8 out: the rounding tensor2img applies) and written as 8-bit PNG.
+batch of equal-sized frames (edvr_amd.ops.imresize or ops.bd_downsample, uint8 in, uint8 out: the rounding tensor2img applies) and
+written as 8-bit PNG.
 """
 import argparse
 import os
@@ -37,6 +40,12 @@ def resize_u8(frames_u8, scale, antialiasing, device):
     return ops.imresize(torch.from_numpy(frames_u8).to(device), 1 / scale, antialiasing, out_dtype=torch.uint8).cpu().numpy()
 
 
+def bd_u8(frames_u8, scale, device):
+    """(n, H, W, 3) uint8 host array -> (n, H / scale, W / scale, 3) uint8 host array, DUF-downsampled on the device."""
+    from edvr_amd import ops
+    return ops.bd_downsample(torch.from_numpy(frames_u8).to(device), scale, out_dtype=torch.uint8).cpu().numpy()
+
+
 def load(path, scale):
     from edvr_amd.data import decode_image
     with open(path, 'rb') as f:
@@ -49,9 +58,13 @@ def save(path, rgb_u8):
     Image.fromarray(rgb_u8).save(os.path.splitext(path)[0] + '.png', format='PNG')
 
 
-def make_lq(gt_root, lq_root, scale=4, antialiasing=True, batch=16, num_threads=8, device='cuda', log=print):
+def make_lq(gt_root, lq_root, scale=4, antialiasing=True, batch=16, num_threads=8, device='cuda', log=print, degradation='bi'):
     """Returns the number of frames written."""
-    from edvr_amd.data import imresize_shape
+    from edvr_amd.data import bd_shape, imresize_shape
+    if degradation not in ('bi', 'bd'):
+        raise ValueError(f"degradation must be 'bi' or 'bd', got {degradation!r}")
+    if degradation == 'bd':
+        bd_shape(7, 7, scale)  # a scale DUF's kernel does not have: ValueError before any file is read
     clips = walk(gt_root)
     if not clips:
         raise FileNotFoundError(f'no <clip>/<frame> images under {gt_root}')
@@ -64,8 +77,12 @@ def make_lq(gt_root, lq_root, scale=4, antialiasing=True, batch=16, num_threads=
                 imgs = list(pool.map(lambda n: load(os.path.join(gt_root, clip, n), scale), names))
                 for shape in sorted({im.shape for im in imgs}):  # one launch per frame size (a clip normally has one)
                     sel = [i for i, im in enumerate(imgs) if im.shape == shape]
-                    imresize_shape(shape[0], shape[1], 1 / scale, antialiasing)  # a frame too small for the kernel: ValueError naming it
-                    out = resize_u8(np.stack([imgs[i] for i in sel]), scale, antialiasing, device)
+                    if degradation == 'bd':
+                        bd_shape(shape[0], shape[1], scale)  # a frame too small for the kernel: ValueError naming it
+                        out = bd_u8(np.stack([imgs[i] for i in sel]), scale, device)
+                    else:
+                        imresize_shape(shape[0], shape[1], 1 / scale, antialiasing)  # likewise
+                        out = resize_u8(np.stack([imgs[i] for i in sel]), scale, antialiasing, device)
                     list(pool.map(lambda io: save(os.path.join(lq_root, clip, names[io[0]]), io[1]), zip(sel, out)))
                 written += len(names)
             log(f'{clip}: {len(frames)} frame(s)')
@@ -77,18 +94,24 @@ def parse_args(argv=None):
     ap.add_argument('gt_root')
     ap.add_argument('lq_root')
     ap.add_argument('--scale', type=int, default=4)
-    ap.add_argument('--no-antialias', action='store_true', help="imresize(..., 'Antialiasing', false)")
+    ap.add_argument('--degradation', choices=('bi', 'bd'), default='bi',
+                    help="bi: MATLAB's antialiased bicubic imresize; bd: DUF's 13 x 13 Gaussian blur and subsampling (scale 2, 3 or 4)")
+    ap.add_argument('--no-antialias', action='store_true', help="imresize(..., 'Antialiasing', false) (bi only)")
     ap.add_argument('--batch', type=int, default=16, help='frames per launch')
     ap.add_argument('--threads', type=int, default=8, help='host threads decoding and encoding')
     args = ap.parse_args(argv)
     if not 1 <= args.scale <= 8:
         ap.error('--scale must be an integer in 1..8')
+    if args.degradation == 'bd' and args.scale not in (2, 3, 4):
+        ap.error('--degradation bd takes --scale 2, 3 or 4')
+    if args.degradation == 'bd' and args.no_antialias:
+        ap.error('--no-antialias belongs to --degradation bi')
     return args
 
 
 def main():
     args = parse_args()
-    n = make_lq(args.gt_root, args.lq_root, args.scale, not args.no_antialias, args.batch, args.threads)
+    n = make_lq(args.gt_root, args.lq_root, args.scale, not args.no_antialias, args.batch, args.threads, degradation=args.degradation)
     print(f'{n} frame(s) -> {args.lq_root}')
 
 
