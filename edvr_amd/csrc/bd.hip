@@ -29,6 +29,7 @@
 #include <cmath>
 
 #include "common.h"
+#include "lq_window.h"
 #include "pixel.h"
 
 namespace edvr {
@@ -43,6 +44,9 @@ struct BdArgs {
   int H, W, ho, wo;
   int src_vec, dst_vec, out_u8;
   float g[13];  // the 1-D kernel, g[6] its centre; zero beyond the truncation radius
+  // the windowed form (WIN; lq_window.h): the source is n windows of wh rows of `pitch` bytes, H and W come from the table, ho = wo = p
+  const int32_t *table;
+  int wh, ww, pitch;
 };
 
 template <int S>
@@ -66,7 +70,9 @@ __device__ __forceinline__ int refl_index(int p, int n) {
   return min(max(p, 0), n - 1);
 }
 
-template <int S, bool U8IN>
+// WIN: output (oy, ox) of image `img` is sample (top + oy, left + ox) of the downsampled FRAME, and the source is a window of that frame
+// (U8IN, byte output); every index is formed in frame coordinates and passes through view_index last
+template <int S, bool U8IN, bool WIN>
 __global__ __launch_bounds__(256) void bd_downsample_kernel(const BdArgs a) {
   using C = BdCfg<S>;
   constexpr int R = C::R, NT = C::NT, TOH = C::TOH, TOW = C::TOW, MS = C::MS, OS = C::OS, G0 = 6 - R;
@@ -77,26 +83,40 @@ __global__ __launch_bounds__(256) void bd_downsample_kernel(const BdArgs a) {
   const int oy0 = by * TOH, ox0 = bx * TOW;
   const int nvy = min(TOH, a.ho - oy0), nvx = min(TOW, a.wo - ox0);
   const int tid = threadIdx.x;
-  const int H = a.H, W = a.W;
+  int H = a.H, W = a.W;
+  int ay0 = 0, ax0 = 0;                  // absolute index of output (0, 0)
+  int vy0 = 0, vx0 = 0, vh = H, vw = W;  // the source view: rows [vy0, vy0 + vh) x columns [vx0, vx0 + vw) of the frame
+  if (WIN) {
+    const int32_t *rec = a.table + (int64_t)LQW_REC * img;
+    vy0 = window_origin(rec[LQW_Y0]), vx0 = window_origin(rec[LQW_X0]), vh = a.wh, vw = a.ww;
+    H = rec[LQW_H], W = rec[LQW_W], ay0 = rec[LQW_TOP], ax0 = rec[LQW_LEFT];
+  }
+  const int64_t pitch = WIN ? (int64_t)a.pitch : (int64_t)W * 3;  // bytes of a source row (U8IN)
   // the tile's column window [p0, p1] in unreflected coordinates; [lo, hi] is the part of it inside the frame.  Every reflection of a
   // column of the window falls into [lo, hi]: -p <= R <= p1 on the left, p0 <= W - 1 - R <= 2 (W - 1) - p on the right (W >= 7 > R).
-  const int p0 = ox0 * S - R, p1 = p0 + (nvx - 1) * S + NT - 1;
-  const int lo = max(p0, 0), hi = min(p1, W - 1);
+  const int p0 = (ax0 + ox0) * S - R, p1 = p0 + (nvx - 1) * S + NT - 1;
+  int lo = max(p0, 0), hi = min(p1, W - 1);
+  if (WIN) {  // a window holds every column of non-zero weight; whatever the table says, [lo, hi] stays inside [p0, p1]
+    lo = min(max(lo, vx0), p1), hi = max(min(hi, vx0 + vw - 1), lo);
+  }
   const int npair = (nvy + 1) >> 1;
 
   // ---- 1. vertical pass: source -> mid, two output rows per thread
   if (U8IN) {
-    const uint8_t *src = static_cast<const uint8_t *>(a.src) + (int64_t)img * H * W * 3;
-    const int g_lo = (3 * lo) >> 4, ng = ((3 * hi + 2) >> 4) - g_lo + 1;  // 16-byte groups of a source row
+    const uint8_t *src = static_cast<const uint8_t *>(a.src) + (int64_t)img * vh * pitch;
+    const int g_lo = (3 * (lo - vx0)) >> 4, ng = ((3 * (hi - vx0) + 2) >> 4) - g_lo + 1;  // 16-byte groups of a source row
+    const int g_max = WIN ? (a.pitch >> 4) - 1 : 0;
     for (int item = tid; item < npair * ng; item += 256) {
-      const int pr = item / ng, g = g_lo + item - pr * ng;
-      const int oyl = 2 * pr, y0 = (oy0 + oyl) * S - R;
+      const int pr = item / ng;
+      int g = g_lo + item - pr * ng;
+      if (WIN) g = min(max(g, 0), g_max);
+      const int oyl = 2 * pr, y0 = (ay0 + oy0 + oyl) * S - R;
       float acc0[16], acc1[16];
 #pragma unroll
       for (int k = 0; k < 16; ++k) acc0[k] = 0.f, acc1[k] = 0.f;
 #pragma unroll
       for (int j = 0; j < NT + S; ++j) {
-        const uint8_t *row = src + (int64_t)refl_index(y0 + j, H) * W * 3;
+        const uint8_t *row = src + view_index<WIN>(refl_index(y0 + j, H), vy0, vh) * pitch;
         uint32_t q[4];
         if (a.src_vec) {
           const u32x4 v = *reinterpret_cast<const u32x4 *>(row + 16 * g);
@@ -120,7 +140,7 @@ __global__ __launch_bounds__(256) void bd_downsample_kernel(const BdArgs a) {
       const bool second = oyl + 1 < nvy;
 #pragma unroll
       for (int k = 0; k < 16; ++k) {
-        const int col = px0 + (r0 + k) / 3, c = (r0 + k) % 3;
+        const int col = vx0 + px0 + (r0 + k) / 3, c = (r0 + k) % 3;
         if (col >= lo && col <= hi) {
           float *m = mid + (c * TOH + oyl) * MS + C::at(col - p0);
           m[0] = acc0[k];
@@ -242,8 +262,18 @@ static inline bool bd_aligned(const void *p, uintptr_t a) { return reinterpret_c
 template <int S>
 static void bd_dispatch(bool u8in, const BdArgs &a, int n, hipStream_t stream) {
   const dim3 grid(cdiv(a.wo, BdCfg<S>::TOW), cdiv(a.ho, BdCfg<S>::TOH), n);
-  if (u8in) hipLaunchKernelGGL((bd_downsample_kernel<S, true>), grid, dim3(256), 0, stream, a);
-  else hipLaunchKernelGGL((bd_downsample_kernel<S, false>), grid, dim3(256), 0, stream, a);
+  if (a.table) hipLaunchKernelGGL((bd_downsample_kernel<S, true, true>), grid, dim3(256), 0, stream, a);
+  else if (u8in) hipLaunchKernelGGL((bd_downsample_kernel<S, true, false>), grid, dim3(256), 0, stream, a);
+  else hipLaunchKernelGGL((bd_downsample_kernel<S, false, false>), grid, dim3(256), 0, stream, a);
+}
+
+// scipy.ndimage's 1-D Gaussian at sigma = 0.4 scale, truncated at int(4 sigma + 0.5), normalised; float64 here, float32 in the kernel
+static void bd_kernel_weights(int scale, float *g) {
+  const double sigma = 0.4 * scale;
+  const int r = (int)(4.0 * sigma + 0.5);
+  double w[13], sum = 0.0;
+  for (int d = -6; d <= 6; ++d) sum += w[d + 6] = std::abs(d) <= r ? std::exp(-0.5 / (sigma * sigma) * d * d) : 0.0;
+  for (int t = 0; t < 13; ++t) g[t] = (float)(w[t] / sum);
 }
 
 static int bd_launch(bool u8in, const void *src, void *dst, int n, int H, int W, int64_t src_img_stride, int ho, int wo, int scale, int out_u8,
@@ -256,12 +286,8 @@ static int bd_launch(bool u8in, const void *src, void *dst, int n, int H, int W,
   EDVR_REQUIRE(cdiv(ho, 8) <= 65535 && (int64_t)H * W <= INT32_MAX / 4, "bd_downsample: a %d x %d frame is too large", H, W);
   BdArgs a;
   a.src = src, a.dst = dst, a.src_img_stride = src_img_stride, a.H = H, a.W = W, a.ho = ho, a.wo = wo, a.out_u8 = out_u8 != 0;
-  // scipy.ndimage's 1-D Gaussian at sigma = 0.4 scale, truncated at int(4 sigma + 0.5), normalised; float64 here, float32 in the kernel
-  const double sigma = 0.4 * scale;
-  const int r = (int)(4.0 * sigma + 0.5);
-  double w[13], sum = 0.0;
-  for (int d = -6; d <= 6; ++d) sum += w[d + 6] = std::abs(d) <= r ? std::exp(-0.5 / (sigma * sigma) * d * d) : 0.0;
-  for (int t = 0; t < 13; ++t) a.g[t] = (float)(w[t] / sum);
+  bd_kernel_weights(scale, a.g);
+  a.table = nullptr, a.wh = a.ww = a.pitch = 0;
   a.src_vec = u8in ? ((3 * (int64_t)W) % 16 == 0 && bd_aligned(src, 16)) : (W % 4 == 0 && src_img_stride % 4 == 0 && bd_aligned(src, 16));
   a.dst_vec = wo % 4 == 0 && bd_aligned(dst, a.out_u8 ? 4 : 16);
   if (scale == 2) bd_dispatch<2>(u8in, a, n, as_stream(stream));
@@ -270,7 +296,30 @@ static int bd_launch(bool u8in, const void *src, void *dst, int n, int H, int W,
   return check_launch("bd_downsample_kernel");
 }
 
+// n crops of p x p LQ samples from n windows of their GT frames (lq_window.h): the same kernel, the same tile, another view of the source
+static int bd_windows_launch(const uint8_t *src, const int32_t *table, const int32_t *table_host, uint8_t *dst, int n, int p, int wh, int ww,
+                             int pitch, int scale, edvr_stream_t stream) {
+  EDVR_REQUIRE(src && table && dst, "bd_downsample_windows: bad arguments");
+  const char *why = lqw_check(LQW_BD, scale, n, p, wh, ww, pitch, src, table_host);
+  EDVR_REQUIRE(!why, "bd_downsample_windows: %s (n %d, crop %d, window %d x %d, pitch %d, scale %d)", why, n, p, wh, ww, pitch, scale);
+  BdArgs a;
+  a.src = src, a.dst = dst, a.src_img_stride = 0, a.H = a.W = 0, a.ho = a.wo = p, a.out_u8 = 1;
+  bd_kernel_weights(scale, a.g);
+  a.src_vec = 1;  // lqw_check: every window row starts on a 16-byte boundary and the pitch covers its last group
+  a.dst_vec = p % 4 == 0 && bd_aligned(dst, 4);
+  a.table = table, a.wh = wh, a.ww = ww, a.pitch = pitch;
+  if (scale == 2) bd_dispatch<2>(true, a, n, as_stream(stream));
+  else if (scale == 3) bd_dispatch<3>(true, a, n, as_stream(stream));
+  else bd_dispatch<4>(true, a, n, as_stream(stream));
+  return check_launch("bd_downsample_kernel (windows)");
+}
+
 }  // namespace edvr
+
+extern "C" int edvr_bd_downsample_u8_windows(const uint8_t *src, const int32_t *table, const int32_t *table_host, uint8_t *dst, int n, int p,
+                                             int wh, int ww, int pitch, int scale, edvr_stream_t stream) {
+  return edvr::bd_windows_launch(src, table, table_host, dst, n, p, wh, ww, pitch, scale, stream);
+}
 
 extern "C" int edvr_bd_downsample_u8(const uint8_t *src, void *dst, int n, int H, int W, int ho, int wo, int scale, int out_u8,
                                      edvr_stream_t stream) {

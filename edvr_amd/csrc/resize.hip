@@ -22,6 +22,7 @@
 #include <cmath>
 
 #include "common.h"
+#include "lq_window.h"
 #include "pixel.h"
 
 namespace edvr {
@@ -40,6 +41,9 @@ struct ResizeArgs {
   int ms;        // columns of one row of the vertical pass's result in LDS (>= the widest column window of a tile)
   int aa_down;   // scale < 1 with antialiasing: the stretched kernel
   int src_vec, dst_vec, out_u8;
+  // the windowed form (WIN; lq_window.h): the source is n windows of wh rows of `pitch` bytes, H and W come from the table, ho = wo = p
+  const int32_t *table;
+  int wh, ww, pitch;
 };
 
 __device__ __forceinline__ double keys_cubic(double x) {
@@ -71,7 +75,9 @@ __device__ int axis_weights(int x1, const ResizeArgs &a, float *w, int stride) {
   return (int)left - 1;
 }
 
-template <bool U8IN>
+// WIN: output (oy, ox) of image `img` is sample (top + oy, left + ox) of the resized FRAME, and the source is a window of that frame
+// (U8IN, byte output); every index is formed in frame coordinates and passes through view_index last
+template <bool U8IN, bool WIN>
 __global__ __launch_bounds__(256) void imresize_bicubic_kernel(const ResizeArgs a) {
   extern __shared__ float smem[];
   const int toh = a.toh, tow = a.tow, taps = a.taps, ms = a.ms, os = tow + 1;
@@ -86,11 +92,19 @@ __global__ __launch_bounds__(256) void imresize_bicubic_kernel(const ResizeArgs 
   const int oy0 = by * toh, ox0 = bx * tow;
   const int nvy = min(toh, a.ho - oy0), nvx = min(tow, a.wo - ox0);
   const int tid = threadIdx.x;
-  const int H = a.H, W = a.W;
+  int H = a.H, W = a.W;
+  int ay0 = 0, ax0 = 0;                // absolute index of output (0, 0)
+  int vy0 = 0, vx0 = 0, vh = H, vw = W;  // the source view: rows [vy0, vy0 + vh) x columns [vx0, vx0 + vw) of the frame
+  if (WIN) {
+    const int32_t *rec = a.table + (int64_t)LQW_REC * img;
+    vy0 = window_origin(rec[LQW_Y0]), vx0 = window_origin(rec[LQW_X0]), vh = a.wh, vw = a.ww;
+    H = rec[LQW_H], W = rec[LQW_W], ay0 = rec[LQW_TOP], ax0 = rec[LQW_LEFT];
+  }
+  const int64_t pitch = WIN ? (int64_t)a.pitch : (int64_t)W * 3;  // bytes of a source row (U8IN)
 
   // ---- 0. weights (waves 0 and 1..3 take an axis each)
-  if (tid < toh) ly[tid] = axis_weights(oy0 + tid + 1, a, wy + tid * taps, 1);
-  if (tid >= 64 && tid - 64 < tow) lx[tid - 64] = axis_weights(ox0 + (tid - 64) + 1, a, wx + (tid - 64), tow);
+  if (tid < toh) ly[tid] = axis_weights(ay0 + oy0 + tid + 1, a, wy + tid * taps, 1);
+  if (tid >= 64 && tid - 64 < tow) lx[tid - 64] = axis_weights(ax0 + ox0 + (tid - 64) + 1, a, wx + (tid - 64), tow);
   __syncthreads();
 
   // the tile's column window [lo, lo + ncols) of the source: what its taps reach, reflections included
@@ -98,12 +112,14 @@ __global__ __launch_bounds__(256) void imresize_bicubic_kernel(const ResizeArgs 
   int lo = max(raw_lo, 0), hi = min(raw_hi, W - 1);
   if (raw_lo < 0) hi = max(hi, min(-raw_lo - 1, W - 1));
   if (raw_hi > W - 1) lo = min(lo, max(2 * W - 1 - raw_hi, 0));
+  if (WIN) lo = min(max(lo, vx0), vx0 + vw - 1), hi = min(max(hi, lo), vx0 + vw - 1);  // taps of weight zero may leave the window
   const int ncols = min(hi - lo + 1, ms);
+  const int llo = lo - vx0;  // first column of the tile's window inside the view
 
   // ---- 1. vertical pass: source -> mid
   if (U8IN) {
-    const uint8_t *src = static_cast<const uint8_t *>(a.src) + (int64_t)img * H * W * 3;
-    const int g_lo = (3 * lo) >> 4, ng = ((3 * (lo + ncols) - 1) >> 4) - g_lo + 1;  // 16-byte groups of a source row
+    const uint8_t *src = static_cast<const uint8_t *>(a.src) + (int64_t)img * vh * pitch;
+    const int g_lo = (3 * llo) >> 4, ng = ((3 * (llo + ncols) - 1) >> 4) - g_lo + 1;  // 16-byte groups of a source row
     for (int item = tid; item < nvy * ng; item += 256) {
       const int oyl = item / ng, g = g_lo + item - oyl * ng;
       const int first = ly[oyl];
@@ -111,7 +127,7 @@ __global__ __launch_bounds__(256) void imresize_bicubic_kernel(const ResizeArgs 
 #pragma unroll
       for (int k = 0; k < 16; ++k) acc[k] = 0.f;
       for (int t = 0; t < taps; ++t) {
-        const uint8_t *row = src + (int64_t)sym_index(first + t, H) * W * 3;
+        const uint8_t *row = src + view_index<WIN>(sym_index(first + t, H), vy0, vh) * pitch;
         const float w = wy[oyl * taps + t];
         uint32_t q[4];
         if (a.src_vec) {
@@ -131,7 +147,7 @@ __global__ __launch_bounds__(256) void imresize_bicubic_kernel(const ResizeArgs 
       const int p0 = (16 * g) / 3, r0 = 16 * g - 3 * p0;
 #pragma unroll
       for (int k = 0; k < 16; ++k) {
-        const int rel = p0 + (r0 + k) / 3 - lo, c = (r0 + k) % 3;
+        const int rel = p0 + (r0 + k) / 3 - llo, c = (r0 + k) % 3;
         if (rel >= 0 && rel < ncols) mid[(c * toh + oyl) * ms + rel] = acc[k];
       }
     }
@@ -235,6 +251,20 @@ static bool resize_axis_fits(int in, int out, double scale, bool aa_down) {
   return 1 - first <= in && last - in <= in;
 }
 
+// tile: an enlargement writes 16 x 64 outputs from a few source rows; a reduction keeps 8 output rows (8 / scale + taps source rows)
+// and as many columns as 64 KB of LDS hold.  Sets toh, tow, taps, ms; returns the bytes of LDS.
+static size_t resize_tile(ResizeArgs &a, double scale, bool aa_down) {
+  a.taps = (int)std::ceil(aa_down ? 4.0 / scale : 4.0) + 2;
+  a.toh = scale >= 1.0 ? 16 : 8;
+  size_t lds = 0;
+  for (a.tow = 64; a.tow >= 16; a.tow >>= 1) {
+    a.ms = ((int)std::ceil((a.tow - 1) / scale) + a.taps + 2) | 1;  // first taps of the tile's columns spread over <= ceil((tow - 1) / scale) + 1
+    lds = sizeof(float) * ((size_t)3 * a.toh * a.ms + 3 * a.toh * (a.tow + 1) + (size_t)(a.toh + a.tow) * a.taps + a.toh + a.tow);
+    if (lds <= 64 * 1024) break;
+  }
+  return lds;
+}
+
 static int resize_launch(bool u8in, const void *src, void *dst, int n, int H, int W, int64_t src_img_stride, int ho, int wo, double scale,
                          int antialiasing, int out_kind, edvr_stream_t stream) {
   EDVR_REQUIRE(src && dst && n > 0 && n <= 65535 && H > 0 && W > 0 && ho > 0 && wo > 0 &&
@@ -249,26 +279,41 @@ static int resize_launch(bool u8in, const void *src, void *dst, int n, int H, in
   ResizeArgs a;
   a.src = src, a.dst = dst, a.src_img_stride = src_img_stride, a.scale = scale, a.H = H, a.W = W, a.ho = ho, a.wo = wo;
   a.aa_down = aa_down, a.out_u8 = out_kind == EDVR_RESIZE_OUT_U8;
-  a.taps = (int)std::ceil(aa_down ? 4.0 / scale : 4.0) + 2;
-  // tile: an enlargement writes 16 x 64 outputs from a few source rows; a reduction keeps 8 output rows (8 / scale + taps source rows)
-  // and as many columns as 64 KB of LDS hold
-  a.toh = scale >= 1.0 ? 16 : 8;
-  size_t lds = 0;
-  for (a.tow = 64; a.tow >= 16; a.tow >>= 1) {
-    a.ms = ((int)std::ceil((a.tow - 1) / scale) + a.taps + 2) | 1;  // first taps of the tile's columns spread over <= ceil((tow - 1) / scale) + 1
-    lds = sizeof(float) * ((size_t)3 * a.toh * a.ms + 3 * a.toh * (a.tow + 1) + (size_t)(a.toh + a.tow) * a.taps + a.toh + a.tow);
-    if (lds <= 64 * 1024) break;
-  }
+  const size_t lds = resize_tile(a, scale, aa_down);
   EDVR_REQUIRE(lds <= 64 * 1024 && cdiv(ho, a.toh) <= 65535, "imresize_bicubic: no tile for scale %g / %d output rows", scale, ho);
   a.src_vec = u8in ? ((3 * (int64_t)W) % 16 == 0 && resize_aligned(src, 16)) : (W % 4 == 0 && src_img_stride % 4 == 0 && resize_aligned(src, 16));
   a.dst_vec = wo % 4 == 0 && resize_aligned(dst, a.out_u8 ? 4 : 16);
   const dim3 grid(cdiv(wo, a.tow), cdiv(ho, a.toh), n);
-  if (u8in) hipLaunchKernelGGL(imresize_bicubic_kernel<true>, grid, dim3(256), lds, as_stream(stream), a);
-  else hipLaunchKernelGGL(imresize_bicubic_kernel<false>, grid, dim3(256), lds, as_stream(stream), a);
+  a.table = nullptr, a.wh = a.ww = a.pitch = 0;
+  if (u8in) hipLaunchKernelGGL((imresize_bicubic_kernel<true, false>), grid, dim3(256), lds, as_stream(stream), a);
+  else hipLaunchKernelGGL((imresize_bicubic_kernel<false, false>), grid, dim3(256), lds, as_stream(stream), a);
   return check_launch("imresize_bicubic_kernel");
 }
 
+// n crops of p x p LQ samples from n windows of their GT frames (lq_window.h): the same kernel, the same tile, another view of the source
+static int resize_windows_launch(const uint8_t *src, const int32_t *table, const int32_t *table_host, uint8_t *dst, int n, int p, int wh, int ww,
+                                 int pitch, int scale, edvr_stream_t stream) {
+  EDVR_REQUIRE(src && table && dst, "imresize_bicubic_windows: bad arguments");
+  const char *why = lqw_check(LQW_BI, scale, n, p, wh, ww, pitch, src, table_host);
+  EDVR_REQUIRE(!why, "imresize_bicubic_windows: %s (n %d, crop %d, window %d x %d, pitch %d, scale %d)", why, n, p, wh, ww, pitch, scale);
+  ResizeArgs a;
+  a.src = src, a.dst = dst, a.src_img_stride = 0, a.scale = 1.0 / scale, a.H = a.W = 0, a.ho = a.wo = p;
+  a.aa_down = 1, a.out_u8 = 1;
+  const size_t lds = resize_tile(a, a.scale, true);
+  EDVR_REQUIRE(lds <= 64 * 1024, "imresize_bicubic_windows: no tile for scale %d", scale);
+  a.src_vec = 1;  // lqw_check: every window row starts on a 16-byte boundary and the pitch covers its last group
+  a.dst_vec = p % 4 == 0 && resize_aligned(dst, 4);
+  a.table = table, a.wh = wh, a.ww = ww, a.pitch = pitch;
+  hipLaunchKernelGGL((imresize_bicubic_kernel<true, true>), dim3(cdiv(p, a.tow), cdiv(p, a.toh), n), dim3(256), lds, as_stream(stream), a);
+  return check_launch("imresize_bicubic_kernel (windows)");
+}
+
 }  // namespace edvr
+
+extern "C" int edvr_imresize_bicubic_u8_windows(const uint8_t *src, const int32_t *table, const int32_t *table_host, uint8_t *dst, int n, int p,
+                                                int wh, int ww, int pitch, int scale, edvr_stream_t stream) {
+  return edvr::resize_windows_launch(src, table, table_host, dst, n, p, wh, ww, pitch, scale, stream);
+}
 
 extern "C" int edvr_imresize_bicubic_u8(const uint8_t *src, void *dst, int n, int H, int W, int ho, int wo, double scale, int antialiasing,
                                         int out_kind, edvr_stream_t stream) {

@@ -110,6 +110,22 @@ class ClipPlan:
         return f'ClipPlan({self.key}: frames {self.frames} of {self.clip}, crop ({self.top}, {self.left}), aug {self.flags})'
 
 
+def _make_client(opt, client, with_lq):
+    """The storage of a training option block: `client` if given (any object with get(kind, clip, frame) -> bytes and
+    size(kind, clip, frame) -> (h, w)), else the backend opt['io_backend'] names over the GT root and - with an LQ tree - the LQ root."""
+    if client is not None:
+        return client
+    roots = {'gt': opt['dataroot_gt']}
+    if with_lq:
+        roots['lq'] = opt['dataroot_lq']
+    backend = dict(opt['io_backend'])['type']
+    if backend == 'lmdb':
+        return LmdbClient(roots)
+    if backend == 'disk':
+        return DiskClient(roots)
+    raise ValueError(f'io_backend {backend} is not supported (disk, lmdb)')
+
+
 class REDSClipPlanner:
     """The decisions of REDSDataset.__getitem__ (reds_dataset.py:106-234), separated from the pixels.  `opt` has the reference's
     keys (dataroot_gt, dataroot_lq, meta_info_file, val_partition, io_backend, num_frame, gt_size, interval_list, random_reverse,
@@ -127,24 +143,25 @@ class REDSClipPlanner:
         self.lq_size = self.gt_size // self.scale
         self.keys = reds_keys(opt['meta_info_file'], opt['val_partition'])
         self.interval_list, self.random_reverse = opt['interval_list'], opt['random_reverse']
-        roots = {'lq': opt['dataroot_lq'], 'gt': opt['dataroot_gt']}
-        backend = dict(opt['io_backend'])['type']
-        if client is not None:  # any object with get(kind, clip, frame) -> bytes and size(kind, clip, frame) -> (h, w)
-            self.client = client
-        elif backend == 'lmdb':
-            self.client = LmdbClient(roots)
-        elif backend == 'disk':
-            self.client = DiskClient(roots)
-        else:
-            raise ValueError(f'io_backend {backend} is not supported (disk, lmdb)')
+        self.lq_from_gt = training_lq_from_gt(opt)  # None: an LQ tree
+        self.client = _make_client(opt, client, self.lq_from_gt is None)
         self._shape = {}  # clip -> ((h_lq, w_lq), (h_gt, w_gt)): all frames of a REDS clip have one size
+        # the one place the two sources of LQ part: where the sizes come from and what load() stages
+        if self.lq_from_gt is None:
+            self.windows = None
+            self._sizes = lambda clip, frame: (self.client.size('lq', clip, frame), self.client.size('gt', clip, frame))
+            self.load = self._load_lq_tree
+        else:
+            self.windows = _WindowsFromGT(self.client, self.lq_size, self.gt_size, *self.lq_from_gt)
+            self._sizes = self.windows.sizes
+            self.load = self._load_gt_windows
 
     def __len__(self):
         return len(self.keys)
 
     def clip_shapes(self, clip, frame):
         if clip not in self._shape:
-            self._shape[clip] = (self.client.size('lq', clip, frame), self.client.size('gt', clip, frame))
+            self._shape[clip] = self._sizes(clip, frame)
         return self._shape[clip]
 
     def plan(self, index, rng=random):
@@ -175,8 +192,13 @@ class REDSClipPlanner:
             flags |= AUG_ROT90
         return ClipPlan(key, clip, center, frames, top, left, flags)
 
-    def load(self, plan, lq_out=None, gt_out=None):
-        """Decode the frames of `plan` and crop bytes: lq (t, p, p, 3), gt (P, P, 3) uint8 RGB, written into lq_out / gt_out
+    def _load_gt_windows(self, plan, lq_out=None, gt_out=None):
+        """load() without an LQ tree: lq is the pair (windows (t, e, pitch) uint8, table (t, 8) int32) of the decoded GT frames for
+        ops.lq_crops_from_windows (e = lq_window_extent, pitch = lq_window_pitch(e)), gt as below."""
+        return self.windows.load(plan, [f'{f:08d}' for f in plan.frames], f'{plan.center:08d}', lq_out, gt_out)
+
+    def _load_lq_tree(self, plan, lq_out=None, gt_out=None):
+        """load(): decode the frames of `plan` and crop bytes: lq (t, p, p, 3), gt (P, P, 3) uint8 RGB, written into lq_out / gt_out
         (views of pinned staging) when given."""
         p, P, s = self.lq_size, self.gt_size, self.scale
         if lq_out is None:
@@ -206,16 +228,17 @@ class Vimeo90KClipPlanner:
             self.keys = [line.split(' ')[0] for line in fin]
         self.neighbor_list = [i + (9 - self.num_frame) // 2 for i in range(self.num_frame)]
         self.random_reverse = opt['random_reverse']
-        roots = {'lq': opt['dataroot_lq'], 'gt': opt['dataroot_gt']}
-        backend = dict(opt['io_backend'])['type']
-        if client is not None:
-            self.client = client
-        elif backend == 'lmdb':
-            self.client = LmdbClient(roots)
-        elif backend == 'disk':
-            self.client = DiskClient(roots)
+        self.lq_from_gt = training_lq_from_gt(opt)  # None: an LQ tree
+        self.client = _make_client(opt, client, self.lq_from_gt is None)
+        # the one place the two sources of LQ part: where the sizes come from and what load() stages
+        if self.lq_from_gt is None:
+            self.windows = None
+            self._sizes = lambda key, frame: (self.client.size('lq', key, frame), self.client.size('gt', key, 'im4'))
+            self.load = self._load_lq_tree
         else:
-            raise ValueError(f'io_backend {backend} is not supported (disk, lmdb)')
+            self.windows = _WindowsFromGT(self.client, self.lq_size, self.gt_size, *self.lq_from_gt)
+            self._sizes = lambda key, frame: self.windows.sizes(key, 'im4')
+            self.load = self._load_gt_windows
 
     def __len__(self):
         return len(self.keys)
@@ -230,8 +253,7 @@ class Vimeo90KClipPlanner:
             self.neighbor_list.reverse()
         key = self.keys[index]
         frames = list(self.neighbor_list)
-        h_lq, w_lq = self.client.size('lq', key, f'im{frames[0]}')
-        h_gt, w_gt = self.client.size('gt', key, 'im4')
+        (h_lq, w_lq), (h_gt, w_gt) = self._sizes(key, f'im{frames[0]}')
         if h_gt != h_lq * self.scale or w_gt != w_lq * self.scale:
             raise ValueError(f'Scale mismatches. GT ({h_gt}, {w_gt}) is not {self.scale}x multiplication of LQ ({h_lq}, {w_lq}).')
         if h_lq < self.lq_size or w_lq < self.lq_size:
@@ -247,7 +269,10 @@ class Vimeo90KClipPlanner:
             flags |= AUG_ROT90
         return ClipPlan(key, key, 4, frames, top, left, flags)
 
-    def load(self, plan, lq_out=None, gt_out=None):
+    def _load_gt_windows(self, plan, lq_out=None, gt_out=None):
+        return self.windows.load(plan, [f'im{f}' for f in plan.frames], 'im4', lq_out, gt_out)
+
+    def _load_lq_tree(self, plan, lq_out=None, gt_out=None):
         p, P, s = self.lq_size, self.gt_size, self.scale
         if lq_out is None:
             lq_out = np.empty((self.num_frame, p, p, 3), np.uint8)
@@ -437,6 +462,159 @@ def duf_downsample(x, kernel_size=13, scale=4):
     return ops.bd_downsample(x, scale)
 
 
+# ------------------------------------------------------------------------------------------------ LQ crops from GT windows (training)
+LQ_WINDOW_SCALES = (2, 3, 4)
+LQ_WINDOW_RECORD_INTS = 8  # y0, x0 (the window's origin in its frame), H, W (the mod-cropped frame), top, left (the LQ crop's origin), 2 unused
+
+
+def _lq_taps(i, scale, degradation):
+    """(first, last) unreflected GT sample, 0-based, that LQ sample `i` of one axis reads with non-zero weight.  'bi': the support of
+    _imresize_reach - strictly inside (u - kw / 2, u + kw / 2), u = x / f + 0.5 (1 - 1 / f) for the 1-based x = i + 1, f = 1 / scale,
+    kw = 4 / f - in exact arithmetic (u is a multiple of 1/2).  'bd': the taps i * scale - 6 .. i * scale + 6 of bd_shape's 13-tap kernel
+    whose weight bd_weights does not truncate to zero."""
+    if degradation == 'bi':
+        from fractions import Fraction
+        f = Fraction(1, scale)
+        kw, u = 4 / f, (i + 1) / f + Fraction(1, 2) * (1 - 1 / f)
+        return math.floor(u - kw / 2) + 1 - 1, math.ceil(u + kw / 2) - 1 - 1
+    nz = np.flatnonzero(bd_weights(scale))
+    return i * scale - BD_KERNEL_SIZE // 2 + int(nz[0]), i * scale - BD_KERNEL_SIZE // 2 + int(nz[-1])
+
+
+def _lq_window_args(size, scale, degradation):
+    if degradation not in DEGRADATIONS:
+        raise ValueError(f'lq_window: degradation must be one of {DEGRADATIONS}, got {degradation!r}')
+    if isinstance(scale, bool) or scale not in LQ_WINDOW_SCALES or int(scale) != scale:
+        raise ValueError(f'lq_window: scale must be one of {LQ_WINDOW_SCALES}, got {scale!r} (degradation {degradation!r})')
+    if int(size) != size or size < 1:
+        raise ValueError(f'lq_window: a crop of {size} LQ samples is empty (gt_size is smaller than the scale)')
+    return int(size), int(scale)
+
+
+def lq_window_extent(size, scale, degradation):
+    """How many GT samples per axis the window of ANY crop of `size` LQ samples has: the unreflected span of its taps of non-zero weight,
+    first tap of the first sample to last tap of the last (the folded range of lq_window is never longer).  One number per
+    (size, scale, degradation), so staging slots have one size."""
+    size, scale = _lq_window_args(size, scale, degradation)
+    extent = _lq_taps(size - 1, scale, degradation)[1] - _lq_taps(0, scale, degradation)[0] + 1
+    reach = -_lq_taps(0, scale, degradation)[0]  # samples before the frame that the first crop reflects (their mirror images: 0 .. reach - 1 / 1 .. reach)
+    if reach > extent - (degradation == 'bd'):
+        raise ValueError(f'lq_window: a crop of {size} LQ samples has a window of {extent} GT samples, shorter than the {reach} one reflection reaches')
+    return extent
+
+
+def lq_window(start, size, n_lq, scale, degradation):
+    """One axis of a training crop made from GT: LQ samples [start, start + size) of a frame of n_lq LQ samples (n_lq * scale GT samples,
+    i.e. mod-cropped) read, with non-zero weight, GT samples [lo, hi) - AFTER the frame's boundary rule (imresize's symmetric extension
+    ... 1 0 | 0 1 ..., duf_downsample's reflection ... 2 1 | 0 1 2 ...) has folded the taps before the first and beyond the last sample
+    back in.  Returns (lo, hi, extent): extent = lq_window_extent(size, scale, degradation) >= hi - lo for every start, and the window
+    [lq_window_origin(lo, n_lq * scale, extent), + extent) holds [lo, hi) and lies inside the frame.  ValueError (as imresize_shape and
+    bd_shape raise it) for a scale outside {2, 3, 4}, a crop outside the frame, and a frame with fewer GT samples than the extent - one
+    reflection would not land inside the window.  Pure Python."""
+    extent = lq_window_extent(size, scale, degradation)
+    start, n_lq = int(start), int(n_lq)
+    n = n_lq * scale
+    if start < 0 or start + size > n_lq:
+        raise ValueError(f'lq_window: LQ samples [{start}, {start + size}) leave the frame of {n_lq}')
+    if n < extent:
+        raise ValueError(f'lq_window: {n} GT samples are fewer than the window of {extent} a crop of {size} LQ samples at x{scale} {degradation!r} reads')
+    a, b = _lq_taps(start, scale, degradation)[0], _lq_taps(start + size - 1, scale, degradation)[1]
+    ra, rb = (-a - 1, 2 * n - 1 - b) if degradation == 'bi' else (-a, 2 * (n - 1) - b)  # where the boundary rule sends a < 0 and b > n - 1
+    lo, hi = max(a, 0), min(b, n - 1)
+    if a < 0:
+        hi = max(hi, ra)
+    if b > n - 1:
+        lo = min(lo, rb)
+    assert 0 <= lo <= hi < n and hi - lo < extent, (lo, hi, n, extent)
+    return lo, hi + 1, extent
+
+
+def lq_window_origin(lo, n, extent):
+    """First GT sample of the fixed-size window that holds the range lq_window returned: the range's own start, pulled back where the
+    window would leave the frame of n GT samples."""
+    return min(lo, n - extent)
+
+
+def lq_window_pitch(extent):
+    """Bytes of one window row in a staging slot: 3 * extent, rounded up so that every row starts on a 16-byte boundary."""
+    return -(-3 * extent // 16) * 16
+
+
+def lq_window_size(extent, scale, degradation):
+    """The crop size whose window has `extent` GT samples (the inverse of lq_window_extent; ValueError if there is none)."""
+    lo = lq_window_extent(1, scale, degradation)
+    if extent < lo or (extent - lo) % scale:
+        raise ValueError(f'lq_window: no crop has a window of {extent} GT samples at x{scale} {degradation!r}')
+    return 1 + (extent - lo) // scale
+
+
+def training_lq_from_gt(opt):
+    """The `lq_from_gt` key of a TRAINING option block: None with an LQ tree (dataroot_lq given: nothing else is looked at), else
+    (scale, degradation) after the checks VideoTestClips makes - plus scale == opt['scale'] and scale in {2, 3, 4}, and no 'quantize':
+    False (the LQ crops are always the 8-bit values a stored tree holds)."""
+    if opt.get('dataroot_lq') is not None:
+        return None
+    if not opt.get('lq_from_gt'):
+        raise ValueError("dataroot_lq is None: give an LQ tree, or lq_from_gt = {'scale': s, 'degradation': 'bi' | 'bd'} to make the LQ crops from GT")
+    spec = dict(opt['lq_from_gt'])
+    degradation = spec.get('degradation', 'bi')
+    if degradation not in DEGRADATIONS:
+        raise ValueError(f'lq_from_gt: degradation must be one of {DEGRADATIONS}, got {degradation!r}')
+    scale = spec['scale']
+    if isinstance(scale, bool) or scale not in LQ_WINDOW_SCALES or int(scale) != scale:
+        raise ValueError(f'lq_from_gt: scale {scale!r} is not one of {LQ_WINDOW_SCALES} (degradation {degradation!r})')
+    if scale != opt['scale']:
+        raise ValueError(f"lq_from_gt: scale {scale} is not the dataset's scale {opt['scale']}")
+    if not spec.get('quantize', True):
+        raise ValueError('lq_from_gt: training LQ crops are always quantised to 8 bits (what a stored LQ tree holds)')
+    lq_window_extent(opt['gt_size'] // int(scale), int(scale), degradation)  # refuses a gt_size whose crop is empty
+    return int(scale), degradation
+
+
+class _WindowsFromGT:
+    """What a planner does instead of reading an LQ tree (lq_from_gt): sizes from the GT header, and load() stages per frame the window of
+    the decoded GT that the LQ crop reads plus its table record, for ops.lq_crops_from_windows."""
+
+    def __init__(self, client, lq_size, gt_size, scale, degradation):
+        self.client, self.lq_size, self.gt_size, self.scale, self.degradation = client, lq_size, gt_size, scale, degradation
+        self.extent = lq_window_extent(lq_size, scale, degradation)
+        self.pitch = lq_window_pitch(self.extent)
+
+    def sizes(self, clip, frame):
+        """((h_lq, w_lq), (h_gt, w_gt)) of the mod-cropped GT frame; ValueError where a frame is smaller than the window."""
+        h, w = self.client.size('gt', clip, frame)
+        h, w = h - h % self.scale, w - w % self.scale
+        if min(h, w) < self.extent:
+            raise ValueError(f'GT ({h}, {w}) is smaller than the window of {self.extent} samples that a {self.lq_size} x {self.lq_size} LQ crop '
+                             f'reads at x{self.scale} {self.degradation!r}. Please remove {clip}/{frame}.')
+        return (h // self.scale, w // self.scale), (h, w)
+
+    def empty(self, num_frame):
+        return np.zeros((num_frame, self.extent, self.pitch), np.uint8), np.zeros((num_frame, LQ_WINDOW_RECORD_INTS), np.int32)
+
+    def load(self, plan, names, center, lq_out, gt_out):
+        p, P, s, e = self.lq_size, self.gt_size, self.scale, self.extent
+        if lq_out is None:
+            lq_out = self.empty(len(names))
+        if gt_out is None:
+            gt_out = np.empty((P, P, 3), np.uint8)
+        win, tab = lq_out
+        have_gt = False
+        for i, name in enumerate(names):
+            img = decode_image(self.client.get('gt', plan.clip, name))
+            H, W = img.shape[0] - img.shape[0] % s, img.shape[1] - img.shape[1] % s
+            y0 = lq_window_origin(lq_window(plan.top, p, H // s, s, self.degradation)[0], H, e)
+            x0 = lq_window_origin(lq_window(plan.left, p, W // s, s, self.degradation)[0], W, e)
+            win[i, :, :3 * e] = img[y0:y0 + e, x0:x0 + e].reshape(e, 3 * e)
+            tab[i] = (y0, x0, H, W, plan.top, plan.left, 0, 0)
+            if name == center and not have_gt:
+                gt_out[...] = img[plan.top * s:plan.top * s + P, plan.left * s:plan.left * s + P]
+                have_gt = True
+        if not have_gt:
+            gt_out[...] = decode_image(self.client.get('gt', plan.clip, center))[plan.top * s:plan.top * s + P, plan.left * s:plan.left * s + P]
+        return lq_out, gt_out
+
+
 class VideoTestClips:
     """VideoTestDataset (basicsr/data/video_test_dataset.py:11-147) with the frames kept on the device.
 
@@ -622,8 +800,21 @@ class REDSDeviceLoader:
         self.seed = seed + rank  # the reference seeds every worker with seed + rank * workers + id (data/__init__.py)
         self.pool = ThreadPoolExecutor(num_threads)
         t, p, P = self.planner.num_frame, self.planner.lq_size, self.planner.gt_size
-        self.slots = [(torch.empty((batch_size, t, p, p, 3), dtype=torch.uint8).pin_memory(),
-                       torch.empty((batch_size, 1, P, P, 3), dtype=torch.uint8).pin_memory()) for _ in range(depth)]
+        # the one place the two sources of LQ part: what a slot's LQ half holds and how it becomes (b, t, p, p, 3) bytes on the device
+        if self.planner.lq_from_gt is None:
+            lq_slots = [torch.empty((batch_size, t, p, p, 3), dtype=torch.uint8).pin_memory() for _ in range(depth)]
+            self._lq_views = [s.numpy() for s in lq_slots]  # [slot][sample] -> what load() writes the LQ into
+            self._lq_upload = self._upload_lq_crops
+        else:
+            w = self.planner.windows
+            n_win, n_tab = batch_size * t * w.extent * w.pitch, batch_size * t * LQ_WINDOW_RECORD_INTS * 4
+            lq_slots = [torch.zeros(n_win + n_tab, dtype=torch.uint8).pin_memory() for _ in range(depth)]  # windows, then their table: one copy
+            self._win_shape, self._n_win = (batch_size * t, w.extent, w.pitch), n_win
+            self._tables = [s[n_win:].view(torch.int32).view(batch_size * t, LQ_WINDOW_RECORD_INTS) for s in lq_slots]
+            self._lq_views = [list(zip(s[:n_win].view(batch_size, t, w.extent, w.pitch).numpy(), tab.view(batch_size, t, -1).numpy()))
+                              for s, tab in zip(lq_slots, self._tables)]
+            self._lq_upload = self._upload_gt_windows
+        self.slots = [(lq, torch.empty((batch_size, 1, P, P, 3), dtype=torch.uint8).pin_memory()) for lq in lq_slots]
         self.stream = torch.cuda.Stream(self.device)
         self.epoch = 0
         self._start()
@@ -660,8 +851,7 @@ class REDSDeviceLoader:
                     return
                 if copied is not None:
                     copied.synchronize()  # the H2D copy that last read this slot
-                lq, gt = self.slots[slot]
-                lqn, gtn = lq.numpy(), gt.numpy()
+                lqn, gtn = self._lq_views[slot], self.slots[slot][1].numpy()
                 list(self.pool.map(lambda a: self.planner.load(a[1], lqn[a[0]], gtn[a[0], 0]), enumerate(plans)))
                 ready.put((slot, plans))
             ready.put(None)
@@ -669,6 +859,19 @@ class REDSDeviceLoader:
             ready.put(e)
 
     # ---- consumer
+    def _upload_lq_crops(self, slot, n):
+        return self.slots[slot][0][:n].to(self.device, non_blocking=True)
+
+    def _upload_gt_windows(self, slot, n):
+        """The slot's windows and table in one copy, then the LQ crops of the n samples: (n, t, p, p, 3) bytes, what an LQ tree holds there."""
+        from . import ops
+        scale, degradation = self.planner.lq_from_gt
+        t, p = self.planner.num_frame, self.planner.lq_size
+        dev = self.slots[slot][0].to(self.device, non_blocking=True)
+        windows = dev[:self._n_win].view(self._win_shape)[:n * t]
+        table = dev[self._n_win:].view(torch.int32).view(-1, LQ_WINDOW_RECORD_INTS)[:n * t]
+        return ops.lq_crops_from_windows(windows, table, scale, degradation, table_host=self._tables[slot][:n * t]).view(n, t, p, p, 3)
+
     def _preload(self):
         from . import ops
         item = self.ready.get()
@@ -682,7 +885,7 @@ class REDSDeviceLoader:
         n = len(plans)
         flags = bytes(p.flags for p in plans)
         with torch.cuda.stream(self.stream):
-            lq_d, gt_d = lq[:n].to(self.device, non_blocking=True), gt[:n].to(self.device, non_blocking=True)
+            lq_d, gt_d = self._lq_upload(slot, n), gt[:n].to(self.device, non_blocking=True)
             copied = torch.cuda.Event()
             copied.record(self.stream)
             out = {'lq': ops.frames_u8_to_f32(lq_d, flags), 'gt': ops.frames_u8_to_f32(gt_d, flags)[:, 0], 'key': [p.key for p in plans]}

@@ -1522,3 +1522,37 @@ def bd_downsample(frames, scale=4, out_dtype=torch.float32):
         _run('bd_downsample', lambda: _lib.check(_lib.lib().edvr_bd_downsample_f32(_ptr(frames), _ptr(out), n, H, W, _img_stride(frames), ho, wo, scale,
                                                                                    int(u8out), _stream()), 'edvr_bd_downsample_f32'), 0, nbytes)
     return out
+
+
+# ------------------------------------------------------------------------------------------------ LQ training crops from GT windows
+def lq_crops_from_windows(windows, table, scale, degradation, table_host=None):
+    """The LQ crops of a training batch from windows of their GT frames, in ONE launch of the imresize ('bi') or bd_downsample ('bd')
+    kernel on another view of its source: windows uint8 (n, e, pitch) - n windows of e rows of e RGB pixels, rows `pitch` =
+    data.lq_window_pitch(e) bytes apart, e = data.lq_window_extent(p, scale, degradation) - and table int32 (n, 8), both on the GPU (one
+    record per window: its origin y0, x0 in the frame, the mod-cropped frame's H, W, the crop's origin top, left in the LQ frame) ->
+    uint8 (n, p, p, 3): bit for bit imresize(frame, 1 / scale, out_dtype=uint8)[top:top + p, left:left + p] / the same of bd_downsample.
+    table_host: the same table in host memory (the pinned slot it was copied from), which the launch checks record by record before it
+    starts anything - without it only scale, extent and pitch are checked, and the kernel clamps every index into the window.
+    ValueError for a scale outside {2, 3, 4}, an unknown degradation and an e no crop size has; there is no CPU fallback."""
+    from .data import LQ_WINDOW_RECORD_INTS, lq_window_size
+    require_gpu(windows, dtypes=(torch.uint8,))
+    require_gpu(table, dtypes=(torch.int32,))
+    if windows.dim() != 3 or table.dim() != 2 or table.shape != (windows.shape[0], LQ_WINDOW_RECORD_INTS):
+        raise ValueError(f'windows are (n, e, pitch) uint8 with an (n, {LQ_WINDOW_RECORD_INTS}) int32 table, got {tuple(windows.shape)} and {tuple(table.shape)}')
+    n, e, pitch = windows.shape
+    if not 0 < n <= 65535:
+        raise ValueError(f'lq_crops_from_windows takes 1..65535 windows per call, got {n}')
+    p = lq_window_size(e, scale, degradation)  # ValueError: scale, degradation, extent
+    scale = int(scale)
+    if pitch % 16 or pitch < 3 * e:
+        raise ValueError(f'window rows of {e} pixels are {pitch} bytes apart: not a multiple of 16 that holds {3 * e}')
+    windows, table = windows.contiguous(), table.contiguous()
+    if table_host is not None:
+        if table_host.is_cuda or table_host.dtype != torch.int32 or table_host.shape != table.shape or not table_host.is_contiguous():
+            raise ValueError('table_host is the table as a contiguous int32 host tensor')
+    out = torch.empty((n, p, p, 3), dtype=torch.uint8, device=windows.device)
+    nbytes = 3.0 * n * (e * e + p * p) + 4.0 * table.numel()  # window pixels + table read, crops written, each element once
+    name = 'edvr_imresize_bicubic_u8_windows' if degradation == 'bi' else 'edvr_bd_downsample_u8_windows'
+    _run('lq_crops_from_windows', lambda: _lib.check(getattr(_lib.lib(), name)(_ptr(windows), _ptr(table), _ptr(table_host), _ptr(out), n, p, e, e, pitch,
+                                                                                scale, _stream()), name), 0, nbytes)
+    return out

@@ -554,6 +554,25 @@ int edvr_bd_downsample_u8(const uint8_t *src, void *dst, int n, int H, int W, in
 int edvr_bd_downsample_f32(const float *src, void *dst, int n, int H, int W, int64_t src_img_stride, int ho, int wo, int scale, int out_u8,
                            edvr_stream_t stream);
 
+/* The two degradations above for TRAINING crops: per image a p x p crop of the x`scale` LQ frame, made from a WINDOW of the GT frame -
+ * the GT samples the crop's taps read with non-zero weight once the frame's boundary rule has folded out-of-frame taps back in
+ * (edvr_amd/data.py: lq_window).  src: n dense windows of wh rows of `pitch` bytes (pitch % 16 == 0, pitch >= 3 ww, src 16-byte
+ * aligned: every row takes the 16-byte load path), ww interleaved RGB pixels per row; wh = ww = the fixed extent lq_window gives for
+ * (p, scale, degradation).  table: DEVICE array of n records of EDVR_LQ_WINDOW_RECORD_INTS int32: { y0, x0: the window's origin in its
+ * frame; H, W: the (mod-cropped) GT frame; top, left: the crop's origin in the LQ frame; 2 unused }.  dst (n, p, p, 3) bytes: exactly
+ * the bytes edvr_imresize_bicubic_u8 (scale 1 / `scale`, antialiasing, EDVR_RESIZE_OUT_U8) / edvr_bd_downsample_u8 (out_u8) give at
+ * [top, top + p) x [left, left + p) of the whole frame - by construction: weights are a function of the absolute output index, the
+ * boundary rule is applied in frame coordinates and then mapped into the window, and the passes are the full-frame kernels' own code.
+ * A tap of weight zero outside the window is clamped into it; whatever the table holds, no read leaves src and no write leaves dst.
+ * EDVR_ERR_ARG, nothing launched: scale outside {2, 3, 4}; wh or ww other than that extent; a pitch or src off 16 bytes; and, when
+ * table_host (a host copy of the table, or NULL) is given, any record whose frame, crop or window the geometry refuses.  No
+ * allocation, no wait. */
+#define EDVR_LQ_WINDOW_RECORD_INTS 8
+int edvr_imresize_bicubic_u8_windows(const uint8_t *src, const int32_t *table, const int32_t *table_host, uint8_t *dst, int n, int p, int wh,
+                                     int ww, int pitch, int scale, edvr_stream_t stream);
+int edvr_bd_downsample_u8_windows(const uint8_t *src, const int32_t *table, const int32_t *table_host, uint8_t *dst, int n, int p, int wh, int ww,
+                                  int pitch, int scale, edvr_stream_t stream);
+
 /* Multi-tensor Adam step <- torch.optim.Adam.step() as the reference builds it (basicsr/models/edvr_model.py:21-53, parameter
  * groups with dcn_lr_mul; stepped in sr_model.py:112).  `chunk_table` is a DEVICE array of n_chunks records of
  * edvr_adam_chunk_bytes() = 64 bytes: { float *p; const float *g; float *m; float *v; int32 n (<= 65536 elements of one tensor);

@@ -57,12 +57,18 @@ def train(args, log=print):
     data_opt = dict(dataroot_gt=args.gt, dataroot_lq=args.lq, dataroot_flow=None, meta_info_file=args.meta, val_partition=args.val_partition,
                     io_backend=dict(type='disk'), num_frame=args.num_frame, gt_size=args.gt_size, interval_list=[1], random_reverse=False,
                     use_flip=True, use_rot=True, scale=4)
+    lq_from_gt = getattr(args, 'lq_from_gt', None)
+    if args.lq is None:  # no LQ tree: the loader makes the LQ crops from windows of the GT frames on the device (8-bit, as a stored tree)
+        data_opt['lq_from_gt'] = dict(scale=lq_from_gt, degradation=getattr(args, 'degradation', None) or 'bi')
     loader = REDSDeviceLoader(data_opt, args.batch, device=device, rank=rank, world_size=world, ratio=args.enlarge_ratio,
                               seed=args.seed, num_threads=args.threads)
     val = None
-    if args.val_lq:
-        val = VideoTestClips(dict(name='REDS4', dataroot_gt=args.val_gt, dataroot_lq=args.val_lq, io_backend=dict(type='disk'),
-                                  cache_data=True, num_frame=args.num_frame, padding='reflection_circle'), device=device)
+    if args.val_lq or (args.val_gt and args.lq is None):
+        val_opt = dict(name='REDS4', dataroot_gt=args.val_gt, dataroot_lq=args.val_lq, io_backend=dict(type='disk'),
+                       cache_data=True, num_frame=args.num_frame, padding='reflection_circle')
+        if args.val_lq is None:  # the validation LQ frames likewise, quantised like the training crops
+            val_opt['lq_from_gt'] = dict(data_opt['lq_from_gt'], quantize=True)
+        val = VideoTestClips(val_opt, device=device)
     if state is not None:
         resume_training(state, [opt], [sched])
         loader.reset(epoch)
@@ -106,13 +112,18 @@ def train(args, log=print):
     return losses
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument('--gt', required=True)
-    ap.add_argument('--lq', required=True)
+    ap.add_argument('--lq', default=None, help='LQ tree; optional with --lq-from-gt')
+    ap.add_argument('--lq-from-gt', type=int, default=None, metavar='SCALE',
+                    help='train without an LQ tree: the loader makes each LQ crop from a window of the GT frame on the device, 8-bit '
+                         '(SCALE 4, the scale of the network)')
+    ap.add_argument('--degradation', choices=('bi', 'bd'), default='bi',
+                    help="with --lq-from-gt: bi = MATLAB bicubic, bd = DUF's Gaussian blur and subsampling")
     ap.add_argument('--meta', required=True)
     ap.add_argument('--val-gt')
-    ap.add_argument('--val-lq')
+    ap.add_argument('--val-lq', help='optional with --lq-from-gt: the validation LQ frames are then made from --val-gt the same way')
     ap.add_argument('--val-partition', default='REDS4')
     ap.add_argument('--no-f4', action='store_true', help='keep the F(4x4,3x3) Winograd kernel out of the training path (edvr_amd.ops.set_f4)')
     ap.add_argument('--num-feat', type=int, default=128)              # EDVR-L (options/train/EDVR/train_EDVR_L_x4_SR_REDS_*.yml)
@@ -136,7 +147,20 @@ def main():
     ap.add_argument('--resume', default=None)
     ap.add_argument('--pretrain', default=None)
     ap.add_argument('--seed', type=int, default=10)
-    train(ap.parse_args())
+    args = ap.parse_args(argv)
+    if (args.lq is None) == (args.lq_from_gt is None):
+        ap.error('give exactly one of --lq and --lq-from-gt')
+    if args.lq_from_gt is not None and args.lq_from_gt != 4:
+        ap.error('--lq-from-gt takes the scale of the network, 4')
+    if args.degradation == 'bd' and args.lq_from_gt is None:
+        ap.error('--degradation bd needs --lq-from-gt')
+    if args.val_gt and args.val_lq is None and args.lq_from_gt is None:
+        ap.error('--val-gt needs --val-lq (or --lq-from-gt)')
+    return args
+
+
+def main():
+    train(parse_args())
 
 
 if __name__ == '__main__':
