@@ -75,9 +75,10 @@ def _nb(*ts):
 _WS = {}
 
 
-def workspace(nbytes, device):
-    """Grow-only scratch buffer per (device, stream).  288 GB of HBM: keep it resident, never free per call."""
-    key = (device.index, torch.cuda.current_stream(device).cuda_stream)
+def workspace(nbytes, device, tag=None):
+    """Grow-only scratch buffer per (device, stream).  288 GB of HBM: keep it resident, never free per call.
+    tag: a buffer of its own per tag, for state that must survive other launches (None: the kernels' scratch, rewritten by any call)."""
+    key = (device.index, torch.cuda.current_stream(device).cuda_stream) if tag is None else (device.index, torch.cuda.current_stream(device).cuda_stream, tag)
     buf = _WS.get(key)
     if buf is None or buf.numel() < nbytes:
         buf = None
@@ -1438,6 +1439,174 @@ def copy_rect(x, out, ky=0, kx=0):
     kh, kw, row, plane, img = _rect_dst(out, n, h, w, ky, kx, False)
     _run('copy_rect', lambda: _lib.check(_lib.lib().edvr_copy_rect_f32(_ptr(x), _ptr(out), n, h, w, _img_stride(x), int(ky), int(kx), kh, kw,
                                                                        row, plane, img, _stream()), 'edvr_copy_rect_f32'), 0, 24.0 * n * kh * kw)
+    void_bound(out)
+    return out
+
+
+# ------------------------------------------------------------------------------------------------ self-ensemble (csrc/ensemble.hip)
+D4_FIRST, D4_LAST = 1, 2  # EDVR_D4_FIRST, EDVR_D4_LAST
+D4_MODES = {'first': D4_FIRST, 'middle': 0, 'last': D4_LAST, 'only': D4_FIRST | D4_LAST}
+
+
+def _d4_elem(elem):
+    k = int(elem)
+    if k != elem or not 0 <= k < 8:
+        raise ValueError(f'a symmetry of the square is an element id 0 ... 7 (4 t + 2 v + h), got {elem!r}')
+    return k
+
+
+def d4_apply(x, elem):
+    """g_k of a (..., H, W) tensor, k = 4 t + 2 v + h: transpose the last two axes if t, then flip rows if v, then flip columns if h
+    (plain torch, any device: the definition the kernels of csrc/ensemble.hip are tested against)."""
+    k = _d4_elem(elem)
+    if k & 4:
+        x = x.transpose(-1, -2)
+    if k & 2:
+        x = x.flip(-2)
+    if k & 1:
+        x = x.flip(-1)
+    return x
+
+
+def d4_invert(y, elem):
+    """g_k^-1: flip columns if h, then flip rows if v, then transpose if t."""
+    k = _d4_elem(elem)
+    if k & 1:
+        y = y.flip(-1)
+    if k & 2:
+        y = y.flip(-2)
+    if k & 4:
+        y = y.transpose(-1, -2)
+    return y
+
+
+def d4_index(elem, r, q, R, C):
+    """The index map the kernels implement (frame_to_tile in csrc/ensemble.hip), pure Python: pixel (r, q) of the frame's orientation
+    <-> (i, j) of the transformed (R, C) image - g_k(x)[i][j] = x[r][q] and g_k^-1(y)[r][q] = y[i][j]."""
+    k = _d4_elem(elem)
+    a, b = (q, r) if k & 4 else (r, q)
+    return (R - 1 - a if k & 2 else a), (C - 1 - b if k & 1 else b)
+
+
+def crop_pad_frames_d4(frames, y0, x0, th, tw, pad_mode=None, elem=0):
+    """d4_apply(crop_pad_frames(frames, y0, x0, th, tw, pad_mode), elem) in one launch, dense: (n, 3, th, tw), or (n, 3, tw, th) for a
+    transposing element (edvr_crop_pad_frames_d4_*).  The padding rule is applied in the frame's own orientation, before the symmetry."""
+    if not frames.is_cuda:
+        raise NotImplementedError('edvr_amd ops run on the GPU only (HIP/gfx950); got a CPU tensor')
+    k = _d4_elem(elem)
+    if pad_mode is not None and pad_mode not in PAD_MODES:
+        raise ValueError(f"pad_mode must be None, 'reflect' or 'replicate', got {pad_mode!r}")
+    u8 = frames.dtype == torch.uint8
+    if u8:
+        if frames.dim() != 4 or frames.shape[-1] != 3:
+            raise ValueError(f'uint8 frames are (n, H, W, 3), got {tuple(frames.shape)}')
+        frames = frames.contiguous()
+        n, H, W, _ = frames.shape
+    else:
+        require_gpu(frames)
+        if frames.dim() != 4 or frames.shape[1] != 3:
+            raise ValueError(f'float32 frames are (n, 3, H, W), got {tuple(frames.shape)}')
+        frames = _as_planes(frames)
+        n, _, H, W = frames.shape
+    y0, x0, th, tw = int(y0), int(x0), int(th), int(tw)
+    if n == 0 or th <= 0 or tw <= 0 or not (0 <= y0 < H and 0 <= x0 < W):
+        raise ValueError(f'crop_pad_frames_d4: a {th} x {tw} rectangle at ({y0}, {x0}) of {n} frame(s) of {H} x {W}')
+    reach = (H - 1, W - 1) if pad_mode is None else (2 * (H - 1), 2 * (W - 1)) if pad_mode == 'reflect' else None
+    if reach is not None and (y0 + th - 1 > reach[0] or x0 + tw - 1 > reach[1]):
+        raise ValueError(f'crop_pad_frames_d4: a {th} x {tw} rectangle at ({y0}, {x0}) reaches beyond what pad_mode={pad_mode!r} makes of a {H} x {W} frame')
+    mode = PAD_MODES[pad_mode or 'replicate']
+    out = torch.empty((n, 3, tw, th) if k & 4 else (n, 3, th, tw), dtype=torch.float32, device=frames.device)
+    if u8:
+        _run('crop_pad_frames_d4', lambda: _lib.check(_lib.lib().edvr_crop_pad_frames_d4_u8(_ptr(frames), _ptr(out), n, H, W, y0, x0, th, tw, mode, k,
+                                                                                            _stream()), 'edvr_crop_pad_frames_d4_u8'), 0, 5.0 * out.numel())
+    else:
+        _run('crop_pad_frames_d4', lambda: _lib.check(_lib.lib().edvr_crop_pad_frames_d4_f32(_ptr(frames), _ptr(out), n, H, W, _img_stride(frames), y0, x0,
+                                                                                             th, tw, mode, k, _stream()), 'edvr_crop_pad_frames_d4_f32'),
+             0, 8.0 * out.numel())
+    return out
+
+
+def _d4_tail(elem, mode, scale, hy, wy):
+    """-> (element id, mode bits, scale, the result's size in the frame's orientation)"""
+    k = _d4_elem(elem)
+    if mode not in D4_MODES:
+        raise ValueError(f'accumulate mode must be one of {sorted(D4_MODES)}, got {mode!r}')
+    return k, D4_MODES[mode], float(scale), ((wy, hy) if k & 4 else (hy, wy))
+
+
+def _d4_acc(acc, out, n, fh, fw, ky, kx):
+    """The float32 accumulator rectangle that goes with the byte rectangle `out`: the same pixels of a (N, 3, H, W) scratch."""
+    kh, kw, row, plane, img = _rect_dst(acc, n, fh, fw, ky, kx, False)
+    if (kh, kw) != (out.shape[1], out.shape[2]):
+        raise ValueError(f'the accumulator rectangle is {kh} x {kw}, the byte rectangle {out.shape[1]} x {out.shape[2]}')
+    return row, plane, img
+
+
+def upsample4x_add_rect_d4(y, base, out, ky=0, kx=0, elem=0, mode='only', scale=1.0):
+    """upsample4x_add_rect under a symmetry, accumulating: value = d4_invert(y + bilinear_x4(base), elem)[:, :, ky:ky + kh, kx:kx + kw] with y
+    and base in the tile's own, transformed orientation; `out` (a float32 rectangle view, the accumulator) takes value ('first'),
+    out + value ('middle'), (out + value) * scale ('last') or value * scale ('only')."""
+    require_gpu(y, base)
+    base = base.contiguous()
+    n, c, h, w = base.shape
+    if c != 3:
+        raise NotImplementedError(f'the rectangle stores are for RGB images: 3 channels, got {c}')
+    assert y.is_contiguous() and tuple(y.shape) == (n, c, 4 * h, 4 * w)
+    k, bits, scale, (fh, fw) = _d4_tail(elem, mode, scale, 4 * h, 4 * w)
+    kh, kw, row, plane, img = _rect_dst(out, n, fh, fw, ky, kx, False)
+    _run('upsample4x_add_rect_d4', lambda: _lib.check(_lib.lib().edvr_upsample4x_add_rect_d4_f32(
+        _ptr(y), _ptr(base), _ptr(out), n, h, w, int(ky), int(kx), kh, kw, row, plane, img, k, bits, scale, _stream()), 'edvr_upsample4x_add_rect_d4_f32'),
+         0, _nb(base) + 36.0 * n * kh * kw)
+    void_bound(out)
+    return out
+
+
+def upsample4x_add_u8_rect_d4(y, base, out, acc, ky=0, kx=0, elem=0, mode='only', scale=1.0):
+    """The byte form: `acc` (the float32 rectangle of a scratch that goes with the uint8 rectangle `out`) accumulates as in
+    upsample4x_add_rect_d4; the 'last' / 'only' launch reads it and stores tensor2img bytes of the result into `out` instead."""
+    require_gpu(y, base)
+    base = base.contiguous()
+    n, c, h, w = base.shape
+    if c != 3:
+        raise NotImplementedError(f'the uint8 output is interleaved RGB: 3 channels, got {c}')
+    assert y.is_contiguous() and tuple(y.shape) == (n, c, 4 * h, 4 * w)
+    k, bits, scale, (fh, fw) = _d4_tail(elem, mode, scale, 4 * h, 4 * w)
+    kh, kw, row, _, img = _rect_dst(out, n, fh, fw, ky, kx, True)
+    a_row, a_plane, a_img = _d4_acc(acc, out, n, fh, fw, ky, kx)
+    _run('upsample4x_add_u8_rect_d4', lambda: _lib.check(_lib.lib().edvr_upsample4x_add_rect_d4_u8(
+        _ptr(y), _ptr(base), _ptr(acc), _ptr(out), n, h, w, int(ky), int(kx), kh, kw, a_row, a_plane, a_img, row, img, k, bits, scale, _stream()),
+        'edvr_upsample4x_add_rect_d4_u8'), 0, _nb(base) + 36.0 * n * kh * kw)
+    return out
+
+
+def f32_to_u8_hwc_rect_d4(x, out, acc, ky=0, kx=0, elem=0, mode='only', scale=1.0):
+    """f32_to_u8_hwc_rect under a symmetry, accumulating in `acc` as upsample4x_add_u8_rect_d4 does (value = d4_invert(x, elem)[...])."""
+    require_gpu(x)
+    x = _as_planes(x)
+    n, c, h, w = x.shape
+    if c != 3:
+        raise NotImplementedError(f'the uint8 output is interleaved RGB: 3 channels, got {c}')
+    k, bits, scale, (fh, fw) = _d4_tail(elem, mode, scale, h, w)
+    kh, kw, row, _, img = _rect_dst(out, n, fh, fw, ky, kx, True)
+    a_row, a_plane, a_img = _d4_acc(acc, out, n, fh, fw, ky, kx)
+    _run('f32_to_u8_hwc_rect_d4', lambda: _lib.check(_lib.lib().edvr_f32_to_u8_hwc_rect_d4(
+        _ptr(x), _ptr(acc), _ptr(out), n, h, w, _img_stride(x), int(ky), int(kx), kh, kw, a_row, a_plane, a_img, row, img, k, bits, scale, _stream()),
+        'edvr_f32_to_u8_hwc_rect_d4'), 0, 36.0 * n * kh * kw)
+    return out
+
+
+def copy_rect_d4(x, out, ky=0, kx=0, elem=0, mode='only', scale=1.0):
+    """copy_rect under a symmetry, accumulating in the float32 rectangle `out` (value = d4_invert(x, elem)[:, :, ky:ky + kh, kx:kx + kw])."""
+    require_gpu(x)
+    x = _as_planes(x)
+    n, c, h, w = x.shape
+    if c != 3:
+        raise NotImplementedError(f'the rectangle stores are for RGB images: 3 channels, got {c}')
+    k, bits, scale, (fh, fw) = _d4_tail(elem, mode, scale, h, w)
+    kh, kw, row, plane, img = _rect_dst(out, n, fh, fw, ky, kx, False)
+    _run('copy_rect_d4', lambda: _lib.check(_lib.lib().edvr_copy_rect_d4_f32(
+        _ptr(x), _ptr(out), n, h, w, _img_stride(x), int(ky), int(kx), kh, kw, row, plane, img, k, bits, scale, _stream()), 'edvr_copy_rect_d4_f32'),
+         0, 36.0 * n * kh * kw)
     void_bound(out)
     return out
 

@@ -13,6 +13,12 @@ byte conversion in one launch), every tile has a bank of its own, and the last k
 rectangle of its result into the chunk's full-frame output (the `*_rect` tails of csrc/video.hip).  No blending: inside its kept
 rectangle a tile's result is final, and equals what the plain path computes on that tile's crop.
 
+Self-ensemble (`self_ensemble`): the video is restored under each of up to eight symmetries of the square, the symmetry is undone and
+the results are averaged.  A symmetry is the same shape of work as a tile - the per-frame stage reads an ORIENTED crop
+(ops.crop_pad_frames_d4), every (tile, element) pair has a bank of its own (the per-frame features are not equivariant), and the last
+kernel of each pair's restore pass stores the inverse symmetry of its kept rectangle, accumulating over the elements (the `*_rect_d4`
+tails of csrc/ensemble.hip).
+
 No-grad inference only: there is no backward through the bank.
 """
 from collections import namedtuple
@@ -32,6 +38,32 @@ def window_table(n_frames, num_frame, padding='reflection_circle'):
     if any(not 0 <= f < n_frames for r in rows for f in r):
         raise ValueError(f"a video of {n_frames} frame(s) is too short for windows of {num_frame} with '{padding}' padding")
     return torch.tensor(rows, dtype=torch.int32).reshape(n_frames, num_frame)
+
+
+ENSEMBLES = {'flip4': (0, 1, 2, 3), 'd4': (0, 1, 2, 3, 4, 5, 6, 7)}
+
+
+def ensemble_elements(self_ensemble):
+    """None | 'flip4' | 'd4' | a sequence of distinct element ids -> None or the tuple of ids, in the order they run.  Element
+    k = 4 t + 2 v + h (t, v, h in {0, 1}) acts on the last two axes: g_k(x) = x.transpose(-1, -2) if t, then .flip(-2) if v, then
+    .flip(-1) if h (ops.d4_apply; ops.d4_invert undoes it)."""
+    if self_ensemble is None:
+        return None
+    if isinstance(self_ensemble, str):
+        if self_ensemble not in ENSEMBLES:
+            raise ValueError(f"self_ensemble must be None, 'flip4', 'd4' or a sequence of element ids 0 ... 7, got {self_ensemble!r}")
+        return ENSEMBLES[self_ensemble]
+    try:
+        ids = tuple(self_ensemble)
+    except TypeError:
+        raise ValueError(f"self_ensemble must be None, 'flip4', 'd4' or a sequence of element ids 0 ... 7, got {self_ensemble!r}") from None
+    if not ids:
+        raise ValueError('self_ensemble: an empty sequence of elements (None turns the ensemble off)')
+    if any(isinstance(k, bool) or not isinstance(k, int) or not 0 <= k < 8 for k in ids):
+        raise ValueError(f'self_ensemble: element ids are integers 0 ... 7 (4 t + 2 v + h), got {ids}')
+    if len(set(ids)) != len(ids):
+        raise ValueError(f'self_ensemble: element ids must be distinct, got {ids}')
+    return ids
 
 
 Tile = namedtuple('Tile', 'src keep dst')
@@ -189,10 +221,22 @@ class VideoRestorer:
     tile, each tile's last kernel storing its kept rectangle into the chunk's full-frame output - bit for bit what this class computes on
     that tile's crop of the padded frames.  Near the cuts the result differs from the untiled one (the network's receptive field is
     larger than any sensible overlap); what shrinks is the memory of everything after the gather, by about the tiles' share of the frame.
-    Either argument turns the tiled path on: uint8 frames then stay bytes (no full-frame float copy), all pieces must share one dtype."""
+    Either argument turns the tiled path on: uint8 frames then stay bytes (no full-frame float copy), all pieces must share one dtype.
+
+    self_ensemble None | 'flip4' (elements 0 ... 3: the flips) | 'd4' (0 ... 7: flips and the transpose) | a sequence of distinct
+    element ids k = 4 t + 2 v + h, run in the order given (`ensemble_elements`).  With P the bottom / right extension of pad_mode in the
+    frame's own orientation, R what this class computes without the argument (float32; on a tile's crop in the tiled path) and g_k the
+    symmetry,
+        acc = g_k0^-1(R(g_k0(P(lq))));  acc = acc + g_ki^-1(R(g_ki(P(lq)))) for i = 1 ... n - 1, in that order, in float32
+        out = crop(acc * (1 / n))       (uint8 output: the tensor2img bytes of that value)
+    It turns the tiled path on as well and composes with pad_mode and tile (the symmetry acts on each tile's crop).  The work list is
+    (tile x element), element innermost; windows, temporal padding and chunking are untouched (no temporal reversal).
+    WHAT IT COSTS: n times the time of the plain path (every kernel of the network runs once per element; the new oriented reads and
+    accumulating tails are bandwidth-sized) and n banks per tile (same ring, same capacity each), plus - with uint8 output - one
+    float32 (chunk, 3, s H, s W) accumulator that lives across chunks.  A transposing element runs the network on (W, H) frames."""
 
     def __init__(self, net, num_frame=None, padding='reflection_circle', chunk=8, out_dtype=torch.float32, pad_mode=None, tile=None,
-                 tile_overlap=None):
+                 tile_overlap=None, self_ensemble=None):
         if out_dtype not in (torch.float32, torch.uint8):
             raise ValueError(f'out_dtype must be torch.float32 or torch.uint8, got {out_dtype}')
         if pad_mode not in (None, 'reflect', 'replicate'):
@@ -204,7 +248,8 @@ class VideoRestorer:
         elif tile_overlap is not None:
             raise ValueError('tile_overlap without tile')
         self.pad_mode, self.tile, self.tile_overlap = pad_mode, tile, tile_overlap
-        self.tiled = pad_mode is not None or tile is not None
+        self.elements = ensemble_elements(self_ensemble)
+        self.tiled = pad_mode is not None or tile is not None or self.elements is not None
         self.net, self.padding, self.chunk, self.out_dtype = net, padding, int(chunk), out_dtype
         self.num_feat = net.conv_l2_1.in_channels
         if num_frame is None:
@@ -221,6 +266,7 @@ class VideoRestorer:
         self._groups = []       # (first frame, count, [bound or None per level], [depth per level]) of every extract call with live frames
         self._pieces = []       # (first frame, float32 (k, 3, H, W)) input frames not dead yet (tiled path: as they came, uint8 (k, H, W, 3) too)
         self.grid = None        # tiled path: [Tile] of the running restore, and per tile ...
+        self.pairs = None       # ... the work list [(Tile, element id or None)]: tile x element, element innermost, and per pair ...
         self.banks = None       # ... its [f1, f2, f3] rings
         self._tile_groups = None  # ... and its _groups
 
@@ -239,6 +285,21 @@ class VideoRestorer:
     def _crop(self, frames, y0, x0, th, tw):
         """The tile at (y0, x0) of `frames` (uint8 HWC or float32 CHW) extended by pad_mode, as float32 (k, 3, th, tw)."""
         return ops.crop_pad_frames(frames, y0, x0, th, tw, self.pad_mode)
+
+    def _crop_d4(self, frames, y0, x0, th, tw, elem):
+        """ops.d4_apply(self._crop(...), elem) in one launch: the oriented tile a self-ensemble element reads."""
+        return ops.crop_pad_frames_d4(frames, y0, x0, th, tw, self.pad_mode, elem)
+
+    def _scratch(self, shape, device):
+        """The float32 accumulator of a chunk with uint8 output: a grow-only buffer of its own (ops.workspace under a tag - the
+        untagged one is the kernels' scratch and is rewritten by the launches between two elements)."""
+        count = 1
+        for d in shape:
+            count *= d
+        return ops.workspace(4 * count, device, tag='self_ensemble')[:4 * count].view(torch.float32).view(shape)
+
+    def _oriented(self, frames, tile, elem):
+        return self._crop(frames, *tile.src) if elem is None else self._crop_d4(frames, *tile.src, elem)
 
     # ---- input
     def _check_mode(self):
@@ -352,16 +413,19 @@ class VideoRestorer:
         self.grid = tile_grid(H, W, self.tile, self.tile_overlap, m)
         th, tw = self.grid[0].src[2:]
         self.slots = self.capacity if length is None else max(1, min(self.capacity, length))
-        self.banks = [[torch.empty((self.slots,) + s, dtype=torch.float32, device=frames.device) for s in self._pyramid_shapes(th, tw)]
-                      for _ in self.grid]
-        self._tile_groups = [[] for _ in self.grid]
+        self.pairs = [(tile, k) for tile in self.grid for k in (self.elements or (None,))]
+        # (a transposing element's network runs on (tw, th) tiles)
+        self.banks = [[torch.empty((self.slots,) + s, dtype=torch.float32, device=frames.device)
+                       for s in (self._pyramid_shapes(tw, th) if k is not None and k & 4 else self._pyramid_shapes(th, tw))]
+                      for _, k in self.pairs]
+        self._tile_groups = [[] for _ in self.pairs]
 
     def _extract_tiled(self, first, count, length):
         frames = self._frames(first, first + count)
         if self.banks is None:
             self._setup_tiles(frames, length)
-        for tile, bank, groups in zip(self.grid, self.banks, self._tile_groups):
-            self._extract_into(bank, groups, self._crop(frames, *tile.src), first, count)
+        for (tile, k), bank, groups in zip(self.pairs, self.banks, self._tile_groups):
+            self._extract_into(bank, groups, self._oriented(frames, tile, k), first, count)
 
     def _restore_tiled(self, first, rows):
         net, t, s, b = self.net, self.num_frame, self.scale, len(rows)
@@ -370,16 +434,23 @@ class VideoRestorer:
         u8 = self.out_dtype == torch.uint8
         out = torch.empty((b, s * H, s * W, 3) if u8 else (b, 3, s * H, s * W), dtype=self.out_dtype, device=centre.device)
         table = self._slot_table([f % self.slots for r in rows for f in r], centre.device)
-        for tile, bank, groups in zip(self.grid, self.banks, self._tile_groups):
-            net.check_offsets(wait=False)  # per tile what a forward does before its launches, as in _restore
+        n = len(self.elements) if self.elements is not None else 0
+        acc = self._scratch((b, 3, s * H, s * W), centre.device) if n and u8 else None  # uint8 output: the elements add up in float32
+        for i, ((tile, k), bank, groups) in enumerate(zip(self.pairs, self.banks, self._tile_groups)):
+            net.check_offsets(wait=False)  # per tile (and element) what a forward does before its launches, as in _restore
             if bank[0].is_cuda:
                 ops.split_guard_check(wait=False)
             self._bank_bounds(bank, groups)
             pyr = self._gather(bank, table)
             (ky, kx, kh, kw), (oy, ox) = tile.keep, tile.dst
             ys, xs = slice(s * oy, s * (oy + kh)), slice(s * ox, s * (ox + kw))
-            net.restore_from_features(pyr, self._crop(centre, *tile.src), b, t, out_dtype=self.out_dtype,
-                                      out=out[:, ys, xs] if u8 else out[:, :, ys, xs], keep=(s * ky, s * kx))
+            how = {}
+            if k is not None:  # the oriented, accumulating tail: the float32 output accumulates in place, the bytes in `acc`
+                e = i % n
+                how = dict(elem=k, accumulate='only' if n == 1 else 'first' if e == 0 else 'last' if e == n - 1 else 'middle', scale=1.0 / n,
+                           acc=acc[:, :, ys, xs] if u8 else None)
+            net.restore_from_features(pyr, self._oriented(centre, tile, k), b, t, out_dtype=self.out_dtype,
+                                      out=out[:, ys, xs] if u8 else out[:, :, ys, xs], keep=(s * ky, s * kx), **how)
         return out
 
     # ---- public
@@ -400,7 +471,7 @@ class VideoRestorer:
         self._check_mode()
         self.schedule = sched = WindowSchedule(self.num_frame, self.padding, self.chunk, _probe=False)
         self.bank, self._groups, self._pieces = None, [], []
-        self.grid = self.banks = self._tile_groups = None
+        self.grid = self.pairs = self.banks = self._tile_groups = None
         try:
             for item in frames:
                 piece = self._as_frames(item)

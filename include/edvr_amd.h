@@ -514,6 +514,38 @@ int edvr_f32_to_u8_hwc_rect(const float *x, uint8_t *dst, int n, int h, int w, i
 int edvr_copy_rect_f32(const float *x, float *dst, int n, int h, int w, int64_t x_img_stride, int ky, int kx, int kh, int kw,
                        int64_t dst_row_stride, int64_t dst_plane_stride, int64_t dst_img_stride, edvr_stream_t stream);
 
+/* Self-ensemble (flip / D4 test-time augmentation; edvr_amd/video.py: self_ensemble).  elem = 4 t + 2 v + h names a symmetry of the
+ * square on the last two axes: g(x) = x transposed if t, then rows reversed if v, then columns reversed if h; its inverse applies the
+ * same steps in the opposite order.
+ * edvr_crop_pad_frames_d4_*: the (th, tw) rectangle edvr_crop_pad_frames_* delivers (the padding rule applied in SOURCE coordinates), as
+ * the dense tile g(rectangle): dst (n, 3, th, tw), or (n, 3, tw, th) when t.
+ * edvr_*_rect_d4_*: the rectangle tails above storing g^-1 of the tile's result and accumulating over the elements of an ensemble.  y /
+ * base / x (and h, w) are in the tile's own, TRANSFORMED orientation and the value of a pixel is the very expression of the plain tail
+ * there; (ky, kx, kh, kw) is the kept rectangle of g^-1(result), i.e. in the frame's orientation.  acc: float32 accumulator rectangle
+ * (row / plane / image strides in floats); mode: EDVR_D4_FIRST -> acc = value (acc is not read); 0 -> acc = acc + value; EDVR_D4_LAST ->
+ * (acc + value) * scale, stored into acc (float tails) or as tensor2img bytes into dst (byte tails: acc is read only, dst is touched by
+ * this mode alone); EDVR_D4_FIRST | EDVR_D4_LAST (an ensemble of one) -> value * scale.  Round-to-nearest adds and one multiply, in that
+ * order; one writer per pixel and launch, no atomics.  Transposing elements go through a padded 32 x 32 LDS tile, so that reads and
+ * stores both run along rows. */
+#define EDVR_D4_FIRST 1
+#define EDVR_D4_LAST 2
+int edvr_crop_pad_frames_d4_u8(const uint8_t *src, float *dst, int n, int H, int W, int y0, int x0, int th, int tw, int pad_mode, int elem,
+                               edvr_stream_t stream);
+int edvr_crop_pad_frames_d4_f32(const float *src, float *dst, int n, int H, int W, int64_t src_img_stride, int y0, int x0, int th, int tw,
+                                int pad_mode, int elem, edvr_stream_t stream);
+int edvr_upsample4x_add_rect_d4_f32(const float *y, const float *base, float *acc, int n, int h, int w, int ky, int kx, int kh, int kw,
+                                    int64_t acc_row_stride, int64_t acc_plane_stride, int64_t acc_img_stride, int elem, int mode, float scale,
+                                    edvr_stream_t stream);
+int edvr_upsample4x_add_rect_d4_u8(const float *y, const float *base, float *acc, uint8_t *dst, int n, int h, int w, int ky, int kx, int kh,
+                                   int kw, int64_t acc_row_stride, int64_t acc_plane_stride, int64_t acc_img_stride, int64_t dst_row_stride,
+                                   int64_t dst_img_stride, int elem, int mode, float scale, edvr_stream_t stream);
+int edvr_f32_to_u8_hwc_rect_d4(const float *x, float *acc, uint8_t *dst, int n, int h, int w, int64_t x_img_stride, int ky, int kx, int kh,
+                               int kw, int64_t acc_row_stride, int64_t acc_plane_stride, int64_t acc_img_stride, int64_t dst_row_stride,
+                               int64_t dst_img_stride, int elem, int mode, float scale, edvr_stream_t stream);
+int edvr_copy_rect_d4_f32(const float *x, float *acc, int n, int h, int w, int64_t x_img_stride, int ky, int kx, int kh, int kw,
+                          int64_t acc_row_stride, int64_t acc_plane_stride, int64_t acc_img_stride, int elem, int mode, float scale,
+                          edvr_stream_t stream);
+
 /* MATLAB-style bicubic imresize on the device <- imresize / calculate_weights_indices (basicsr/utils/matlab_functions.py:88-170 and
  * 17-84; the Python statement of scripts/matlab_scripts/generate_bicubic_img.m, i.e. of "BI x4"): one launch resamples n frames by one
  * factor on both axes, rows first, then columns, accumulating in fp32.  Per axis, for the 1-based output x: u = x / scale + 0.5 (1 - 1 /

@@ -17,6 +17,11 @@ Frames of any size (VideoRestorer pad_mode / tile), same method, merged into pro
     python scripts/bench_video.py --leg tiles --config L_T5                     # 544x960 untiled against 2x2 tiles, time and peak memory
     python scripts/bench_video.py --leg seam --config L_T5                      # |tiled - untiled| near and away from the cuts, per overlap
     python scripts/bench_video.py --leg large --config L_T5                     # peak memory against frame area, extrapolated
+
+Self-ensemble (VideoRestorer self_ensemble), same method, merged into profiles/video/bench_video_ensemble.json:
+
+    python scripts/bench_video.py --self-ensemble flip4 --config L_T5 [--out-dtype uint8]   # frames/s against the plain path (~ 1 / n)
+    python scripts/bench_video.py --self-ensemble d4 --config L_T5                          # and the new kernels' share of kernel time
 """
 import argparse
 import json
@@ -251,6 +256,32 @@ def leg_large(args, net, kwargs, dev, frames, chunk):
     return out
 
 
+D4_KERNELS = ('crop_pad_frames_d4', 'upsample4x_add_rect_d4', 'upsample4x_add_u8_rect_d4', 'f32_to_u8_hwc_rect_d4', 'copy_rect_d4')
+
+
+def leg_ensemble(args, net, kwargs, dev, frames, chunk):
+    """self_ensemble against the plain VideoRestorer at the same chunk: frames/s (expected about 1 / n), peak memory, and the share of
+    kernel time spent in the oriented reads and accumulating tails of csrc/ensemble.hip."""
+    from edvr_amd import VideoRestorer, ensemble_elements
+    h, w = CONFIGS[args.config][1]
+    dt = getattr(torch, args.out_dtype)
+    elements = ensemble_elements(args.self_ensemble)
+    lq = torch.rand(frames, 3, h, w, generator=torch.Generator().manual_seed(0)).to(dev)
+    plain = VideoRestorer(net, padding=args.padding, chunk=chunk, out_dtype=dt)
+    plus = VideoRestorer(net, padding=args.padding, chunk=chunk, out_dtype=dt, self_ensemble=elements)
+    res, outs = _two_arms({'ensemble': lambda: plus.restore(lq), 'plain': lambda: plain.restore(lq)}, frames, args.repeats, net)
+    tab = kernel_table(lambda: plus.restore(lq))
+    net.check_offsets()
+    new_ms = sum(r['ms'] for r in tab['kernels'] if r['name'] in D4_KERNELS)
+    diff = (outs['ensemble'].float() - outs['plain'].float()).abs().max().item()
+    ratio = res['ensemble']['frames_per_s'] / res['plain']['frames_per_s']
+    return {'leg': 'ensemble', 'hw': [h, w], 'self_ensemble': args.self_ensemble, 'elements': list(elements), 'banks': len(plus.pairs),
+            'ratio_ensemble_over_plain_frames_per_s': round(ratio, 4), 'expected_ratio_one_over_n': round(1.0 / len(elements), 4),
+            'new_kernels_ms': round(new_ms, 3), 'new_kernels_share_of_kernel_time': round(new_ms / tab['kernel_ms'], 5),
+            'new_kernels': [r for r in tab['kernels'] if r['name'] in D4_KERNELS],
+            'max_abs_difference_to_plain_output': diff, **res}
+
+
 def main_leg(args):
     from edvr_amd import _lib
     from edvr_amd.build import source_hash
@@ -259,14 +290,17 @@ def main_leg(args):
     dev = torch.device('cuda:0')
     net = _build_net(kwargs, dev)
     with torch.no_grad():
-        result = {'pad': leg_pad, 'tiles': leg_tiles, 'seam': leg_seam, 'large': leg_large}[args.leg](args, net, kwargs, dev, frames, chunk)
+        legs = {'pad': leg_pad, 'tiles': leg_tiles, 'seam': leg_seam, 'large': leg_large, 'ensemble': leg_ensemble}
+        result = legs[args.leg](args, net, kwargs, dev, frames, chunk)
     result = {'config': args.config, 'edvr': dict(kwargs), 'frames': frames, 'chunk': chunk, 'padding': args.padding, 'out_dtype': args.out_dtype,
               'repeats': args.repeats, **result, 'csrc_sha16': source_hash(), 'library': _lib.lib().edvr_version().decode(),
               'device': torch.cuda.get_device_name(0)}
-    path = os.path.abspath(args.json or os.path.join(os.path.dirname(os.path.abspath(__file__)), '..', 'profiles', 'video', 'bench_video_tiles.json'))
+    default = 'bench_video_ensemble.json' if args.leg == 'ensemble' else 'bench_video_tiles.json'
+    path = os.path.abspath(args.json or os.path.join(os.path.dirname(os.path.abspath(__file__)), '..', 'profiles', 'video', default))
     os.makedirs(os.path.dirname(path), exist_ok=True)
     merged = json.load(open(path)) if os.path.exists(path) else {}
-    merged[f'{args.leg}_{args.config}' + ('' if args.out_dtype == 'float32' else '_' + args.out_dtype)] = result
+    key = f'{args.self_ensemble}_{args.config}' if args.leg == 'ensemble' else f'{args.leg}_{args.config}'
+    merged[key + ('' if args.out_dtype == 'float32' else '_' + args.out_dtype)] = result
     with open(path, 'w') as f:
         json.dump(merged, f, indent=1, sort_keys=True)
         f.write('\n')
@@ -283,7 +317,13 @@ def main():
     ap.add_argument('--out-dtype', default='float32', choices=['float32', 'uint8'])
     ap.add_argument('--json', default=None, help='default: profiles/video/bench_video.json (bench_video_tiles.json with --leg)')
     ap.add_argument('--leg', default=None, choices=['pad', 'tiles', 'seam', 'large'], help='frames of any size: pad_mode / tile measurements')
+    ap.add_argument('--self-ensemble', default=None, choices=['flip4', 'd4'],
+                    help='timing arm: self_ensemble against the plain VideoRestorer (profiles/video/bench_video_ensemble.json)')
     args = ap.parse_args()
+    if args.self_ensemble:
+        if args.leg:
+            ap.error('--self-ensemble is a leg of its own: give it without --leg')
+        args.leg = 'ensemble'
     if not torch.cuda.is_available():
         raise SystemExit('bench_video.py measures on the GPU: none found')
     if args.leg:

@@ -2,6 +2,8 @@
 (metrics.validate_video on edvr_amd/video.py: VideoRestorer) instead of once per window the frame appears in.  Same options, same
 sharding of the clips over the ranks, same per-folder and overall averages; `--batch` is the number of output frames per alignment /
 fusion / reconstruction pass.  `--pad-mode reflect` admits frames of any size, `--tile TH TW` bounds the memory of large ones.
+`--self-ensemble flip4|d4` also restores every clip under the 4 flips / the 8 symmetries of the square and averages (the "+" rows of
+the papers; VideoRestorer's self_ensemble, n times the time) and reports the plain and the ensemble PSNR side by side.
 
     python scripts/eval_video.py --lq datasets/REDS4/sharp_bicubic --gt datasets/REDS4/GT --weights EDVR_L_x4_SR_REDS_official.pth
     python scripts/eval_video.py --lq-from-gt 4 --bicubic-baseline --gt my_footage --weights EDVR_L_x4_SR_REDS_official.pth
@@ -59,12 +61,17 @@ def evaluate(args, log=print):
     ds = VideoTestClips(opt, device=device)
     # frames of any size (--pad-mode / --tile / --tile-overlap): passed on only where given
     any_size = {k: (tuple(v) if k == 'tile' else v) for k in ('pad_mode', 'tile', 'tile_overlap') for v in [getattr(args, k, None)] if v is not None}
-    results, base = {}, {}
+    ensemble = getattr(args, 'self_ensemble', None)
+    results, base, plus = {}, {}, {}
     for folder in ds.folders[rank::world]:
         lq, gt = ds.clip(folder)
         _, psnr = metrics.validate_video(net, lq, gt, num_frame=args.num_frame, padding=args.padding, chunk=args.batch,
                                          crop_border=args.crop_border, test_y_channel=args.test_y_channel, **any_size)
         results[folder] = (sum(psnr), len(psnr))
+        if ensemble:
+            _, p = metrics.validate_video(net, lq, gt, num_frame=args.num_frame, padding=args.padding, chunk=args.batch,
+                                          crop_border=args.crop_border, test_y_channel=args.test_y_channel, self_ensemble=ensemble, **any_size)
+            plus[folder] = (sum(p), len(p))
         if baseline:
             b = bicubic_baseline(lq, gt, args.hr_in, args.crop_border, args.test_y_channel, args.batch)
             base[folder] = (sum(b), len(b))
@@ -82,17 +89,21 @@ def evaluate(args, log=print):
         return {k: s / max(n, 1) for k, (s, n) in sorted(parts.items())}
 
     summary, base = merged(results), merged(base) if baseline else {}
+    plus = merged(plus) if ensemble else {}
     if rank == 0:
         beside = (lambda v: f' (bicubic {v:.4f} dB)') if baseline else (lambda v: '')
+        with_plus = (lambda v: f', self-ensemble {ensemble} {v:.4f} dB') if ensemble else (lambda v: '')
         for k, v in summary.items():
-            log(f'{k}: PSNR {v:.4f} dB' + beside(base.get(k, float('nan'))))
+            log(f'{k}: PSNR {v:.4f} dB' + with_plus(plus.get(k, float('nan'))) + beside(base.get(k, float('nan'))))
         if summary:  # the average of the per-folder averages
             log(f'average over {len(summary)} folder(s): {sum(summary.values()) / len(summary):.4f} dB' +
-                beside(sum(base.values()) / max(len(base), 1)))
+                with_plus(sum(plus.values()) / max(len(plus), 1)) + beside(sum(base.values()) / max(len(base), 1)))
         if getattr(args, 'json', None):
             import json
             record = {'psnr': summary, 'average': sum(summary.values()) / max(len(summary), 1),
                       'degradation': degradation if args.lq is None else None}  # None: the LQ folder's, whatever made it
+            if ensemble:
+                record.update(self_ensemble=ensemble, self_ensemble_psnr=plus, self_ensemble_average=sum(plus.values()) / max(len(plus), 1))
             if baseline:
                 record.update(bicubic_psnr=base, bicubic_average=sum(base.values()) / max(len(base), 1))
             with open(args.json, 'w') as f:
@@ -126,6 +137,8 @@ def parse_args(argv=None):
                     help='frames of any size: extend them at the bottom and right to the size multiple (4; 16 with --hr-in), crop the output')
     ap.add_argument('--tile', type=int, nargs=2, default=None, metavar=('TH', 'TW'), help='restore tile by tile (input pixels, multiples of the size multiple)')
     ap.add_argument('--tile-overlap', type=int, default=None, help='input pixels neighbouring tiles share (default 8 x the size multiple)')
+    ap.add_argument('--self-ensemble', default=None, choices=['flip4', 'd4'],
+                    help='also restore under the 4 flips / the 8 symmetries of the square and average; reported beside the plain PSNR (n x the time)')
     args = ap.parse_args(argv)
     if (args.lq is None) == (args.lq_from_gt is None):
         ap.error('give exactly one of --lq and --lq-from-gt')
