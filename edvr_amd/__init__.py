@@ -17,6 +17,6 @@ from .data import bd_shape, duf_downsample, imresize, imresize_shape  # noqa: F4
 from .dcn import (DeformConv, DeformConvFunction, DeformConvPack, ModulatedDeformConv,  # noqa: F401
                   ModulatedDeformConvFunction, ModulatedDeformConvPack, deform_conv, modulated_deform_conv)
 from .edvr_arch import EDVR, PCDAlignment, PredeblurModule, TSAFusion  # noqa: F401
-from .video import VideoRestorer, WindowSchedule, ensemble_elements, tile_grid, window_table  # noqa: F401
+from .video import VideoRestorer, WindowSchedule, ensemble_elements, tile_bands, tile_grid, window_table  # noqa: F401
 
 __version__ = '0.1.0'

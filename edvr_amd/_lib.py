@@ -78,6 +78,10 @@ PROTOTYPES = {
     'edvr_upsample4x_add_rect_d4_u8': (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i64, i64, i64, i64, i64, i32, i32, f32, vp]),
     'edvr_f32_to_u8_hwc_rect_d4': (i32, [vp, vp, vp, i32, i32, i32, i64, i32, i32, i32, i32, i64, i64, i64, i64, i64, i32, i32, f32, vp]),
     'edvr_copy_rect_d4_f32': (i32, [vp, vp, i32, i32, i32, i64, i32, i32, i32, i32, i64, i64, i64, i32, i32, f32, vp]),
+    'edvr_upsample4x_add_rect_blend_f32': (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i64, i64, i64, i32, i32, f32, i32, i32, i32, i32, vp]),
+    'edvr_upsample4x_add_rect_blend_u8': (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i64, i64, i64, i64, i64, i32, i32, f32, i32, i32, i32, i32, vp]),
+    'edvr_f32_to_u8_hwc_rect_blend': (i32, [vp, vp, vp, i32, i32, i32, i64, i32, i32, i32, i32, i64, i64, i64, i64, i64, i32, i32, f32, i32, i32, i32, i32, vp]),
+    'edvr_copy_rect_blend_f32': (i32, [vp, vp, i32, i32, i32, i64, i32, i32, i32, i32, i64, i64, i64, i32, i32, f32, i32, i32, i32, i32, vp]),
     'edvr_imresize_bicubic_u8': (i32, [vp, vp, i32, i32, i32, i32, i32, ctypes.c_double, i32, i32, vp]),
     'edvr_imresize_bicubic_f32': (i32, [vp, vp, i32, i32, i32, i64, i32, i32, ctypes.c_double, i32, i32, vp]),
     'edvr_bd_downsample_u8': (i32, [vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]),

@@ -4,6 +4,7 @@
 //
 //   edvr_crop_pad_frames_d4_*   the rectangle edvr_crop_pad_frames_* delivers, as the dense tile g_k(rectangle)
 //   edvr_*_rect_d4_*            the four rectangle tails of video.hip storing g_k^-1(tile result), accumulating over the elements
+//   edvr_*_rect_blend_*         the same four tails cross-fading neighbouring tiles over a band around each cut (BLEND below)
 //
 // Element k = 4 t + 2 v + h on the last two axes:  g_k(x) = x.transpose(-1, -2) if t; then .flip(-2) if v; then .flip(-1) if h.
 // Both directions are ONE index map between a pixel (r, q) of the frame's orientation and (i, j) of the transformed (R, C) image:
@@ -174,6 +175,7 @@ struct RectArgs {
   int a_vec, d_vec;                             // 16-byte accesses to acc / three-dword stores to dst allowed
   int elem, mode;
   float scale;
+  int by0, by1, bx0, bx1;                       // BLEND: low / high band lengths of the rectangle per axis, output pixels (0: no band)
 };
 
 // what a launch leaves for one pixel: first -> value; else acc + value; last -> that times scale
@@ -182,20 +184,54 @@ __device__ __forceinline__ float accumulate(float value, float acc, int mode, fl
   return (mode & MODE_LAST) ? __fmul_rn(s, scale) : s;
 }
 
+// ---- BLEND (tile_blend of edvr_amd/video.py): the rectangle is a tile's EXTENDED rectangle, whose first by0 / bx0 and last by1 / bx1 rows
+// / columns are bands it shares with the neighbouring tile on that side.  The j-th pixel of a band of B has weight r(j) = fl((2 j + 1) /
+// (2 B)) (IEEE division) for the higher-index tile and fl(1 - r(j)) for the lower-index one, 1 outside the bands; w = fl(w_y * w_x).
+// A pixel in a low band has an earlier contributor (this launch is not its first), one in a high band a later one (not its last).
+__device__ __forceinline__ float axis_weight(int p, int len, int lo, int hi, bool &first, bool &last) {
+  if (p < lo) {
+    first = false;
+    return (float)(2 * p + 1) / (float)(2 * lo);
+  }
+  if (p >= len - hi) {
+    last = false;
+    return 1.f - (float)(2 * (p - (len - hi)) + 1) / (float)(2 * hi);
+  }
+  return 1.f;
+}
+
+// first -> w * value; else acc + w * value; last -> that times scale.  The product is rounded on its own: the empty asm keeps
+// -ffp-contract=fast from fusing it into the add (__fmul_rn is a plain `*` to the compiler).
+__device__ __forceinline__ float accumulate_weighted(float value, float w, float acc, int mode, float scale) {
+  float p = __fmul_rn(w, value);
+  asm volatile("" : "+v"(p));
+  return accumulate(p, acc, mode, scale);
+}
+
 // t = 0.  VEC (kx % 4 == 0, kw % 4 == 0, 16-byte aligned rows of y): thread = 4 consecutive pixels of a kept DESTINATION row = one
-// 16-byte load of y per channel at the mirrored group, reversed under h.
-template <bool UP, bool U8, bool VEC>
+// 16-byte load of y per channel at the mirrored group, reversed under h.  BLEND + VEC: bx0 and bx1 are multiples of 4 as well, so that
+// the four pixels of a group agree on first / last.
+template <bool UP, bool U8, bool VEC, bool BLEND>
 __global__ __launch_bounds__(256) void rect_flip_kernel(const RectArgs a) {
   constexpr int P = VEC ? 4 : 1;
   const int hy = UP ? 4 * a.h : a.h, wy = UP ? 4 * a.w : a.w;
   const int hf = a.elem & 1, vf = a.elem & 2;
   const int wq = a.kw / P;
   const int64_t total = (int64_t)a.n * a.kh * wq, yplane = (int64_t)hy * wy;
-  const bool bytes = U8 && (a.mode & MODE_LAST);
   for (int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * 256) {
     const int q = (int)(idx % wq) * P;
     const int r = (int)((idx / wq) % a.kh);
     const int64_t img = idx / ((int64_t)wq * a.kh);
+    int mode = a.mode;  // of this thread's pixels
+    float wgt[P];
+    if constexpr (BLEND) {
+      bool first = true, last = true;
+      const float wr = axis_weight(r, a.kh, a.by0, a.by1, first, last);
+#pragma unroll
+      for (int i = 0; i < P; ++i) wgt[i] = __fmul_rn(wr, axis_weight(q + i, a.kw, a.bx0, a.bx1, first, last));
+      mode &= ~((first ? 0 : MODE_FIRST) | (last ? 0 : MODE_LAST));
+    }
+    const bool bytes = U8 && (mode & MODE_LAST);
     const int oy = vf ? hy - 1 - (a.ky + r) : a.ky + r;
     const int ox = hf ? wy - P - (a.kx + q) : a.kx + q;  // first y column of the group; destination pixel i <- column (hf ? ox + P - 1 - i : ox + i)
     float v[3][P];
@@ -216,7 +252,7 @@ __global__ __launch_bounds__(256) void rect_flip_kernel(const RectArgs a) {
       }
       float *ap = a.acc + img * a.a_img + c * a.a_plane + (int64_t)r * a.a_row + q;
       float old[P];
-      if (!(a.mode & MODE_FIRST)) {
+      if (!(mode & MODE_FIRST)) {
         if (VEC && a.a_vec) {
           const f32x4 t = *reinterpret_cast<const f32x4 *>(ap);
 #pragma unroll
@@ -230,7 +266,10 @@ __global__ __launch_bounds__(256) void rect_flip_kernel(const RectArgs a) {
         for (int i = 0; i < P; ++i) old[i] = 0.f;
       }
 #pragma unroll
-      for (int i = 0; i < P; ++i) v[c][i] = accumulate(v[c][i], old[i], a.mode, a.scale);
+      for (int i = 0; i < P; ++i) {
+        if constexpr (BLEND) v[c][i] = accumulate_weighted(v[c][i], wgt[i], old[i], mode, a.scale);
+        else v[c][i] = accumulate(v[c][i], old[i], mode, a.scale);
+      }
       if (bytes) {
 #pragma unroll
         for (int i = 0; i < P; ++i) v[c][i] = to_u8(v[c][i]);
@@ -260,7 +299,7 @@ __global__ __launch_bounds__(256) void rect_flip_kernel(const RectArgs a) {
 // frame's orientation = y's (i, j) with i = v ? hy - 1 - (kx + q) : kx + q and j = h ? wy - 1 - (ky + r) : ky + r.  Value side: lanes
 // along y's rows (the destination's r, mirrored under h so that j ascends with the lane) compute the value -> lds[q][r].  Accumulator
 // side: lanes along the destination's rows read lds[q][r] column-wise and do the read-modify-write (or the byte store) there.
-template <bool UP, bool U8>
+template <bool UP, bool U8, bool BLEND>
 __global__ __launch_bounds__(256) void rect_transpose_kernel(const RectArgs a) {
   __shared__ float lds[3][TS * TP];
   const int hy = UP ? 4 * a.h : a.h, wy = UP ? 4 * a.w : a.w;
@@ -289,17 +328,26 @@ __global__ __launch_bounds__(256) void rect_transpose_kernel(const RectArgs a) {
   __syncthreads();
   {
     const int q = q0 + lane;
-    const bool bytes = U8 && (a.mode & MODE_LAST);
 #pragma unroll
     for (int p = 0; p < 4; ++p) {
       const int rl = grp + 8 * p, r = r0 + rl;
       if (r < a.kh && q < a.kw) {
+        int mode = a.mode;
+        float wgt = 1.f;
+        if constexpr (BLEND) {
+          bool first = true, last = true;
+          const float wr = axis_weight(r, a.kh, a.by0, a.by1, first, last);
+          wgt = __fmul_rn(wr, axis_weight(q, a.kw, a.bx0, a.bx1, first, last));
+          mode &= ~((first ? 0 : MODE_FIRST) | (last ? 0 : MODE_LAST));
+        }
+        const bool bytes = U8 && (mode & MODE_LAST);
         float v[3];
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
           float *ap = a.acc + img * a.a_img + c * a.a_plane + (int64_t)r * a.a_row + q;
-          const float old = (a.mode & MODE_FIRST) ? 0.f : ap[0];
-          v[c] = accumulate(lds[c][lane * TP + rl], old, a.mode, a.scale);
+          const float old = (mode & MODE_FIRST) ? 0.f : ap[0];
+          if constexpr (BLEND) v[c] = accumulate_weighted(lds[c][lane * TP + rl], wgt, old, mode, a.scale);
+          else v[c] = accumulate(lds[c][lane * TP + rl], old, mode, a.scale);
           if (!bytes) ap[0] = v[c];
         }
         if (bytes) {
@@ -348,14 +396,25 @@ static int crop_pad_launch(bool u8, const void *src, float *dst, int n, int H, i
   return check_launch(name);
 }
 
-template <bool UP, bool U8>
+struct Bands {
+  int y0, y1, x0, x1;
+};
+
+template <bool UP, bool U8, bool BLEND = false>
 static int rect_launch(const char *name, const float *y, const float *base, float *acc, uint8_t *dst, int n, int h, int w, int64_t y_img_stride,
                        int ky, int kx, int kh, int kw, int64_t a_row, int64_t a_plane, int64_t a_img, int64_t d_row, int64_t d_img, int elem, int mode,
-                       float scale, edvr_stream_t stream) {
+                       float scale, edvr_stream_t stream, Bands bands = Bands{0, 0, 0, 0}) {
   const int hy = UP ? 4 * h : h, wy = UP ? 4 * w : w;
   EDVR_REQUIRE(elem >= 0 && elem < 8 && mode >= 0 && mode <= (MODE_FIRST | MODE_LAST), "%s: element %d, mode %d", name, elem, mode);
   const int fh = (elem & 4) ? wy : hy, fw = (elem & 4) ? hy : wy;  // the result in the frame's orientation
   const bool bytes = U8 && (mode & MODE_LAST);
+  if (BLEND) {  // every band has the one width B, the bands of an axis do not meet
+    const int B = std::max(std::max(bands.y0, bands.y1), std::max(bands.x0, bands.x1));
+    const auto ok = [B](int v) { return v == 0 || v == B; };
+    EDVR_REQUIRE(ok(bands.y0) && ok(bands.y1) && ok(bands.x0) && ok(bands.x1) && B >= 0 && (int64_t)bands.y0 + bands.y1 <= kh &&
+                     (int64_t)bands.x0 + bands.x1 <= kw,
+                 "%s: bands (%d, %d, %d, %d) of a %d x %d rectangle", name, bands.y0, bands.y1, bands.x0, bands.x1, kh, kw);
+  }
   EDVR_REQUIRE(y && (base || !UP) && acc && (dst || !bytes) && n > 0 && h > 0 && w > 0 && ky >= 0 && kx >= 0 && kh > 0 && kw > 0 && ky + kh <= fh &&
                    kx + kw <= fw && (n == 1 || y_img_stride >= 3 * (int64_t)hy * wy) && a_row >= kw && a_plane >= (kh - 1) * a_row + kw &&
                    (n == 1 || a_img >= 2 * a_plane + (kh - 1) * a_row + kw) &&
@@ -365,18 +424,19 @@ static int rect_launch(const char *name, const float *y, const float *base, floa
   a.y = y, a.base = base, a.acc = acc, a.dst = dst, a.y_img_stride = y_img_stride, a.a_row = a_row, a.a_plane = a_plane, a.a_img = a_img;
   a.d_row = d_row, a.d_img = d_img, a.n = n, a.h = h, a.w = w, a.ky = ky, a.kx = kx, a.kh = kh, a.kw = kw;
   a.elem = elem, a.mode = mode, a.scale = scale;
+  a.by0 = bands.y0, a.by1 = bands.y1, a.bx0 = bands.x0, a.bx1 = bands.x1;
   a.a_vec = aligned_to(acc, 16) && a_row % 4 == 0 && a_plane % 4 == 0 && a_img % 4 == 0;
   a.d_vec = bytes && aligned_to(dst, 4) && d_row % 4 == 0 && d_img % 4 == 0;
   if (elem & 4) {
     const int64_t tiles = cdiv64(kh, TS) * cdiv64(kw, TS);
     EDVR_REQUIRE(tiles <= 0x7fffffff && n <= 65535, "%s: %lld tiles of %d images do not fit one grid", name, (long long)tiles, n);
-    hipLaunchKernelGGL((rect_transpose_kernel<UP, U8>), dim3((unsigned)tiles, (unsigned)n), dim3(256), 0, as_stream(stream), a);
+    hipLaunchKernelGGL((rect_transpose_kernel<UP, U8, BLEND>), dim3((unsigned)tiles, (unsigned)n), dim3(256), 0, as_stream(stream), a);
     return check_launch(name);
   }
-  const bool vec = kx % 4 == 0 && kw % 4 == 0 && wy % 4 == 0 && y_img_stride % 4 == 0 && aligned_to(y, 16);
+  const bool vec = kx % 4 == 0 && kw % 4 == 0 && wy % 4 == 0 && y_img_stride % 4 == 0 && aligned_to(y, 16) && bands.x0 % 4 == 0 && bands.x1 % 4 == 0;
   const dim3 grid(grid_blocks((int64_t)n * kh * (vec ? kw / 4 : kw)));
-  if (vec) hipLaunchKernelGGL((rect_flip_kernel<UP, U8, true>), grid, dim3(256), 0, as_stream(stream), a);
-  else hipLaunchKernelGGL((rect_flip_kernel<UP, U8, false>), grid, dim3(256), 0, as_stream(stream), a);
+  if (vec) hipLaunchKernelGGL((rect_flip_kernel<UP, U8, true, BLEND>), grid, dim3(256), 0, as_stream(stream), a);
+  else hipLaunchKernelGGL((rect_flip_kernel<UP, U8, false, BLEND>), grid, dim3(256), 0, as_stream(stream), a);
   return check_launch(name);
 }
 
@@ -421,4 +481,39 @@ extern "C" int edvr_copy_rect_d4_f32(const float *x, float *acc, int n, int h, i
                                      edvr_stream_t stream) {
   return edvr::d4::rect_launch<false, false>("copy_rect_d4_f32", x, nullptr, acc, nullptr, n, h, w, x_img_stride, ky, kx, kh, kw, acc_row_stride,
                                              acc_plane_stride, acc_img_stride, 0, 0, elem, mode, scale, stream);
+}
+
+extern "C" int edvr_upsample4x_add_rect_blend_f32(const float *y, const float *base, float *acc, int n, int h, int w, int ky, int kx, int kh,
+                                                  int kw, int64_t acc_row_stride, int64_t acc_plane_stride, int64_t acc_img_stride, int elem,
+                                                  int mode, float scale, int band_y_lo, int band_y_hi, int band_x_lo, int band_x_hi,
+                                                  edvr_stream_t stream) {
+  return edvr::d4::rect_launch<true, false, true>("upsample4x_add_rect_blend_f32", y, base, acc, nullptr, n, h, w, 48 * (int64_t)h * w, ky, kx, kh,
+                                                  kw, acc_row_stride, acc_plane_stride, acc_img_stride, 0, 0, elem, mode, scale, stream,
+                                                  edvr::d4::Bands{band_y_lo, band_y_hi, band_x_lo, band_x_hi});
+}
+
+extern "C" int edvr_upsample4x_add_rect_blend_u8(const float *y, const float *base, float *acc, uint8_t *dst, int n, int h, int w, int ky, int kx,
+                                                 int kh, int kw, int64_t acc_row_stride, int64_t acc_plane_stride, int64_t acc_img_stride,
+                                                 int64_t dst_row_stride, int64_t dst_img_stride, int elem, int mode, float scale, int band_y_lo,
+                                                 int band_y_hi, int band_x_lo, int band_x_hi, edvr_stream_t stream) {
+  return edvr::d4::rect_launch<true, true, true>("upsample4x_add_rect_blend_u8", y, base, acc, dst, n, h, w, 48 * (int64_t)h * w, ky, kx, kh, kw,
+                                                 acc_row_stride, acc_plane_stride, acc_img_stride, dst_row_stride, dst_img_stride, elem, mode,
+                                                 scale, stream, edvr::d4::Bands{band_y_lo, band_y_hi, band_x_lo, band_x_hi});
+}
+
+extern "C" int edvr_f32_to_u8_hwc_rect_blend(const float *x, float *acc, uint8_t *dst, int n, int h, int w, int64_t x_img_stride, int ky, int kx,
+                                             int kh, int kw, int64_t acc_row_stride, int64_t acc_plane_stride, int64_t acc_img_stride,
+                                             int64_t dst_row_stride, int64_t dst_img_stride, int elem, int mode, float scale, int band_y_lo,
+                                             int band_y_hi, int band_x_lo, int band_x_hi, edvr_stream_t stream) {
+  return edvr::d4::rect_launch<false, true, true>("f32_to_u8_hwc_rect_blend", x, nullptr, acc, dst, n, h, w, x_img_stride, ky, kx, kh, kw,
+                                                  acc_row_stride, acc_plane_stride, acc_img_stride, dst_row_stride, dst_img_stride, elem, mode,
+                                                  scale, stream, edvr::d4::Bands{band_y_lo, band_y_hi, band_x_lo, band_x_hi});
+}
+
+extern "C" int edvr_copy_rect_blend_f32(const float *x, float *acc, int n, int h, int w, int64_t x_img_stride, int ky, int kx, int kh, int kw,
+                                        int64_t acc_row_stride, int64_t acc_plane_stride, int64_t acc_img_stride, int elem, int mode, float scale,
+                                        int band_y_lo, int band_y_hi, int band_x_lo, int band_x_hi, edvr_stream_t stream) {
+  return edvr::d4::rect_launch<false, false, true>("copy_rect_blend_f32", x, nullptr, acc, nullptr, n, h, w, x_img_stride, ky, kx, kh, kw,
+                                                   acc_row_stride, acc_plane_stride, acc_img_stride, 0, 0, elem, mode, scale, stream,
+                                                   edvr::d4::Bands{band_y_lo, band_y_hi, band_x_lo, band_x_hi});
 }

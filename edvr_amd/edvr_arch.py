@@ -272,7 +272,7 @@ class EDVR(nn.Module):
         return [f1, f2, f3]
 
     def restore_from_features(self, pyr, x_center, b, t, out_dtype=torch.float32, out=None, keep=None, elem=None, accumulate='only', scale=1.0,
-                              acc=None):
+                              acc=None, bands=None):
         """Everything after the per-frame stage.  pyr = [f1, f2, f3]: the b * t window images of each level, clip after clip (image
         i * t + j = frame j of output frame i's window), x_center (b, c, H, W): the input frames the outputs are residuals of.
         out_dtype=torch.uint8 (no-grad calls only): the result as (b, H', W', 3) bytes with tensor2img semantics (clamp, x 255, round
@@ -284,7 +284,11 @@ class EDVR(nn.Module):
         are in the orientation g_elem of the frames, the last kernel stores g_elem^-1 of the result, keep and out being in the frames' own
         orientation, and accumulates: accumulate 'first' | 'middle' | 'last' | 'only' and scale as ops.upsample4x_add_rect_d4 defines
         them.  The float32 accumulator is `out` itself, or `acc` (the same rectangle of a float32 (b, 3, ., .) scratch) with uint8 output,
-        where only 'last' / 'only' writes `out`."""
+        where only 'last' / 'only' writes `out`.
+        bands (with out= only; passed only when tiles are blended - edvr_amd/video.py: tile_blend): (y low, y high, x low, x high), how
+        many of the first / last rows / columns of the rectangle are a band shared with a neighbouring tile (output pixels, the frames'
+        orientation).  The last kernel is then the weighted, accumulating tail ops.upsample4x_add_rect_blend defines (elem None: the
+        identity, element 0); with uint8 output `acc` is needed whether there is an ensemble or not."""
         if out_dtype not in (torch.float32, torch.uint8):
             raise ValueError(f'out_dtype must be torch.float32 or torch.uint8, got {out_dtype}')
         if out_dtype == torch.uint8 and torch.is_grad_enabled():
@@ -293,10 +297,10 @@ class EDVR(nn.Module):
             raise ValueError('keep= names a rectangle of the result to store into out=: it needs out')
         if out is not None and torch.is_grad_enabled():
             raise RuntimeError('EDVR.restore_from_features(out=) writes in place and has no backward: call it under torch.no_grad()')
-        if elem is None and (accumulate != 'only' or scale != 1.0 or acc is not None):
+        if elem is None and (accumulate != 'only' or scale != 1.0 or (acc is not None and bands is None)):
             raise ValueError('accumulate=, scale= and acc= belong to a self-ensemble element: they need elem')
-        if elem is not None and (out is None or (out_dtype == torch.uint8) != (acc is not None)):
-            raise ValueError('elem= stores into out= (and, with uint8 output, accumulates in acc=)')
+        if (elem is not None or bands is not None) and (out is None or (out_dtype == torch.uint8) != (acc is not None)):
+            raise ValueError('elem= and bands= store into out= (and, with uint8 output, accumulate in acc=)')
         f1, f2, f3 = pyr
         dst = out
         ctr = self.center_frame_idx
@@ -326,7 +330,17 @@ class EDVR(nn.Module):
         out = F_.conv(self.conv_hr, out, act=LRELU)
         if dst is not None:  # the same values, the last kernel storing the kept rectangle into the caller's tensor
             ky, kx = keep if keep is not None else (0, 0)
-            if elem is not None:  # self-ensemble: the oriented, accumulating forms of the same four tails (csrc/ensemble.hip)
+            if bands is not None:  # blended tiles: the weighted forms of the oriented, accumulating tails (csrc/ensemble.hip)
+                how = dict(bands=bands, elem=0 if elem is None else elem, mode=accumulate, scale=scale)
+                if self.hr_in:
+                    last = F_.conv(self.conv_last, out, res1=x_center)
+                    out = (F_.ops.f32_to_u8_hwc_rect_blend(last, dst, acc, ky, kx, **how) if acc is not None
+                           else F_.ops.copy_rect_blend(last, dst, ky, kx, **how))
+                else:
+                    last = F_.conv(self.conv_last, out)
+                    out = (F_.ops.upsample4x_add_u8_rect_blend(last, x_center, dst, acc, ky, kx, **how) if acc is not None
+                           else F_.ops.upsample4x_add_rect_blend(last, x_center, dst, ky, kx, **how))
+            elif elem is not None:  # self-ensemble: the oriented, accumulating forms of the same four tails (csrc/ensemble.hip)
                 how = dict(elem=elem, mode=accumulate, scale=scale)
                 if self.hr_in:
                     last = F_.conv(self.conv_last, out, res1=x_center)

@@ -1611,6 +1611,98 @@ def copy_rect_d4(x, out, ky=0, kx=0, elem=0, mode='only', scale=1.0):
     return out
 
 
+# ------------------------------------------------------------------------------------------------ tile blending (csrc/ensemble.hip)
+def _bands(bands, kh, kw):
+    """(low, high band lengths of the rows; low, high of the columns) of a rectangle, output pixels: each 0 or the one width B."""
+    try:
+        vals = tuple(bands)
+    except TypeError:
+        vals = ()
+    if len(vals) != 4 or any(isinstance(v, bool) or not isinstance(v, int) or v < 0 for v in vals):
+        raise ValueError(f'bands are four non-negative integers (y low, y high, x low, x high), got {bands!r}')
+    B = max(vals)
+    if any(v not in (0, B) for v in vals):
+        raise ValueError(f'every band has the same width: each of {vals} must be 0 or {B}')
+    if vals[0] + vals[1] > kh or vals[2] + vals[3] > kw:
+        raise ValueError(f'the bands {vals} of an axis overlap inside a {kh} x {kw} rectangle')
+    return vals
+
+
+def upsample4x_add_rect_blend(y, base, out, ky=0, kx=0, bands=(0, 0, 0, 0), elem=0, mode='only', scale=1.0):
+    """upsample4x_add_rect_d4 with a weight per pixel: `out` (ky, kx, kh, kw) is a tile's extended rectangle, bands = (y low, y high, x
+    low, x high) how many of its first / last rows / columns are a band of B output pixels shared with the neighbouring tile.  Weight of
+    band pixel j: r(j) = float32(2 j + 1) / float32(2 B) in a low band, 1 - r(j) in a high band, 1 elsewhere; w = w_y * w_x.  A pixel in no
+    low band with 'first' / 'only': out = w * value, else out = out + w * value; in no high band with 'last' / 'only': that times scale
+    (include/edvr_amd.h: edvr_*_rect_blend_*)."""
+    require_gpu(y, base)
+    base = base.contiguous()
+    n, c, h, w = base.shape
+    if c != 3:
+        raise NotImplementedError(f'the rectangle stores are for RGB images: 3 channels, got {c}')
+    assert y.is_contiguous() and tuple(y.shape) == (n, c, 4 * h, 4 * w)
+    k, bits, scale, (fh, fw) = _d4_tail(elem, mode, scale, 4 * h, 4 * w)
+    kh, kw, row, plane, img = _rect_dst(out, n, fh, fw, ky, kx, False)
+    bd = _bands(bands, kh, kw)
+    _run('upsample4x_add_rect_blend', lambda: _lib.check(_lib.lib().edvr_upsample4x_add_rect_blend_f32(
+        _ptr(y), _ptr(base), _ptr(out), n, h, w, int(ky), int(kx), kh, kw, row, plane, img, k, bits, scale, *bd, _stream()),
+        'edvr_upsample4x_add_rect_blend_f32'), 0, _nb(base) + 36.0 * n * kh * kw)
+    void_bound(out)
+    return out
+
+
+def upsample4x_add_u8_rect_blend(y, base, out, acc, ky=0, kx=0, bands=(0, 0, 0, 0), elem=0, mode='only', scale=1.0):
+    """The byte form: `acc` (the float32 rectangle of a scratch that goes with the uint8 rectangle `out`) accumulates as in
+    upsample4x_add_rect_blend; a pixel's last contributor stores the tensor2img bytes of its result into `out` instead."""
+    require_gpu(y, base)
+    base = base.contiguous()
+    n, c, h, w = base.shape
+    if c != 3:
+        raise NotImplementedError(f'the uint8 output is interleaved RGB: 3 channels, got {c}')
+    assert y.is_contiguous() and tuple(y.shape) == (n, c, 4 * h, 4 * w)
+    k, bits, scale, (fh, fw) = _d4_tail(elem, mode, scale, 4 * h, 4 * w)
+    kh, kw, row, _, img = _rect_dst(out, n, fh, fw, ky, kx, True)
+    a_row, a_plane, a_img = _d4_acc(acc, out, n, fh, fw, ky, kx)
+    bd = _bands(bands, kh, kw)
+    _run('upsample4x_add_u8_rect_blend', lambda: _lib.check(_lib.lib().edvr_upsample4x_add_rect_blend_u8(
+        _ptr(y), _ptr(base), _ptr(acc), _ptr(out), n, h, w, int(ky), int(kx), kh, kw, a_row, a_plane, a_img, row, img, k, bits, scale, *bd, _stream()),
+        'edvr_upsample4x_add_rect_blend_u8'), 0, _nb(base) + 36.0 * n * kh * kw)
+    return out
+
+
+def f32_to_u8_hwc_rect_blend(x, out, acc, ky=0, kx=0, bands=(0, 0, 0, 0), elem=0, mode='only', scale=1.0):
+    """f32_to_u8_hwc_rect_d4 with the weights of upsample4x_add_rect_blend, accumulating in `acc` as upsample4x_add_u8_rect_blend does."""
+    require_gpu(x)
+    x = _as_planes(x)
+    n, c, h, w = x.shape
+    if c != 3:
+        raise NotImplementedError(f'the uint8 output is interleaved RGB: 3 channels, got {c}')
+    k, bits, scale, (fh, fw) = _d4_tail(elem, mode, scale, h, w)
+    kh, kw, row, _, img = _rect_dst(out, n, fh, fw, ky, kx, True)
+    a_row, a_plane, a_img = _d4_acc(acc, out, n, fh, fw, ky, kx)
+    bd = _bands(bands, kh, kw)
+    _run('f32_to_u8_hwc_rect_blend', lambda: _lib.check(_lib.lib().edvr_f32_to_u8_hwc_rect_blend(
+        _ptr(x), _ptr(acc), _ptr(out), n, h, w, _img_stride(x), int(ky), int(kx), kh, kw, a_row, a_plane, a_img, row, img, k, bits, scale, *bd, _stream()),
+        'edvr_f32_to_u8_hwc_rect_blend'), 0, 36.0 * n * kh * kw)
+    return out
+
+
+def copy_rect_blend(x, out, ky=0, kx=0, bands=(0, 0, 0, 0), elem=0, mode='only', scale=1.0):
+    """copy_rect_d4 with the weights of upsample4x_add_rect_blend, accumulating in the float32 rectangle `out`."""
+    require_gpu(x)
+    x = _as_planes(x)
+    n, c, h, w = x.shape
+    if c != 3:
+        raise NotImplementedError(f'the rectangle stores are for RGB images: 3 channels, got {c}')
+    k, bits, scale, (fh, fw) = _d4_tail(elem, mode, scale, h, w)
+    kh, kw, row, plane, img = _rect_dst(out, n, fh, fw, ky, kx, False)
+    bd = _bands(bands, kh, kw)
+    _run('copy_rect_blend', lambda: _lib.check(_lib.lib().edvr_copy_rect_blend_f32(
+        _ptr(x), _ptr(out), n, h, w, _img_stride(x), int(ky), int(kx), kh, kw, row, plane, img, k, bits, scale, *bd, _stream()), 'edvr_copy_rect_blend_f32'),
+         0, 36.0 * n * kh * kw)
+    void_bound(out)
+    return out
+
+
 # ------------------------------------------------------------------------------------------------ bicubic imresize (csrc/resize.hip)
 def imresize(frames, scale, antialiasing=True, out_dtype=torch.float32):
     """MATLAB-style bicubic imresize (basicsr/utils/matlab_functions.py:88-170) of a batch of frames in ONE launch, weights computed in

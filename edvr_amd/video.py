@@ -10,8 +10,9 @@ reconstruction (`EDVR.restore_from_features`) see exactly the tensors a `forward
 Frames of ANY size (`pad_mode`, `tile`): the frame is extended at the bottom and right to the network's size multiple and covered by
 equal tiles (`tile_grid`); the per-frame stage reads tiles straight from the caller's frames (ops.crop_pad_frames: crop, pad and the
 byte conversion in one launch), every tile has a bank of its own, and the last kernel of each tile's restore pass stores the KEPT
-rectangle of its result into the chunk's full-frame output (the `*_rect` tails of csrc/video.hip).  No blending: inside its kept
-rectangle a tile's result is final, and equals what the plain path computes on that tile's crop.
+rectangle of its result into the chunk's full-frame output (the `*_rect` tails of csrc/video.hip).  By default nothing is blended:
+inside its kept rectangle a tile's result is final, and equals what the plain path computes on that tile's crop.  `tile_blend` cross-fades
+neighbouring tiles over a band around each cut instead (`tile_bands`; the `*_rect_blend` tails of csrc/ensemble.hip).
 
 Self-ensemble (`self_ensemble`): the video is restored under each of up to eight symmetries of the square, the symmetry is undone and
 the results are averaged.  A symmetry is the same shape of work as a tile - the per-frame stage reads an ORIENTED crop
@@ -112,6 +113,60 @@ def tile_grid(H, W, tile=None, overlap=None, multiple=4):
     th, tw = min(th, Hp), min(tw, Wp)
     return [Tile((y0, x0, th, tw), (ky, kx, kh, kw), (y0 + ky, x0 + kx))
             for y0, ky, kh in _tile_axis(H, Hp, th, overlap, m) for x0, kx, kw in _tile_axis(W, Wp, tw, overlap, m)]
+
+
+TileBlend = namedtuple('TileBlend', 'ext dst bands')
+TileBlend.__doc__ = """ext = (ey, ex, eh, ew): the EXTENDED rectangle inside the tile - its kept rectangle plus half a band into each neighbouring
+band; dst = (oy, ox): where it lies in the frame; bands = (y low, y high, x low, x high): how many of its first / last rows / columns are
+a band shared with the lower- / higher-index neighbour, each 0 or the blend width.  Input pixels throughout."""
+
+
+def _blend_axis(axis, size, tile, b, name):
+    """One axis of tile_bands: `axis` = _tile_axis' [(origin, first kept, kept count)] of tiles of `tile` -> [(first, count, low band,
+    high band)] of the extended parts, relative to the tile, after checking that the bands [cut - b / 2, cut + b / 2) are disjoint and
+    lie inside the frame."""
+    half, count = b // 2, len(axis)
+    cuts = [o + k0 for o, k0, _ in axis] + [size]  # cuts[0] = 0; cuts[1 ... count - 1] are the interior ones
+    for i in range(1, count):
+        if cuts[i + 1] - cuts[i] < (b if i + 1 < count else half) or cuts[i] - cuts[i - 1] < (b if i > 1 else half):
+            raise ValueError(f'tile_blend {b}: the {name} cuts {cuts[1:count]} of a frame of {size} leave kept lengths '
+                             f'{[cuts[j + 1] - cuts[j] for j in range(count)]}; bands of {b} around the cuts need at least {b} between two '
+                             f'cuts and {half} before the first and after the last (a larger tile, a smaller overlap or a smaller tile_blend)')
+    out = []
+    for i, (o, k0, kn) in enumerate(axis):
+        lo, hi = (b if i > 0 else 0), (b if i + 1 < count else 0)
+        first, n = k0 - lo // 2, kn + lo // 2 + hi // 2
+        assert first >= 0 and first + n <= tile and lo + hi <= n, 'a band reaches outside a tile it blends'  # (b <= overlap)
+        out.append((first, n, lo, hi))
+    return out
+
+
+def tile_bands(H, W, tile=None, overlap=None, blend=None, multiple=4):
+    """The blending geometry that goes with tile_grid(H, W, tile, overlap, multiple) (pure Python): a list of TileBlend, tile by tile in
+    the grid's order.  blend = b: a positive multiple of 2 * multiple, at most the overlap.  Around every interior cut c of an axis lies
+    the band [c - b / 2, c + b / 2), inside both neighbouring tiles; a tile stores its kept rectangle extended by b / 2 into each
+    neighbouring band.  ValueError where two bands of an axis would meet or a band would leave the (H, W) frame - a kept length between
+    two cuts below b or an outer one below b / 2, which happens next to the inward-shifted last tile."""
+    m = int(multiple)
+    grid = tile_grid(H, W, tile, overlap, m)
+    if overlap is None:
+        overlap = 8 * m if tile is not None else 0
+    if isinstance(blend, bool) or not isinstance(blend, int) or blend <= 0 or blend % (2 * m):
+        raise ValueError(f'tile_blend {blend!r} must be a positive multiple of {2 * m}')
+    if blend > overlap:
+        raise ValueError(f'tile_blend {blend} must not exceed tile_overlap {overlap}')
+    Hp, Wp = _round_up(H, m), _round_up(W, m)
+    th, tw = grid[0].src[2:]
+    rows = _blend_axis(_tile_axis(H, Hp, th, overlap, m), H, th, blend, 'row')
+    cols = _blend_axis(_tile_axis(W, Wp, tw, overlap, m), W, tw, blend, 'column')
+    out = [TileBlend((ey, ex, eh, ew), None, (ylo, yhi, xlo, xhi)) for ey, eh, ylo, yhi in rows for ex, ew, xlo, xhi in cols]
+    return [tb._replace(dst=(t.src[0] + tb.ext[0], t.src[1] + tb.ext[1])) for t, tb in zip(grid, out)]
+
+
+def band_ramp(B, device=None):
+    """r(j), j = 0 ... B - 1: the weight of the higher-index tile across a band of B output pixels - the correctly rounded float32
+    quotient of float(2 j + 1) by float(2 B).  The lower-index tile has 1 - r(j) (a float32 subtraction)."""
+    return (2 * torch.arange(B, dtype=torch.float32, device=device) + 1) / torch.tensor(float(2 * B), dtype=torch.float32, device=device)
 
 
 class WindowSchedule:
@@ -233,10 +288,23 @@ class VideoRestorer:
     (tile x element), element innermost; windows, temporal padding and chunking are untouched (no temporal reversal).
     WHAT IT COSTS: n times the time of the plain path (every kernel of the network runs once per element; the new oriented reads and
     accumulating tails are bandwidth-sized) and n banks per tile (same ring, same capacity each), plus - with uint8 output - one
-    float32 (chunk, 3, s H, s W) accumulator that lives across chunks.  A transposing element runs the network on (W, H) frames."""
+    float32 (chunk, 3, s H, s W) accumulator that lives across chunks.  A transposing element runs the network on (W, H) frames.
+
+    tile_blend None | b (input pixels; needs tile; a positive multiple of 2 m, at most tile_overlap): neighbouring tiles are cross-faded
+    over a band instead of being cut.  Around every interior cut c of an axis lies the band [c - b / 2, c + b / 2) (`tile_bands`; bands
+    of an axis that would meet, or a band outside the frame, are a ValueError at the first frame); a tile stores its kept rectangle
+    extended by b / 2 into each neighbouring band.  With B = s b and j = 0 ... B - 1 the output pixel of a band in the frame's orientation,
+        r(j) = float32(2 j + 1) / float32(2 B)     the higher-index tile's weight; the lower-index tile has 1.0f - r(j); 1.0f off the bands
+        w = w_y * w_x                              (all float32, round to nearest; four tiles meet in a corner)
+    and over a pixel's contributors in work-list order (tiles row-major, element innermost), v being the float32 the unblended path
+    stores for that tile (and element) there,
+        acc = w * v;  acc = acc + w * v ...;  with an ensemble of n the last stores (acc + w * v) * (1 / n)
+    each product rounded before its add.  Without an ensemble a pixel outside every band is bit for bit the unblended tiled result.
+    No network work is added - the bands are computed by both tiles already; the tails turn from stores into read-modify-writes inside
+    the bands, and uint8 output keeps the float32 (chunk, 3, s H, s W) accumulator an ensemble needs."""
 
     def __init__(self, net, num_frame=None, padding='reflection_circle', chunk=8, out_dtype=torch.float32, pad_mode=None, tile=None,
-                 tile_overlap=None, self_ensemble=None):
+                 tile_overlap=None, self_ensemble=None, tile_blend=None):
         if out_dtype not in (torch.float32, torch.uint8):
             raise ValueError(f'out_dtype must be torch.float32 or torch.uint8, got {out_dtype}')
         if pad_mode not in (None, 'reflect', 'replicate'):
@@ -247,7 +315,11 @@ class VideoRestorer:
             tile = (int(tile[0]), int(tile[1]))
         elif tile_overlap is not None:
             raise ValueError('tile_overlap without tile')
-        self.pad_mode, self.tile, self.tile_overlap = pad_mode, tile, tile_overlap
+        if tile_blend is not None:
+            if tile is None:
+                raise ValueError('tile_blend without tile')
+            tile_bands(self.multiple, self.multiple, tile, tile_overlap, tile_blend, self.multiple)  # its argument errors now as well
+        self.pad_mode, self.tile, self.tile_overlap, self.tile_blend = pad_mode, tile, tile_overlap, tile_blend
         self.elements = ensemble_elements(self_ensemble)
         self.tiled = pad_mode is not None or tile is not None or self.elements is not None
         self.net, self.padding, self.chunk, self.out_dtype = net, padding, int(chunk), out_dtype
@@ -266,6 +338,7 @@ class VideoRestorer:
         self._groups = []       # (first frame, count, [bound or None per level], [depth per level]) of every extract call with live frames
         self._pieces = []       # (first frame, float32 (k, 3, H, W)) input frames not dead yet (tiled path: as they came, uint8 (k, H, W, 3) too)
         self.grid = None        # tiled path: [Tile] of the running restore, and per tile ...
+        self.blend_grid = None  # ... with tile_blend its TileBlend, ...
         self.pairs = None       # ... the work list [(Tile, element id or None)]: tile x element, element innermost, and per pair ...
         self.banks = None       # ... its [f1, f2, f3] rings
         self._tile_groups = None  # ... and its _groups
@@ -411,6 +484,7 @@ class VideoRestorer:
         if self.pad_mode == 'reflect' and (Hp - H > H - 1 or Wp - W > W - 1):
             raise ValueError(f"pad_mode='reflect' mirrors without repeating the edge: a frame of {H} x {W} is too small to be extended to {Hp} x {Wp}")
         self.grid = tile_grid(H, W, self.tile, self.tile_overlap, m)
+        self.blend_grid = None if self.tile_blend is None else tile_bands(H, W, self.tile, self.tile_overlap, self.tile_blend, m)
         th, tw = self.grid[0].src[2:]
         self.slots = self.capacity if length is None else max(1, min(self.capacity, length))
         self.pairs = [(tile, k) for tile in self.grid for k in (self.elements or (None,))]
@@ -435,7 +509,9 @@ class VideoRestorer:
         out = torch.empty((b, s * H, s * W, 3) if u8 else (b, 3, s * H, s * W), dtype=self.out_dtype, device=centre.device)
         table = self._slot_table([f % self.slots for r in rows for f in r], centre.device)
         n = len(self.elements) if self.elements is not None else 0
-        acc = self._scratch((b, 3, s * H, s * W), centre.device) if n and u8 else None  # uint8 output: the elements add up in float32
+        blend = self.blend_grid
+        # uint8 output: the elements (and blended tiles) add up in float32
+        acc = self._scratch((b, 3, s * H, s * W), centre.device) if (n or blend is not None) and u8 else None
         for i, ((tile, k), bank, groups) in enumerate(zip(self.pairs, self.banks, self._tile_groups)):
             net.check_offsets(wait=False)  # per tile (and element) what a forward does before its launches, as in _restore
             if bank[0].is_cuda:
@@ -443,12 +519,16 @@ class VideoRestorer:
             self._bank_bounds(bank, groups)
             pyr = self._gather(bank, table)
             (ky, kx, kh, kw), (oy, ox) = tile.keep, tile.dst
+            if blend is not None:  # the extended rectangle instead of the kept one
+                (ky, kx, kh, kw), (oy, ox), bands = blend[i // max(n, 1)]
             ys, xs = slice(s * oy, s * (oy + kh)), slice(s * ox, s * (ox + kw))
             how = {}
             if k is not None:  # the oriented, accumulating tail: the float32 output accumulates in place, the bytes in `acc`
                 e = i % n
                 how = dict(elem=k, accumulate='only' if n == 1 else 'first' if e == 0 else 'last' if e == n - 1 else 'middle', scale=1.0 / n,
                            acc=acc[:, :, ys, xs] if u8 else None)
+            if blend is not None:  # the weighted tail (identity element without an ensemble)
+                how.update(bands=tuple(s * v for v in bands), acc=acc[:, :, ys, xs] if u8 else None)
             net.restore_from_features(pyr, self._oriented(centre, tile, k), b, t, out_dtype=self.out_dtype,
                                       out=out[:, ys, xs] if u8 else out[:, :, ys, xs], keep=(s * ky, s * kx), **how)
         return out
@@ -471,7 +551,7 @@ class VideoRestorer:
         self._check_mode()
         self.schedule = sched = WindowSchedule(self.num_frame, self.padding, self.chunk, _probe=False)
         self.bank, self._groups, self._pieces = None, [], []
-        self.grid = self.pairs = self.banks = self._tile_groups = None
+        self.grid = self.blend_grid = self.pairs = self.banks = self._tile_groups = None
         try:
             for item in frames:
                 piece = self._as_frames(item)

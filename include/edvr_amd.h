@@ -546,6 +546,36 @@ int edvr_copy_rect_d4_f32(const float *x, float *acc, int n, int h, int w, int64
                           int64_t acc_row_stride, int64_t acc_plane_stride, int64_t acc_img_stride, int elem, int mode, float scale,
                           edvr_stream_t stream);
 
+/* Tile blending (edvr_amd/video.py: tile_blend) - csrc/ensemble.hip.  The four edvr_*_rect_d4_* tails above with a WEIGHT: neighbouring
+ * tiles are cross-faded over a band of B output pixels around each cut instead of being cut there.  (ky, kx, kh, kw) is the tile's
+ * EXTENDED rectangle (its kept rectangle plus half a band into each neighbour's side); band_y_lo / band_y_hi / band_x_lo / band_x_hi,
+ * each 0 or B, say how many of its first / last rows / columns are a band shared with the lower- / higher-index neighbour
+ * (band_y_lo + band_y_hi <= kh, band_x_lo + band_x_hi <= kw).  For the j-th pixel (j = 0 ... B - 1, frame's orientation) of a band,
+ * r(j) = float(2 j + 1) / float(2 B), the correctly rounded float32 quotient: the higher-index tile (whose LOW band it is) has weight
+ * r(j), the lower-index tile (whose HIGH band it is) 1.0f - r(j); outside the bands the weight of an axis is 1.0f; w = w_y * w_x.  All
+ * round-to-nearest float32 operations.  With value the float the _d4 tail (element 0: the plain tail) computes for the pixel:
+ *   p = w * value, rounded on its own (never fused into the add);
+ *   first contributor of the pixel: s = p; every later one: s = acc + p;  last contributor: s * scale is what is stored
+ * where "first" = the launch has EDVR_D4_FIRST and the pixel lies in none of the rectangle's low bands, "last" = the launch has
+ * EDVR_D4_LAST and the pixel lies in none of its high bands - per pixel, not per launch, so nothing has to be zeroed.  The byte tails
+ * store tensor2img bytes into dst for the pixels this launch is last for and the float into acc for all others.  Launches in work-list
+ * order (tiles row-major, element innermost) on one stream; one writer per pixel and launch, no atomics.  Without an ensemble: elem 0,
+ * mode EDVR_D4_FIRST | EDVR_D4_LAST, scale 1 (a multiply by 1.0f is exact). */
+int edvr_upsample4x_add_rect_blend_f32(const float *y, const float *base, float *acc, int n, int h, int w, int ky, int kx, int kh, int kw,
+                                       int64_t acc_row_stride, int64_t acc_plane_stride, int64_t acc_img_stride, int elem, int mode, float scale,
+                                       int band_y_lo, int band_y_hi, int band_x_lo, int band_x_hi, edvr_stream_t stream);
+int edvr_upsample4x_add_rect_blend_u8(const float *y, const float *base, float *acc, uint8_t *dst, int n, int h, int w, int ky, int kx, int kh,
+                                      int kw, int64_t acc_row_stride, int64_t acc_plane_stride, int64_t acc_img_stride, int64_t dst_row_stride,
+                                      int64_t dst_img_stride, int elem, int mode, float scale, int band_y_lo, int band_y_hi, int band_x_lo,
+                                      int band_x_hi, edvr_stream_t stream);
+int edvr_f32_to_u8_hwc_rect_blend(const float *x, float *acc, uint8_t *dst, int n, int h, int w, int64_t x_img_stride, int ky, int kx, int kh,
+                                  int kw, int64_t acc_row_stride, int64_t acc_plane_stride, int64_t acc_img_stride, int64_t dst_row_stride,
+                                  int64_t dst_img_stride, int elem, int mode, float scale, int band_y_lo, int band_y_hi, int band_x_lo,
+                                  int band_x_hi, edvr_stream_t stream);
+int edvr_copy_rect_blend_f32(const float *x, float *acc, int n, int h, int w, int64_t x_img_stride, int ky, int kx, int kh, int kw,
+                             int64_t acc_row_stride, int64_t acc_plane_stride, int64_t acc_img_stride, int elem, int mode, float scale,
+                             int band_y_lo, int band_y_hi, int band_x_lo, int band_x_hi, edvr_stream_t stream);
+
 /* MATLAB-style bicubic imresize on the device <- imresize / calculate_weights_indices (basicsr/utils/matlab_functions.py:88-170 and
  * 17-84; the Python statement of scripts/matlab_scripts/generate_bicubic_img.m, i.e. of "BI x4"): one launch resamples n frames by one
  * factor on both axes, rows first, then columns, accumulating in fp32.  Per axis, for the 1-based output x: u = x / scale + 0.5 (1 - 1 /

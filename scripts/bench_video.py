@@ -22,6 +22,11 @@ Self-ensemble (VideoRestorer self_ensemble), same method, merged into profiles/v
 
     python scripts/bench_video.py --self-ensemble flip4 --config L_T5 [--out-dtype uint8]   # frames/s against the plain path (~ 1 / n)
     python scripts/bench_video.py --self-ensemble d4 --config L_T5                          # and the new kernels' share of kernel time
+
+Tile blending (VideoRestorer tile_blend), same method, merged into profiles/video/bench_video_blend.json:
+
+    python scripts/bench_video.py --tile-blend 32 --config L_T5 [--out-dtype uint8]   # 544x960, 2x2 tiles: blended against unblended tiles,
+                                                                                      # the blend tails' share, the seam table both ways
 """
 import argparse
 import json
@@ -282,6 +287,64 @@ def leg_ensemble(args, net, kwargs, dev, frames, chunk):
             'max_abs_difference_to_plain_output': diff, **res}
 
 
+BLEND_KERNELS = ('upsample4x_add_rect_blend', 'upsample4x_add_u8_rect_blend', 'f32_to_u8_hwc_rect_blend', 'copy_rect_blend')
+
+
+def _seam_rows(out, ref, scale, cuts_y, cuts_x, width):
+    """leg_seam's numbers: max / mean |out - ref| / scale inside a band of `width` output pixels either side of the cuts, and outside."""
+    d = (out.float() - ref.float()).abs() / scale
+    band = torch.zeros(d.shape[-2], d.shape[-1], dtype=torch.bool, device=d.device)
+    for c in cuts_y:
+        band[max(c - width, 0):c + width] = True
+    for c in cuts_x:
+        band[:, max(c - width, 0):c + width] = True
+    inside, outside = d[..., band], d[..., ~band]
+    return {'band_output_pixels': width, 'band_max': inside.max().item(), 'band_mean': inside.mean().item(),
+            'outside_max': outside.max().item() if outside.numel() else None, 'outside_mean': outside.mean().item() if outside.numel() else None}
+
+
+def leg_blend(args, net, kwargs, dev, frames, chunk):
+    """tile_blend against the unblended tiled path with the SAME tiles (2 x 2 at the default overlap, the frame of --leg tiles): frames/s,
+    peak memory, the share of kernel time in the blend tails, and - float32 output - leg_seam's table for both against the untiled
+    result of a shorter structured video.  Blending adds no network launch: the expectation is a ratio of 1 within the arms' spread."""
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..', 'tests'))
+    from util_edvr import motion_frames
+    from edvr_amd import VideoRestorer, tile_grid
+    h, w = LEG_HW['tiles'][args.config]
+    m, s = (16, 1) if kwargs.get('hr_in') else (4, 4)
+    tile, ov = _default_2x2(h, w, m)
+    grid = tile_grid(h, w, tile, None, m)
+    dt = getattr(torch, args.out_dtype)
+    lq = torch.rand(frames, 3, h, w, generator=torch.Generator().manual_seed(0)).to(dev)
+    cut = VideoRestorer(net, padding=args.padding, chunk=chunk, out_dtype=dt, tile=tile)
+    blended = VideoRestorer(net, padding=args.padding, chunk=chunk, out_dtype=dt, tile=tile, tile_blend=args.tile_blend)
+    res, outs = _two_arms({'blended': lambda: blended.restore(lq), 'unblended': lambda: cut.restore(lq)}, frames, args.repeats, net)
+    tab = kernel_table(lambda: blended.restore(lq))
+    net.check_offsets()
+    new_ms = sum(r['ms'] for r in tab['kernels'] if r['name'] in BLEND_KERNELS)
+    ratio = res['blended']['frames_per_s'] / res['unblended']['frames_per_s']
+    del outs, lq
+    seam = None
+    if dt == torch.float32:  # the seam table of leg_seam: a short structured video, against the untiled result
+        n = min(frames, 12)
+        mv = motion_frames(1, (n, 3, h, w), seed=0)[0].to(dev)
+        ref = VideoRestorer(net, padding=args.padding, chunk=chunk).restore(mv)
+        scale = ref.abs().max().item()
+        cuts_y = sorted({s * t.dst[0] for t in grid if t.dst[0] > 0})
+        cuts_x = sorted({s * t.dst[1] for t in grid if t.dst[1] > 0})
+        seam = {'frames': n, 'input': 'util_edvr.motion_frames', 'output_scale': scale,
+                'weights': 'random init, conv_offset N(0, 0.02) / bias N(0, 0.5): not a trained model',
+                'unblended': _seam_rows(cut.restore(mv), ref, scale, cuts_y, cuts_x, s * ov),
+                'blended': _seam_rows(blended.restore(mv), ref, scale, cuts_y, cuts_x, s * ov)}
+        net.check_offsets()
+    return {'leg': 'blend', 'hw': [h, w], 'tile': list(tile), 'tile_overlap': ov, 'tile_blend': args.tile_blend, 'tiles': len(grid),
+            'ratio_blended_over_unblended_frames_per_s': round(ratio, 4),
+            'within_unblended_spread': bool(ratio >= 1.0 - res['unblended']['spread']),
+            'kernel_time_ratio_blended_over_unblended': round(res['blended']['kernel_ms'] / res['unblended']['kernel_ms'], 4),
+            'blend_tails_ms': round(new_ms, 3), 'blend_tails_share_of_kernel_time': round(new_ms / tab['kernel_ms'], 5),
+            'blend_tails': [r for r in tab['kernels'] if r['name'] in BLEND_KERNELS], 'seam': seam, **res}
+
+
 def main_leg(args):
     from edvr_amd import _lib
     from edvr_amd.build import source_hash
@@ -290,16 +353,17 @@ def main_leg(args):
     dev = torch.device('cuda:0')
     net = _build_net(kwargs, dev)
     with torch.no_grad():
-        legs = {'pad': leg_pad, 'tiles': leg_tiles, 'seam': leg_seam, 'large': leg_large, 'ensemble': leg_ensemble}
+        legs = {'pad': leg_pad, 'tiles': leg_tiles, 'seam': leg_seam, 'large': leg_large, 'ensemble': leg_ensemble, 'blend': leg_blend}
         result = legs[args.leg](args, net, kwargs, dev, frames, chunk)
     result = {'config': args.config, 'edvr': dict(kwargs), 'frames': frames, 'chunk': chunk, 'padding': args.padding, 'out_dtype': args.out_dtype,
               'repeats': args.repeats, **result, 'csrc_sha16': source_hash(), 'library': _lib.lib().edvr_version().decode(),
               'device': torch.cuda.get_device_name(0)}
-    default = 'bench_video_ensemble.json' if args.leg == 'ensemble' else 'bench_video_tiles.json'
+    default = {'ensemble': 'bench_video_ensemble.json', 'blend': 'bench_video_blend.json'}.get(args.leg, 'bench_video_tiles.json')
     path = os.path.abspath(args.json or os.path.join(os.path.dirname(os.path.abspath(__file__)), '..', 'profiles', 'video', default))
     os.makedirs(os.path.dirname(path), exist_ok=True)
     merged = json.load(open(path)) if os.path.exists(path) else {}
-    key = f'{args.self_ensemble}_{args.config}' if args.leg == 'ensemble' else f'{args.leg}_{args.config}'
+    key = (f'{args.self_ensemble}_{args.config}' if args.leg == 'ensemble' else f'blend{args.tile_blend}_{args.config}' if args.leg == 'blend'
+           else f'{args.leg}_{args.config}')
     merged[key + ('' if args.out_dtype == 'float32' else '_' + args.out_dtype)] = result
     with open(path, 'w') as f:
         json.dump(merged, f, indent=1, sort_keys=True)
@@ -319,7 +383,13 @@ def main():
     ap.add_argument('--leg', default=None, choices=['pad', 'tiles', 'seam', 'large'], help='frames of any size: pad_mode / tile measurements')
     ap.add_argument('--self-ensemble', default=None, choices=['flip4', 'd4'],
                     help='timing arm: self_ensemble against the plain VideoRestorer (profiles/video/bench_video_ensemble.json)')
+    ap.add_argument('--tile-blend', type=int, default=None, metavar='N',
+                    help='timing arm: tile_blend=N against the unblended tiled path, same 2 x 2 tiles (profiles/video/bench_video_blend.json)')
     args = ap.parse_args()
+    if args.tile_blend is not None:
+        if args.leg or args.self_ensemble:
+            ap.error('--tile-blend is a leg of its own: give it without --leg / --self-ensemble')
+        args.leg = 'blend'
     if args.self_ensemble:
         if args.leg:
             ap.error('--self-ensemble is a leg of its own: give it without --leg')

@@ -1,7 +1,8 @@
 """scripts/test_reds.py for the folder datasets (REDS4 / Vid4 layout) with every frame's features extracted ONCE per clip
 (metrics.validate_video on edvr_amd/video.py: VideoRestorer) instead of once per window the frame appears in.  Same options, same
 sharding of the clips over the ranks, same per-folder and overall averages; `--batch` is the number of output frames per alignment /
-fusion / reconstruction pass.  `--pad-mode reflect` admits frames of any size, `--tile TH TW` bounds the memory of large ones.
+fusion / reconstruction pass.  `--pad-mode reflect` admits frames of any size, `--tile TH TW` bounds the memory of large ones,
+`--tile-blend N` cross-fades neighbouring tiles over N input pixels around each cut (VideoRestorer's tile_blend).
 `--self-ensemble flip4|d4` also restores every clip under the 4 flips / the 8 symmetries of the square and averages (the "+" rows of
 the papers; VideoRestorer's self_ensemble, n times the time) and reports the plain and the ensemble PSNR side by side.
 
@@ -59,8 +60,9 @@ def evaluate(args, log=print):
             raise ValueError('either an LQ folder or lq_from_gt is needed')
         opt['lq_from_gt'] = dict(scale=lq_from_gt, quantize=True) if degradation == 'bi' else dict(scale=lq_from_gt, degradation=degradation)
     ds = VideoTestClips(opt, device=device)
-    # frames of any size (--pad-mode / --tile / --tile-overlap): passed on only where given
-    any_size = {k: (tuple(v) if k == 'tile' else v) for k in ('pad_mode', 'tile', 'tile_overlap') for v in [getattr(args, k, None)] if v is not None}
+    # frames of any size (--pad-mode / --tile / --tile-overlap / --tile-blend): passed on only where given
+    any_size = {k: (tuple(v) if k == 'tile' else v) for k in ('pad_mode', 'tile', 'tile_overlap', 'tile_blend')
+                for v in [getattr(args, k, None)] if v is not None}
     ensemble = getattr(args, 'self_ensemble', None)
     results, base, plus = {}, {}, {}
     for folder in ds.folders[rank::world]:
@@ -137,6 +139,9 @@ def parse_args(argv=None):
                     help='frames of any size: extend them at the bottom and right to the size multiple (4; 16 with --hr-in), crop the output')
     ap.add_argument('--tile', type=int, nargs=2, default=None, metavar=('TH', 'TW'), help='restore tile by tile (input pixels, multiples of the size multiple)')
     ap.add_argument('--tile-overlap', type=int, default=None, help='input pixels neighbouring tiles share (default 8 x the size multiple)')
+    ap.add_argument('--tile-blend', type=int, default=None, metavar='N',
+                    help='with --tile: cross-fade neighbouring tiles over N input pixels around each cut (a multiple of twice the size multiple, '
+                         'at most the overlap)')
     ap.add_argument('--self-ensemble', default=None, choices=['flip4', 'd4'],
                     help='also restore under the 4 flips / the 8 symmetries of the square and average; reported beside the plain PSNR (n x the time)')
     args = ap.parse_args(argv)
@@ -144,6 +149,8 @@ def parse_args(argv=None):
         ap.error('give exactly one of --lq and --lq-from-gt')
     if args.lq_from_gt is not None and not 1 <= args.lq_from_gt <= 8:
         ap.error('--lq-from-gt takes a scale in 1..8')
+    if args.tile_blend is not None and args.tile is None:
+        ap.error('--tile-blend needs --tile')
     if args.degradation == 'bd' and args.lq_from_gt not in (2, 3, 4):
         ap.error('--degradation bd needs --lq-from-gt 2, 3 or 4')
     return args
