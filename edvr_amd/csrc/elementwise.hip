@@ -17,10 +17,12 @@ namespace edvr {
 __device__ __forceinline__ float sigmoidf(float v) { return 1.f / (1.f + __expf(-v)); }
 
 // ---- TSA temporal attention.  VEC pixels per thread (float4 when hw % 4 == 0).
-template <int VEC>
-__global__ __launch_bounds__(256) void tsa_temporal_kernel(const float *__restrict__ emb, const float *__restrict__ emb_ref,
-                                                           const float *__restrict__ aligned, float *__restrict__ out,
-                                                           float *__restrict__ prob_out, int b, int t, int c, int hw) {
+// PAIR: the product is stored a second time, to frame t - 1 - ti of out_rev - the modulated features of the clip in reversed frame
+// order (edvr_amd/video.py: time_reverse), from the same pass over emb, emb_ref and aligned.
+template <int VEC, bool PAIR>
+__device__ __forceinline__ void tsa_temporal_body(const float *__restrict__ emb, const float *__restrict__ emb_ref,
+                                                  const float *__restrict__ aligned, float *__restrict__ out, float *__restrict__ out_rev,
+                                                  float *__restrict__ prob_out, int b, int t, int c, int hw) {
   typedef float vec_t __attribute__((ext_vector_type(VEC)));
   const int hwv = hw / VEC;
   const int64_t total = (int64_t)b * t * hwv;
@@ -38,8 +40,31 @@ __global__ __launch_bounds__(256) void tsa_temporal_kernel(const float *__restri
     if (prob_out) reinterpret_cast<vec_t *>(prob_out + (int64_t)(bi * t + ti) * hw)[pv] = pr;
     const vec_t *a = reinterpret_cast<const vec_t *>(aligned + ((int64_t)(bi * t + ti) * c) * hw) + pv;
     vec_t *o = reinterpret_cast<vec_t *>(out + ((int64_t)(bi * t + ti) * c) * hw) + pv;
-    for (int ch = 0; ch < c; ++ch) o[(int64_t)ch * hwv] = a[(int64_t)ch * hwv] * pr;
+    if constexpr (PAIR) {
+      vec_t *o2 = reinterpret_cast<vec_t *>(out_rev + ((int64_t)(bi * t + (t - 1 - ti)) * c) * hw) + pv;
+      for (int ch = 0; ch < c; ++ch) {
+        const vec_t m = a[(int64_t)ch * hwv] * pr;
+        o[(int64_t)ch * hwv] = m;
+        o2[(int64_t)ch * hwv] = m;
+      }
+    } else {
+      for (int ch = 0; ch < c; ++ch) o[(int64_t)ch * hwv] = a[(int64_t)ch * hwv] * pr;
+    }
   }
+}
+
+template <int VEC>
+__global__ __launch_bounds__(256) void tsa_temporal_kernel(const float *__restrict__ emb, const float *__restrict__ emb_ref,
+                                                           const float *__restrict__ aligned, float *__restrict__ out,
+                                                           float *__restrict__ prob_out, int b, int t, int c, int hw) {
+  tsa_temporal_body<VEC, false>(emb, emb_ref, aligned, out, nullptr, prob_out, b, t, c, hw);
+}
+
+template <int VEC>
+__global__ __launch_bounds__(256) void tsa_temporal_pair_kernel(const float *__restrict__ emb, const float *__restrict__ emb_ref,
+                                                                const float *__restrict__ aligned, float *__restrict__ out,
+                                                                float *__restrict__ out_rev, int b, int t, int c, int hw) {
+  tsa_temporal_body<VEC, true>(emb, emb_ref, aligned, out, out_rev, nullptr, b, t, c, hw);
 }
 
 // ---- fused 3x3/s2/p1 max + avg pooling -> cat(max, avg)
@@ -308,6 +333,25 @@ int edvr_tsa_temporal_f32(const float *emb, const float *emb_ref, const float *a
                        aligned, out, prob_out, b, t, c, hw);
   }
   return check_launch("tsa_temporal_kernel");
+}
+
+int edvr_tsa_temporal_pair_f32(const float *emb, const float *emb_ref, const float *aligned, float *out, float *out_rev, int b, int t,
+                               int c, int hw, edvr_stream_t stream) {
+  using namespace edvr;
+  EDVR_REQUIRE(emb && emb_ref && aligned && out && out_rev && b > 0 && t > 0 && c > 0 && hw > 0, "tsa_temporal_pair: bad arguments");
+  // every thread reads `aligned` and writes both outputs at other frames than its own: the three buffers must not overlap
+  const int64_t n = (int64_t)b * t * c * hw;
+  EDVR_REQUIRE((out + n <= out_rev || out_rev + n <= out) && (out + n <= aligned || aligned + n <= out) &&
+                   (out_rev + n <= aligned || aligned + n <= out_rev),
+               "tsa_temporal_pair: out, out_rev and aligned must be distinct buffers");
+  if (hw % 4 == 0) {
+    hipLaunchKernelGGL(tsa_temporal_pair_kernel<4>, dim3(grid_for((int64_t)b * t * (hw / 4))), dim3(256), 0, as_stream(stream), emb,
+                       emb_ref, aligned, out, out_rev, b, t, c, hw);
+  } else {
+    hipLaunchKernelGGL(tsa_temporal_pair_kernel<1>, dim3(grid_for((int64_t)b * t * hw)), dim3(256), 0, as_stream(stream), emb, emb_ref,
+                       aligned, out, out_rev, b, t, c, hw);
+  }
+  return check_launch("tsa_temporal_pair_kernel");
 }
 
 int edvr_pool_maxavg_3x3s2_f32(const float *x, float *y, int n, int c, int h, int w, edvr_stream_t stream) {

@@ -112,13 +112,25 @@ class TSAFusion(nn.Module):
         self.upsample = nn.Upsample(scale_factor=2, mode='bilinear', align_corners=False)
 
     def forward(self, aligned_feat):
+        return self.spatial(self.temporal(aligned_feat))
+
+    def temporal(self, aligned_feat, pair=False):
+        """Temporal attention: aligned (b, t, c, h, w) -> the modulated features aligned * sigmoid(<emb_j, emb_ref>) as (b, t * c, h, w),
+        the operand of `spatial`.  pair=True (no-grad only): (mod, mod_rev) from one pass (F_.tsa_temporal_pair), mod_rev being mod
+        with the t frames of every clip in reversed order - what this method computes for the reversed clip, since the attention of
+        a frame depends on that frame and the centre frame alone."""
         b, t, c, h, w = aligned_feat.shape
         alias = F_.ops.carry_bound  # (a view of a tensor inherits its magnitude bound: the split-operand convs read it, ops.input_bound)
         emb_ref = F_.conv(self.temporal_attn1, alias(aligned_feat[:, self.center_frame_idx], aligned_feat))  # strided view, no clone
         emb = F_.conv(self.temporal_attn2, alias(aligned_feat.reshape(b * t, c, h, w), aligned_feat)).view(b, t, -1, h, w)
+        if pair:
+            mod, mod_rev = F_.tsa_temporal_pair(emb, emb_ref, aligned_feat)
+            return alias(mod.view(b, t * c, h, w), mod), alias(mod_rev.view(b, t * c, h, w), mod_rev)
         mod = F_.tsa_temporal(emb, emb_ref, aligned_feat)
-        mod = alias(mod.view(b, t * c, h, w), mod)
+        return alias(mod.view(b, t * c, h, w), mod)
 
+    def spatial(self, mod):
+        """Everything from feat_fusion on: the first layers that read the frames in their order along the channel axis."""
         feat = F_.conv(self.feat_fusion, mod, act=LRELU)
         attn = F_.conv(self.spatial_attn1, mod, act=LRELU)
         attn = F_.conv(self.spatial_attn2, F_.pool_maxavg(attn), act=LRELU)
@@ -288,7 +300,60 @@ class EDVR(nn.Module):
         bands (with out= only; passed only when tiles are blended - edvr_amd/video.py: tile_blend): (y low, y high, x low, x high), how
         many of the first / last rows / columns of the rectangle are a band shared with a neighbouring tile (output pixels, the frames'
         orientation).  The last kernel is then the weighted, accumulating tail ops.upsample4x_add_rect_blend defines (elem None: the
-        identity, element 0); with uint8 output `acc` is needed whether there is an ensemble or not."""
+        identity, element 0); with uint8 output `acc` is needed whether there is an ensemble or not.
+        The composition of align_windows and restore_from_aligned, which the temporal-reversal ensemble calls separately."""
+        self._check_tail_args(out_dtype, out, keep, elem, accumulate, scale, acc, bands)
+        operand, sink = self.align_windows(pyr, b, t)
+        return self._restore_aligned(operand, x_center, b, t, out_dtype, out, keep, elem, accumulate, scale, acc, bands, sink)
+
+    def align_windows(self, pyr, b, t, pair=False):
+        """The part of restore_from_features that does not depend on the order of a window's frames: PCD alignment of all b * t images
+        against their clip's centre frame and (with_tsa) the temporal attention.  Returns (operand, sink): operand (b, t * c, h, w), what
+        the fusion's first convs read; sink, the offset statistics of the DCNs, to hand to ONE restore_from_aligned call.
+        pair=True (no-grad only): (operand, operand_rev, sink) - operand_rev is the operand of the clips in reversed frame order
+        (edvr_amd/video.py: time_reverse): frame j aligned with the centre is the same tensor whichever way the clip runs, so it is the
+        same images at positions t - 1 - j: the second output of the attention kernel, or without TSA one gather of the aligned images."""
+        f1, f2, f3 = pyr
+        ctr = self.center_frame_idx
+        h, w = f1.shape[2], f1.shape[3]
+        if pair and 2 * ctr != t - 1:
+            raise ValueError(f'align_windows(pair=True): the reversed clip keeps its centre only when it is the middle frame, got {ctr} of {t}')
+        # all b*t frames aligned in one pass; frame i pairs with the centre frame of its clip
+        sink = []
+        dcns = self.pcd_align.dcn_modules()
+        for m in dcns:
+            m.stats_sink = sink
+        try:
+            aligned = self.pcd_align.align([f1, f2, f3], [f1, f2, f3], ref_map=(t, t, ctr))
+        finally:
+            for m in dcns:
+                m.stats_sink = None
+        flat = aligned
+        aligned = F_.ops.carry_bound(aligned.view(b, t, -1, h, w), aligned)
+        if self.taps is not None:
+            self.taps['aligned'] = aligned
+        if self.with_tsa:
+            operand = self.fusion.temporal(aligned, pair=pair)
+            return (*operand, sink) if pair else (operand, sink)
+        operand = F_.ops.carry_bound(aligned.view(b, -1, h, w), aligned)
+        if not pair:
+            return operand, sink
+        if torch.is_grad_enabled():
+            raise RuntimeError('align_windows(pair=True) has no backward: call it under torch.no_grad()')
+        table = torch.arange(b * t, dtype=torch.int32, device=flat.device).view(b, t).flip(1).reshape(-1)
+        rev = F_.ops.gather_images([flat], table)[0]
+        return operand, F_.ops.carry_bound(rev.view(b, -1, h, w), rev), sink
+
+    def restore_from_aligned(self, operand, x_center, b, t, out_dtype=torch.float32, out=None, keep=None, elem=None, accumulate='only', scale=1.0,
+                             acc=None, bands=None, sink=None):
+        """The part of restore_from_features after align_windows: the rest of the fusion, reconstruction, upsampling and the tail, with
+        restore_from_features' tail arguments.  sink: align_windows' statistics - given to exactly one of the calls that share an
+        alignment (the DCNs ran once); every call sends its own overflow flags (split_guard_submit)."""
+        self._check_tail_args(out_dtype, out, keep, elem, accumulate, scale, acc, bands)
+        return self._restore_aligned(operand, x_center, b, t, out_dtype, out, keep, elem, accumulate, scale, acc, bands, sink)
+
+    @staticmethod
+    def _check_tail_args(out_dtype, out, keep, elem, accumulate, scale, acc, bands):
         if out_dtype not in (torch.float32, torch.uint8):
             raise ValueError(f'out_dtype must be torch.float32 or torch.uint8, got {out_dtype}')
         if out_dtype == torch.uint8 and torch.is_grad_enabled():
@@ -301,25 +366,11 @@ class EDVR(nn.Module):
             raise ValueError('accumulate=, scale= and acc= belong to a self-ensemble element: they need elem')
         if (elem is not None or bands is not None) and (out is None or (out_dtype == torch.uint8) != (acc is not None)):
             raise ValueError('elem= and bands= store into out= (and, with uint8 output, accumulate in acc=)')
-        f1, f2, f3 = pyr
+
+    def _restore_aligned(self, operand, x_center, b, t, out_dtype, out, keep, elem, accumulate, scale, acc, bands, sink):
         dst = out
-        ctr = self.center_frame_idx
-        h, w = f1.shape[2], f1.shape[3]
-        # all b*t frames aligned in one pass; frame i pairs with the centre frame of its clip
-        sink = []
-        dcns = self.pcd_align.dcn_modules()
-        for m in dcns:
-            m.stats_sink = sink
-        try:
-            aligned = self.pcd_align.align([f1, f2, f3], [f1, f2, f3], ref_map=(t, t, ctr))
-        finally:
-            for m in dcns:
-                m.stats_sink = None
-        aligned = F_.ops.carry_bound(aligned.view(b, t, -1, h, w), aligned)
         taps = self.taps
-        if taps is not None:
-            taps['aligned'] = aligned
-        feat = self.fusion(aligned) if self.with_tsa else F_.conv(self.fusion, F_.ops.carry_bound(aligned.view(b, -1, h, w), aligned))
+        feat = self.fusion.spatial(operand) if self.with_tsa else F_.conv(self.fusion, operand)
         if taps is not None:
             taps['fused'] = feat
         out = self.reconstruction(feat)
@@ -363,8 +414,9 @@ class EDVR(nn.Module):
             out = F_.ops.upsample4x_add_u8(F_.conv(self.conv_last, out), x_center)
         else:
             out = F_.upsample4x_add(F_.conv(self.conv_last, out), x_center)
-        self._queue_offset_check(sink, b, t)
-        F_.ops.split_guard_submit(f1.device)
+        if sink:
+            self._queue_offset_check(sink, b, t)
+        F_.ops.split_guard_submit(operand.device)
         return out
 
     def _queue_offset_check(self, sink, b, t):

@@ -232,6 +232,13 @@ def tsa_temporal(emb, emb_ref, aligned):
     return ops.tsa_temporal(emb, emb_ref, aligned)
 
 
+def tsa_temporal_pair(emb, emb_ref, aligned):
+    """(tsa_temporal(...), the same with every clip's frames in reversed order), one pass (ops.tsa_temporal_pair).  No-grad only."""
+    if torch.is_grad_enabled():
+        raise RuntimeError('tsa_temporal_pair has no backward: call it under torch.no_grad()')
+    return ops.tsa_temporal_pair(emb, emb_ref, aligned)
+
+
 def tsa_combine(feat, attn, attn_add):
     if _needs_grad(feat, attn, attn_add):
         from . import autograd as ag

@@ -914,6 +914,37 @@ def tsa_temporal(emb, emb_ref, aligned, want_prob=False):
     return (out, prob) if want_prob else out
 
 
+def tsa_temporal_pair(emb, emb_ref, aligned, out=None, out_rev=None):
+    """tsa_temporal with a second output from the same pass (edvr_tsa_temporal_pair_f32): returns (out, out_rev), out bit for bit
+    tsa_temporal's and out_rev[:, j] = out[:, t - 1 - j] - the modulated features of every clip in reversed frame order (the
+    temporal-reversal self-ensemble of edvr_amd/video.py).  No-grad only.  out / out_rev: contiguous (b, t, c, h, w) buffers to write
+    (allocated when None); out, out_rev and aligned must not share memory.  Both outputs take `aligned`'s magnitude bound."""
+    if torch.is_grad_enabled():
+        raise RuntimeError('tsa_temporal_pair has no backward: call it under torch.no_grad()')
+    require_gpu(emb, emb_ref, aligned, out, out_rev)
+    b, t, c, h, w = aligned.shape
+    al_in = aligned
+    emb, emb_ref, aligned = emb.contiguous(), emb_ref.contiguous(), aligned.contiguous()
+    if tuple(emb.shape) != (b, t, c, h, w) or tuple(emb_ref.shape) != (b, c, h, w):
+        raise ValueError(f'tsa_temporal_pair: emb {tuple(emb.shape)} / emb_ref {tuple(emb_ref.shape)} do not match aligned {tuple(aligned.shape)}')
+    out = torch.empty_like(aligned) if out is None else out
+    out_rev = torch.empty_like(aligned) if out_rev is None else out_rev
+    nbytes = 4 * aligned.numel()
+    for o in (out, out_rev):
+        if tuple(o.shape) != (b, t, c, h, w) or not o.is_contiguous():
+            raise ValueError(f'tsa_temporal_pair: outputs are contiguous {(b, t, c, h, w)} tensors, got {tuple(o.shape)} / strides {o.stride()}')
+    spans = [(v.data_ptr(), v.data_ptr() + nbytes) for v in (out, out_rev, aligned)]
+    if any(a0 < b1 and b0 < a1 for i, (a0, a1) in enumerate(spans) for b0, b1 in spans[i + 1:]):
+        raise ValueError('tsa_temporal_pair: out, out_rev and aligned must be distinct buffers (every frame is read and written at two places)')
+    _run('tsa_temporal_pair', lambda: _lib.check(_lib.lib().edvr_tsa_temporal_pair_f32(_ptr(emb), _ptr(emb_ref), _ptr(aligned), _ptr(out), _ptr(out_rev), b, t, c,
+                                                     h * w, _stream()),
+                                            'edvr_tsa_temporal_pair_f32'), 0, _nb(emb, emb_ref, aligned, out, out_rev))
+    void_bound(out, out_rev)
+    carry_bound(out, al_in)  # aligned * sigmoid(.), and a permutation of it
+    carry_bound(out_rev, al_in)
+    return out, out_rev
+
+
 def pool_maxavg(x):
     require_gpu(x)
     x_in, x = x, x.contiguous()

@@ -20,6 +20,11 @@ the results are averaged.  A symmetry is the same shape of work as a tile - the 
 kernel of each pair's restore pass stores the inverse symmetry of its kept rectangle, accumulating over the elements (the `*_rect_d4`
 tails of csrc/ensemble.hip).
 
+Temporal reversal (`time_reverse`): every element also runs on the video in reversed frame order.  The window of an output frame in the
+reversed video is its forward window reversed, and alignment and temporal attention treat each (neighbour, centre) pair on its own, so
+the reversed pass reads the same bank, the same gather and the same aligned features: one attention launch with two outputs
+(ops.tsa_temporal_pair) hands the fusion its operand in both frame orders, and only fusion, reconstruction and tail run twice.
+
 No-grad inference only: there is no backward through the bank.
 """
 from collections import namedtuple
@@ -301,10 +306,30 @@ class VideoRestorer:
         acc = w * v;  acc = acc + w * v ...;  with an ensemble of n the last stores (acc + w * v) * (1 / n)
     each product rounded before its add.  Without an ensemble a pixel outside every band is bit for bit the unblended tiled result.
     No network work is added - the bands are computed by both tiles already; the tails turn from stores into read-modify-writes inside
-    the bands, and uint8 output keeps the float32 (chunk, 3, s H, s W) accumulator an ensemble needs."""
+    the bands, and uint8 output keeps the float32 (chunk, 3, s H, s W) accumulator an ensemble needs.
+
+    time_reverse False | True: every spatial element g_k ((0,) when self_ensemble is None) also runs on the video in reversed frame order.
+    With rev(v) = v.flip(0) and P, R, g_k as above, per tile, in float32,
+        terms, in this order:  for k in elements:  g_k^-1(R(g_k(P(lq)))),  then  g_k^-1(rev(R(rev(g_k(P(lq))))))
+        acc = first term;  acc = acc + next term ...;  out = crop(acc * (1 / (2 n)))        (n = len(elements))
+    through the accumulating tails of self_ensemble (first / middle / last by the position 2 e + r of 2 n; the identity element when
+    there is no spatial ensemble; with tile_blend their weighted forms, the two time orders adjacent in the work-list order); uint8
+    output is the tensor2img bytes of that value, accumulated in the tagged float32 scratch.  It turns the tiled path on; windows,
+    temporal padding, chunking, bank capacity and streaming are unchanged, and `pairs` / `banks` stay (tile x spatial element).
+    share_alignment (needs time_reverse; default True): output frame i's window in the reversed video is its forward window reversed
+    (every padding mode), PCD aligns image j with the centre frame and nothing else, and the attention map of image j likewise - so per
+    (tile, element) and chunk there is ONE gather and ONE EDVR.align_windows(pair=True), whose attention kernel stores the modulated
+    features in both frame orders, then two EDVR.restore_from_aligned calls (fusion, reconstruction, upsampling, tail).  Offset
+    statistics are queued once (the DCNs ran once), the overflow guard after each tail.  False: the plain implementation - a second
+    gather with every row of the slot table reversed and a second EDVR.restore_from_features - kept as the in-tree cross-check (the arms
+    are bit-identical in the tests) and as a fallback.
+    WHAT IT COSTS: shared, 2 x fusion, reconstruction and upsampling and 1 x alignment and attention per element (by the module
+    definitions about 15 of 115 conv-units per output frame saved for each of the T frames of a window; DESIGN 4.10 has the
+    measurement), the second copy of the modulated features (chunk x T x C x h x w float32) while the first tail runs, no further bank;
+    unshared, 2 x everything after the per-frame stage.  With uint8 output the float32 accumulator, as with an ensemble."""
 
     def __init__(self, net, num_frame=None, padding='reflection_circle', chunk=8, out_dtype=torch.float32, pad_mode=None, tile=None,
-                 tile_overlap=None, self_ensemble=None, tile_blend=None):
+                 tile_overlap=None, self_ensemble=None, tile_blend=None, time_reverse=False, share_alignment=None):
         if out_dtype not in (torch.float32, torch.uint8):
             raise ValueError(f'out_dtype must be torch.float32 or torch.uint8, got {out_dtype}')
         if pad_mode not in (None, 'reflect', 'replicate'):
@@ -321,7 +346,14 @@ class VideoRestorer:
             tile_bands(self.multiple, self.multiple, tile, tile_overlap, tile_blend, self.multiple)  # its argument errors now as well
         self.pad_mode, self.tile, self.tile_overlap, self.tile_blend = pad_mode, tile, tile_overlap, tile_blend
         self.elements = ensemble_elements(self_ensemble)
-        self.tiled = pad_mode is not None or tile is not None or self.elements is not None
+        if not isinstance(time_reverse, bool):
+            raise ValueError(f'time_reverse must be True or False, got {time_reverse!r}')
+        if share_alignment is not None and not isinstance(share_alignment, bool):
+            raise ValueError(f'share_alignment must be True or False, got {share_alignment!r}')
+        if share_alignment is not None and not time_reverse:
+            raise ValueError('share_alignment chooses how the reversed pass of time_reverse runs: it needs time_reverse=True')
+        self.time_reverse, self.share_alignment = time_reverse, time_reverse and share_alignment is not False
+        self.tiled = pad_mode is not None or tile is not None or self.elements is not None or time_reverse
         self.net, self.padding, self.chunk, self.out_dtype = net, padding, int(chunk), out_dtype
         self.num_feat = net.conv_l2_1.in_channels
         if num_frame is None:
@@ -510,8 +542,13 @@ class VideoRestorer:
         table = self._slot_table([f % self.slots for r in rows for f in r], centre.device)
         n = len(self.elements) if self.elements is not None else 0
         blend = self.blend_grid
-        # uint8 output: the elements (and blended tiles) add up in float32
-        acc = self._scratch((b, 3, s * H, s * W), centre.device) if (n or blend is not None) and u8 else None
+        rev = self.time_reverse
+        terms = 2 * max(n, 1) if rev else n  # what adds up per tile: the elements, each in both time orders with time_reverse
+        table_rev = None
+        if rev and not self.share_alignment:  # the plain arm: the same bank, every window's frames in reversed order
+            table_rev = self._slot_table([f % self.slots for r in rows for f in reversed(r)], centre.device)
+        # uint8 output: the elements, the two time orders (and blended tiles) add up in float32
+        acc = self._scratch((b, 3, s * H, s * W), centre.device) if (terms or blend is not None) and u8 else None
         for i, ((tile, k), bank, groups) in enumerate(zip(self.pairs, self.banks, self._tile_groups)):
             net.check_offsets(wait=False)  # per tile (and element) what a forward does before its launches, as in _restore
             if bank[0].is_cuda:
@@ -529,8 +566,27 @@ class VideoRestorer:
                            acc=acc[:, :, ys, xs] if u8 else None)
             if blend is not None:  # the weighted tail (identity element without an ensemble)
                 how.update(bands=tuple(s * v for v in bands), acc=acc[:, :, ys, xs] if u8 else None)
-            net.restore_from_features(pyr, self._oriented(centre, tile, k), b, t, out_dtype=self.out_dtype,
-                                      out=out[:, ys, xs] if u8 else out[:, :, ys, xs], keep=(s * ky, s * kx), **how)
+            how.update(out_dtype=self.out_dtype, out=out[:, ys, xs] if u8 else out[:, :, ys, xs], keep=(s * ky, s * kx))
+            x_center = self._oriented(centre, tile, k)
+            if not rev:
+                net.restore_from_features(pyr, x_center, b, t, **how)
+                continue
+            # time_reverse: this pair's two terms, positions 2 e and 2 e + 1 of `terms`, through the accumulating tails (the identity
+            # element without a spatial ensemble).  A window's centre frame is the same in both time orders.
+            e = i % max(n, 1)
+            mode = lambda pos: 'first' if pos == 0 else 'last' if pos == terms - 1 else 'middle'
+            how.update(elem=0 if k is None else k, scale=1.0 / terms, acc=acc[:, :, ys, xs] if u8 else None)
+            if self.share_alignment:  # one alignment and one attention pass give the fusion's operand in both orders
+                mod, mod_rev, sink = net.align_windows(pyr, b, t, pair=True)
+                del pyr
+                net.restore_from_aligned(mod, x_center, b, t, sink=sink, **dict(how, accumulate=mode(2 * e)))
+                del mod
+                net.restore_from_aligned(mod_rev, x_center, b, t, **dict(how, accumulate=mode(2 * e + 1)))
+                del mod_rev
+            else:
+                net.restore_from_features(pyr, x_center, b, t, **dict(how, accumulate=mode(2 * e)))
+                del pyr
+                net.restore_from_features(self._gather(bank, table_rev), x_center, b, t, **dict(how, accumulate=mode(2 * e + 1)))
         return out
 
     # ---- public

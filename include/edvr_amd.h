@@ -349,6 +349,11 @@ int edvr_dcnv1_bwd_f32(const float *x, const float *offset, const float *weight,
  * out[b,t,c,p] = aligned[b,t,c,p] * prob[b,t,p].  prob_out (b,t,hw) may be NULL. */
 int edvr_tsa_temporal_f32(const float *emb, const float *emb_ref, const float *aligned, float *out, float *prob_out,
                           int b, int t, int c, int hw, edvr_stream_t stream);
+/* The same pass with two outputs: out as above (bit for bit), and out_rev[b,t-1-ti,c,p] = out[b,ti,c,p] - the modulated features of
+ * every clip in reversed frame order (temporal-reversal self-ensemble, edvr_amd/video.py).  out, out_rev and aligned are distinct,
+ * non-overlapping buffers (anything else is an error); t = 1 is legal (out_rev equals out in value). */
+int edvr_tsa_temporal_pair_f32(const float *emb, const float *emb_ref, const float *aligned, float *out, float *out_rev,
+                               int b, int t, int c, int hw, edvr_stream_t stream);
 /* MaxPool2d(3,2,1) and AvgPool2d(3,2,1, count_include_pad) in one pass; y (n, 2c, ho, wo) = cat(max, avg). */
 int edvr_pool_maxavg_3x3s2_f32(const float *x, float *y, int n, int c, int h, int w, edvr_stream_t stream);
 /* nn.Upsample(scale_factor=2, bilinear, align_corners=False); y = scale * up(x). */

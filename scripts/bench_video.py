@@ -27,6 +27,11 @@ Tile blending (VideoRestorer tile_blend), same method, merged into profiles/vide
 
     python scripts/bench_video.py --tile-blend 32 --config L_T5 [--out-dtype uint8]   # 544x960, 2x2 tiles: blended against unblended tiles,
                                                                                       # the blend tails' share, the seam table both ways
+
+Temporal reversal (VideoRestorer time_reverse), same method, merged into profiles/video/bench_video_time.json:
+
+    python scripts/bench_video.py --time-reverse --config L_T5 [--self-ensemble flip4]   # plain against both arms (share_alignment True /
+                                                                                         # False): frames/s, peak memory, the pair kernel's share
 """
 import argparse
 import json
@@ -345,6 +350,36 @@ def leg_blend(args, net, kwargs, dev, frames, chunk):
             'blend_tails': [r for r in tab['kernels'] if r['name'] in BLEND_KERNELS], 'seam': seam, **res}
 
 
+def leg_time(args, net, kwargs, dev, frames, chunk):
+    """time_reverse, both arms (share_alignment True / False), against the VideoRestorer without it at the same chunk and the same
+    spatial ensemble: frames/s (the unshared arm: expected about 1 / 2 of that), peak memory, and the share of the shared arm's kernel
+    time spent in the attention kernel with two outputs."""
+    from edvr_amd import VideoRestorer
+    h, w = CONFIGS[args.config][1]
+    dt = getattr(torch, args.out_dtype)
+    base = dict(padding=args.padding, chunk=chunk, out_dtype=dt, **({'self_ensemble': args.self_ensemble} if args.self_ensemble else {}))
+    lq = torch.rand(frames, 3, h, w, generator=torch.Generator().manual_seed(0)).to(dev)
+    plain = VideoRestorer(net, **base)
+    shared = VideoRestorer(net, time_reverse=True, **base)
+    unshared = VideoRestorer(net, time_reverse=True, share_alignment=False, **base)
+    res, outs = _two_arms({'shared': lambda: shared.restore(lq), 'unshared': lambda: unshared.restore(lq), 'plain': lambda: plain.restore(lq)},
+                          frames, args.repeats, net)
+    tab = kernel_table(lambda: shared.restore(lq))
+    net.check_offsets()
+    pair_ms = sum(r['ms'] for r in tab['kernels'] if r['name'] == 'tsa_temporal_pair')
+    fps = {k: res[k]['frames_per_s'] for k in res}
+    gain = fps['shared'] / fps['unshared']
+    return {'leg': 'time', 'hw': [h, w], 'self_ensemble': args.self_ensemble,
+            'ratio_unshared_over_plain_frames_per_s': round(fps['unshared'] / fps['plain'], 4),
+            'ratio_shared_over_plain_frames_per_s': round(fps['shared'] / fps['plain'], 4),
+            'ratio_shared_over_unshared_frames_per_s': round(gain, 4),
+            'shared_faster_beyond_plain_spread': bool(gain - 1.0 > res['plain']['spread']),
+            'kernel_time_ratio_shared_over_unshared': round(res['shared']['kernel_ms'] / res['unshared']['kernel_ms'], 4),
+            'arms_bit_identical': bool(torch.equal(outs['shared'], outs['unshared'])),
+            'pair_kernel_ms': round(pair_ms, 3), 'pair_kernel_share_of_kernel_time': round(pair_ms / tab['kernel_ms'], 5),
+            'max_abs_difference_to_plain_output': (outs['shared'].float() - outs['plain'].float()).abs().max().item(), **res}
+
+
 def main_leg(args):
     from edvr_amd import _lib
     from edvr_amd.build import source_hash
@@ -353,17 +388,19 @@ def main_leg(args):
     dev = torch.device('cuda:0')
     net = _build_net(kwargs, dev)
     with torch.no_grad():
-        legs = {'pad': leg_pad, 'tiles': leg_tiles, 'seam': leg_seam, 'large': leg_large, 'ensemble': leg_ensemble, 'blend': leg_blend}
+        legs = {'pad': leg_pad, 'tiles': leg_tiles, 'seam': leg_seam, 'large': leg_large, 'ensemble': leg_ensemble, 'blend': leg_blend,
+                'time': leg_time}
         result = legs[args.leg](args, net, kwargs, dev, frames, chunk)
     result = {'config': args.config, 'edvr': dict(kwargs), 'frames': frames, 'chunk': chunk, 'padding': args.padding, 'out_dtype': args.out_dtype,
               'repeats': args.repeats, **result, 'csrc_sha16': source_hash(), 'library': _lib.lib().edvr_version().decode(),
               'device': torch.cuda.get_device_name(0)}
-    default = {'ensemble': 'bench_video_ensemble.json', 'blend': 'bench_video_blend.json'}.get(args.leg, 'bench_video_tiles.json')
+    default = {'ensemble': 'bench_video_ensemble.json', 'blend': 'bench_video_blend.json',
+               'time': 'bench_video_time.json'}.get(args.leg, 'bench_video_tiles.json')
     path = os.path.abspath(args.json or os.path.join(os.path.dirname(os.path.abspath(__file__)), '..', 'profiles', 'video', default))
     os.makedirs(os.path.dirname(path), exist_ok=True)
     merged = json.load(open(path)) if os.path.exists(path) else {}
     key = (f'{args.self_ensemble}_{args.config}' if args.leg == 'ensemble' else f'blend{args.tile_blend}_{args.config}' if args.leg == 'blend'
-           else f'{args.leg}_{args.config}')
+           else f'time_{args.self_ensemble}_{args.config}' if args.leg == 'time' and args.self_ensemble else f'{args.leg}_{args.config}')
     merged[key + ('' if args.out_dtype == 'float32' else '_' + args.out_dtype)] = result
     with open(path, 'w') as f:
         json.dump(merged, f, indent=1, sort_keys=True)
@@ -371,7 +408,7 @@ def main_leg(args):
     print(json.dumps(result))
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument('--config', default='L_T5', choices=sorted(CONFIGS))
     ap.add_argument('--frames', type=int, default=None)
@@ -385,15 +422,27 @@ def main():
                     help='timing arm: self_ensemble against the plain VideoRestorer (profiles/video/bench_video_ensemble.json)')
     ap.add_argument('--tile-blend', type=int, default=None, metavar='N',
                     help='timing arm: tile_blend=N against the unblended tiled path, same 2 x 2 tiles (profiles/video/bench_video_blend.json)')
-    args = ap.parse_args()
+    ap.add_argument('--time-reverse', action='store_true',
+                    help='timing arm: time_reverse (both share_alignment arms) against the VideoRestorer without it, with --self-ensemble on '
+                         'top of that ensemble (profiles/video/bench_video_time.json)')
+    args = ap.parse_args(argv)
     if args.tile_blend is not None:
-        if args.leg or args.self_ensemble:
-            ap.error('--tile-blend is a leg of its own: give it without --leg / --self-ensemble')
+        if args.leg or args.self_ensemble or args.time_reverse:
+            ap.error('--tile-blend is a leg of its own: give it without --leg / --self-ensemble / --time-reverse')
         args.leg = 'blend'
-    if args.self_ensemble:
+    if args.time_reverse:
+        if args.leg:
+            ap.error('--time-reverse is a leg of its own: give it without --leg (it composes with --self-ensemble)')
+        args.leg = 'time'
+    elif args.self_ensemble:
         if args.leg:
             ap.error('--self-ensemble is a leg of its own: give it without --leg')
         args.leg = 'ensemble'
+    return args
+
+
+def main():
+    args = parse_args()
     if not torch.cuda.is_available():
         raise SystemExit('bench_video.py measures on the GPU: none found')
     if args.leg:

@@ -5,6 +5,8 @@ fusion / reconstruction pass.  `--pad-mode reflect` admits frames of any size, `
 `--tile-blend N` cross-fades neighbouring tiles over N input pixels around each cut (VideoRestorer's tile_blend).
 `--self-ensemble flip4|d4` also restores every clip under the 4 flips / the 8 symmetries of the square and averages (the "+" rows of
 the papers; VideoRestorer's self_ensemble, n times the time) and reports the plain and the ensemble PSNR side by side.
+`--time-reverse` adds the video in reversed frame order to the ensemble (VideoRestorer's time_reverse: x2 on top, the alignment shared
+between the two orders); alone it is an ensemble of the two time orders, with `--self-ensemble d4` the x16 one.
 
     python scripts/eval_video.py --lq datasets/REDS4/sharp_bicubic --gt datasets/REDS4/GT --weights EDVR_L_x4_SR_REDS_official.pth
     python scripts/eval_video.py --lq-from-gt 4 --bicubic-baseline --gt my_footage --weights EDVR_L_x4_SR_REDS_official.pth
@@ -63,16 +65,19 @@ def evaluate(args, log=print):
     # frames of any size (--pad-mode / --tile / --tile-overlap / --tile-blend): passed on only where given
     any_size = {k: (tuple(v) if k == 'tile' else v) for k in ('pad_mode', 'tile', 'tile_overlap', 'tile_blend')
                 for v in [getattr(args, k, None)] if v is not None}
-    ensemble = getattr(args, 'self_ensemble', None)
+    ensemble, reverse = getattr(args, 'self_ensemble', None), bool(getattr(args, 'time_reverse', False))
+    # what the second pass runs, and how it is called in the report
+    plus_kw = {**({'self_ensemble': ensemble} if ensemble else {}), **({'time_reverse': True} if reverse else {})}
+    label = '+'.join(([ensemble] if ensemble else []) + (['time-reverse'] if reverse else []))
     results, base, plus = {}, {}, {}
     for folder in ds.folders[rank::world]:
         lq, gt = ds.clip(folder)
         _, psnr = metrics.validate_video(net, lq, gt, num_frame=args.num_frame, padding=args.padding, chunk=args.batch,
                                          crop_border=args.crop_border, test_y_channel=args.test_y_channel, **any_size)
         results[folder] = (sum(psnr), len(psnr))
-        if ensemble:
+        if plus_kw:
             _, p = metrics.validate_video(net, lq, gt, num_frame=args.num_frame, padding=args.padding, chunk=args.batch,
-                                          crop_border=args.crop_border, test_y_channel=args.test_y_channel, self_ensemble=ensemble, **any_size)
+                                          crop_border=args.crop_border, test_y_channel=args.test_y_channel, **plus_kw, **any_size)
             plus[folder] = (sum(p), len(p))
         if baseline:
             b = bicubic_baseline(lq, gt, args.hr_in, args.crop_border, args.test_y_channel, args.batch)
@@ -91,10 +96,10 @@ def evaluate(args, log=print):
         return {k: s / max(n, 1) for k, (s, n) in sorted(parts.items())}
 
     summary, base = merged(results), merged(base) if baseline else {}
-    plus = merged(plus) if ensemble else {}
+    plus = merged(plus) if plus_kw else {}
     if rank == 0:
         beside = (lambda v: f' (bicubic {v:.4f} dB)') if baseline else (lambda v: '')
-        with_plus = (lambda v: f', self-ensemble {ensemble} {v:.4f} dB') if ensemble else (lambda v: '')
+        with_plus = (lambda v: f', self-ensemble {label} {v:.4f} dB') if plus_kw else (lambda v: '')
         for k, v in summary.items():
             log(f'{k}: PSNR {v:.4f} dB' + with_plus(plus.get(k, float('nan'))) + beside(base.get(k, float('nan'))))
         if summary:  # the average of the per-folder averages
@@ -104,8 +109,10 @@ def evaluate(args, log=print):
             import json
             record = {'psnr': summary, 'average': sum(summary.values()) / max(len(summary), 1),
                       'degradation': degradation if args.lq is None else None}  # None: the LQ folder's, whatever made it
-            if ensemble:
+            if plus_kw:
                 record.update(self_ensemble=ensemble, self_ensemble_psnr=plus, self_ensemble_average=sum(plus.values()) / max(len(plus), 1))
+                if reverse:
+                    record.update(time_reverse=True)
             if baseline:
                 record.update(bicubic_psnr=base, bicubic_average=sum(base.values()) / max(len(base), 1))
             with open(args.json, 'w') as f:
@@ -144,6 +151,9 @@ def parse_args(argv=None):
                          'at most the overlap)')
     ap.add_argument('--self-ensemble', default=None, choices=['flip4', 'd4'],
                     help='also restore under the 4 flips / the 8 symmetries of the square and average; reported beside the plain PSNR (n x the time)')
+    ap.add_argument('--time-reverse', action='store_true',
+                    help='also restore the video in reversed frame order and average (x2; composes with --self-ensemble); reported beside the '
+                         'plain PSNR')
     args = ap.parse_args(argv)
     if (args.lq is None) == (args.lq_from_gt is None):
         ap.error('give exactly one of --lq and --lq-from-gt')
