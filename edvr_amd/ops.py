@@ -1848,3 +1848,131 @@ def lq_crops_from_windows(windows, table, scale, degradation, table_host=None):
     _run('lq_crops_from_windows', lambda: _lib.check(getattr(_lib.lib(), name)(_ptr(windows), _ptr(table), _ptr(table_host), _ptr(out), n, p, e, e, pitch,
                                                                                 scale, _stream()), name), 0, nbytes)
     return out
+
+
+# ------------------------------------------------------------------------------------------------ Y'CbCr 4:2:0 <-> RGB (csrc/yuv.hip)
+YUV_MATRICES = {'bt601': (0.299, 0.114), 'bt709': (0.2126, 0.0722)}              # (Kr, Kb)
+YUV_RANGES = {'limited': (219.0, 224.0, 16.0), 'full': (255.0, 255.0, 0.0)}     # luma scale, chroma scale, luma offset (chroma offset 128)
+
+
+def yuv420_frame_size(H, W):
+    """Bytes of one I420 frame of (H, W): the luma plane and two chroma planes of (ceil(H / 2), ceil(W / 2))."""
+    return H * W + 2 * ((H + 1) // 2) * ((W + 1) // 2)
+
+
+def yuv_coeffs(matrix='bt601', range='limited'):
+    """(M, Mi, off) in float64 (nested lists): M maps RGB in 0 ... 255 to (Y, Cb, Cr) before the offsets off = (yoff, 128, 128), Mi is its
+    inverse (adjugate over determinant, every step one float64 operation).  The kernels get both rounded to float32."""
+    if matrix not in YUV_MATRICES:
+        raise ValueError(f'matrix must be one of {sorted(YUV_MATRICES)}, got {matrix!r}')
+    if range not in YUV_RANGES:
+        raise ValueError(f'range must be one of {sorted(YUV_RANGES)}, got {range!r}')
+    kr, kb = YUV_MATRICES[matrix]
+    kg = 1.0 - kr - kb
+    ys, cs, yoff = YUV_RANGES[range]
+    sy, scb, scr = ys / 255.0, cs / 255.0 / (2.0 * (1.0 - kb)), cs / 255.0 / (2.0 * (1.0 - kr))
+    m = [[sy * kr, sy * kg, sy * kb], [scb * -kr, scb * -kg, scb * (1.0 - kb)], [scr * (1.0 - kr), scr * -kg, scr * -kb]]
+    (a, b, c), (d, e, f), (g, h, i) = m
+    adj = [[e * i - f * h, c * h - b * i, b * f - c * e], [f * g - d * i, a * i - c * g, c * d - a * f], [d * h - e * g, b * g - a * h, a * e - b * d]]
+    det = a * adj[0][0] + b * adj[1][0] + c * adj[2][0]
+    return m, [[v / det for v in row] for row in adj], [yoff, 128.0, 128.0]
+
+
+def _yuv_coef_arg(mat, off):
+    return (ctypes.c_float * 12)(*[v for row in mat for v in row], *off)
+
+
+def _yuv_batch(yuv, H, W, what):
+    if yuv.dim() != 2:
+        raise ValueError(f'{what} is a 2-D uint8 batch (n, >= framesize), got {tuple(yuv.shape)}')
+    if H < 1 or W < 1:
+        raise ValueError(f'a frame has at least one row and column, got {H} x {W}')
+    fs = yuv420_frame_size(H, W)
+    if yuv.shape[1] < fs:
+        raise ValueError(f'{what}: rows of {yuv.shape[1]} bytes are shorter than the {fs} bytes of a {H} x {W} I420 frame')
+    if yuv.stride(1) != 1:
+        raise ValueError(f'{what}: the bytes of a frame must be contiguous (stride(1) == 1), got stride {yuv.stride(1)}')
+    n = yuv.shape[0]
+    if n < 1:
+        raise ValueError(f'{what}: no frames')
+    if n > 1 and yuv.stride(0) < fs:
+        raise ValueError(f'{what}: frames {yuv.stride(0)} bytes apart overlap')
+    return n, fs, (yuv.stride(0) if n > 1 else fs)
+
+
+def yuv420_to_rgb(yuv, H, W, matrix='bt601', range='limited', chroma='bilinear', out_dtype=torch.float32):
+    """8-bit I420 frames -> RGB in ONE launch.  yuv: uint8 (n, >= framesize) on the GPU with stride(1) == 1 and ANY row stride and base
+    offset - each row starts with the H W luma bytes, then the (ceil(H / 2), ceil(W / 2)) Cb and Cr planes, i.e. the payload of a Y4M
+    frame (`buf[:, 6:]` of a Y4MReader buffer works as it is).  matrix 'bt601' | 'bt709', range 'limited' | 'full' (`yuv_coeffs`), chroma
+    'bilinear' (centre-sited 1/4 - 3/4 filter, vertical then horizontal, indices clamped) | 'nearest'.  Returns float32 (n, 3, H, W) in
+    [0, 1] or uint8 (n, H, W, 3); the definition, operation by operation, is DESIGN 4.11.  ValueError for bad names and layouts."""
+    if chroma not in ('bilinear', 'nearest'):
+        raise ValueError(f"chroma must be 'bilinear' or 'nearest', got {chroma!r}")
+    if out_dtype not in (torch.float32, torch.uint8):
+        raise ValueError(f'out_dtype must be torch.float32 or torch.uint8, got {out_dtype}')
+    _, mi, off = yuv_coeffs(matrix, range)
+    require_gpu(yuv, dtypes=(torch.uint8,))
+    H, W = int(H), int(W)
+    n, fs, stride = _yuv_batch(yuv, H, W, 'yuv')
+    u8out = out_dtype == torch.uint8
+    out = torch.empty((n, H, W, 3) if u8out else (n, 3, H, W), dtype=out_dtype, device=yuv.device)
+    coef, bil = _yuv_coef_arg(mi, off), int(chroma == 'bilinear')
+    nbytes = float(n) * (fs + 3 * H * W * (1 if u8out else 4))
+    if u8out:
+        _run('yuv420_to_rgb', lambda: _lib.check(_lib.lib().edvr_yuv420_to_rgb_u8(_ptr(yuv), _ptr(out), n, H, W, stride, coef, bil, _stream()),
+                                                 'edvr_yuv420_to_rgb_u8'), 0, nbytes)
+    else:
+        _run('yuv420_to_rgb', lambda: _lib.check(_lib.lib().edvr_yuv420_to_rgb_f32(_ptr(yuv), _ptr(out), n, H, W, stride, 3 * H * W, coef, bil, _stream()),
+                                                 'edvr_yuv420_to_rgb_f32'), 0, nbytes)
+    return out
+
+
+def _byte_span(t):
+    """[first, last) byte addresses a tensor's elements lie in."""
+    if t.numel() == 0:
+        return t.data_ptr(), t.data_ptr()
+    last = sum((s - 1) * st for s, st in zip(t.shape, t.stride()))
+    return t.data_ptr(), t.data_ptr() + (last + 1) * t.element_size()
+
+
+def rgb_to_yuv420(rgb, matrix='bt601', range='limited', out=None):
+    """RGB frames -> 8-bit I420 in ONE launch: rgb float32 (n, 3, H, W) (clamped to [0, 1], x 255, NOT rounded before the matrix: the
+    only quantisation is the one to YUV bytes; dense images, a slice of a longer video works) or uint8 (n, H, W, 3).  Returns uint8
+    (n, framesize), framesize = yuv420_frame_size(H, W): luma, then Cb and Cr, each the mean of its 2 x 2 block (an odd edge replicates).
+    out: a uint8 (n, >= framesize) batch to write into instead, stride(1) == 1, any row stride and base offset (`buf[:, 6:]` of a Y4M
+    write buffer); bytes past a frame's end are left alone and `out` is returned.  ValueError for bad names, layouts and an `out` that
+    overlaps the input."""
+    m, _, off = yuv_coeffs(matrix, range)
+    if not rgb.is_cuda:
+        raise NotImplementedError('edvr_amd ops run on the GPU only (HIP/gfx950); got a CPU tensor')
+    u8 = rgb.dtype == torch.uint8
+    if u8:
+        if rgb.dim() != 4 or rgb.shape[-1] != 3:
+            raise ValueError(f'uint8 frames are (n, H, W, 3), got {tuple(rgb.shape)}')
+        rgb = rgb.contiguous()
+        n, H, W, _ = rgb.shape
+    else:
+        require_gpu(rgb)
+        if rgb.dim() != 4 or rgb.shape[1] != 3:
+            raise ValueError(f'float32 frames are (n, 3, H, W), got {tuple(rgb.shape)}')
+        rgb = _as_planes(rgb)
+        n, _, H, W = rgb.shape
+    if out is None:
+        out = torch.empty((n, yuv420_frame_size(H, W)), dtype=torch.uint8, device=rgb.device)
+    else:
+        require_gpu(out, dtypes=(torch.uint8,))
+        if out.dim() == 2 and out.shape[0] != n:
+            raise ValueError(f'out holds {out.shape[0]} frames, the input {n}')
+    n, fs, stride = _yuv_batch(out, H, W, 'out')
+    (a0, a1), (b0, b1) = _byte_span(rgb), _byte_span(out)
+    if a0 < b1 and b0 < a1:
+        raise ValueError('out overlaps the input')
+    coef = _yuv_coef_arg(m, off)
+    nbytes = float(n) * (fs + 3 * H * W * (1 if u8 else 4))
+    if u8:
+        _run('rgb_to_yuv420', lambda: _lib.check(_lib.lib().edvr_rgb_to_yuv420_u8(_ptr(rgb), _ptr(out), n, H, W, stride, coef, _stream()),
+                                                 'edvr_rgb_to_yuv420_u8'), 0, nbytes)
+    else:
+        _run('rgb_to_yuv420', lambda: _lib.check(_lib.lib().edvr_rgb_to_yuv420_f32(_ptr(rgb), _ptr(out), n, H, W, _img_stride(rgb), stride, coef, _stream()),
+                                                 'edvr_rgb_to_yuv420_f32'), 0, nbytes)
+    return out

@@ -1,0 +1,219 @@
+"""YUV4MPEG2 ("Y4M") in, YUV4MPEG2 out: the container around ops.yuv420_to_rgb / VideoRestorer / ops.rgb_to_yuv420, with no dependency.
+
+    ffmpeg -i in.mp4 -f yuv4mpegpipe - | python scripts/restore_video.py - - --weights ... | ffmpeg -i - out.mp4
+
+A Y4M stream is one text line `YUV4MPEG2 W<width> H<height> F<num>:<den> I<interlacing> A<num>:<den> C<chroma> X<comment>...`, then per
+frame a line `FRAME[ parameters]` and the raw planes: for 8-bit 4:2:0 the H W luma bytes, then the (ceil(H / 2), ceil(W / 2)) Cb and Cr
+planes - exactly the batch row ops.yuv420_to_rgb reads.  Everything here works on non-seekable streams (pipes), holds a bounded number
+of frames and uses no threads: pinned host buffers and non_blocking copies keep the device busy while the host reads and writes.
+"""
+import torch
+
+from . import ops
+from .ops import yuv420_frame_size
+
+MAGIC = b'YUV4MPEG2'
+FRAME = b'FRAME\n'
+CHROMA_420 = ('420jpeg', '420mpeg2', '420paldv', '420')
+
+
+def default_matrix(H, W):
+    """What players assume when a stream does not say: BT.709 for HD sizes (W >= 1280 or H > 576), BT.601 below."""
+    return 'bt709' if W >= 1280 or H > 576 else 'bt601'
+
+
+def _host_buffer(shape):
+    """uint8 host memory, pinned where a device exists (non_blocking copies need it)."""
+    return torch.empty(shape, dtype=torch.uint8, pin_memory=torch.cuda.is_available())
+
+
+def _bytes_of(t):
+    return memoryview(t.numpy()).cast('B')
+
+
+class Y4MReader:
+    """Reads 8-bit 4:2:0 progressive YUV4MPEG2 from a binary stream (a file, a pipe, sys.stdin.buffer, io.BytesIO): nothing seeks.
+
+    Accepted: C420jpeg, C420mpeg2, C420paldv, C420 and no C tag - ALL treated as centre-sited chroma (the 'bilinear' filter of
+    ops.yuv420_to_rgb; the left-sited filter of mpeg2 / the co-sited rows of paldv are not implemented, the difference is a quarter-sample
+    chroma shift); Ip, I? and no I tag; XCOLORRANGE=FULL | LIMITED (no tag: limited).  ValueError: a bad magic, a missing or non-positive
+    W / H, interlaced video (It, Ib, Im), C422 / C444 / Cmono / C411 ..., any high-bit-depth format (C420p10, p12, p16 ...), a frame line
+    that is not `FRAME`, and a truncated frame (the message names the frame index).
+
+    width, height, fps ('30000:1001' as written, or None), aspect (likewise), range ('limited' | 'full'), chroma (the tag's value or
+    None), framesize; `frames_read` counts what read() returned so far."""
+
+    def __init__(self, stream):
+        self.stream = stream
+        line = stream.readline(1024)
+        if not line.startswith(MAGIC + b' ') or not line.endswith(b'\n'):
+            raise ValueError(f'not a YUV4MPEG2 stream: the header starts with {line[:16]!r}')
+        self.width = self.height = self.fps = self.aspect = self.chroma = None
+        self.range, interlace = 'limited', None
+        for tok in line[len(MAGIC):].decode('ascii', 'replace').split():
+            tag, val = tok[0], tok[1:]
+            if tag == 'W':
+                self.width = self._positive(val, 'W')
+            elif tag == 'H':
+                self.height = self._positive(val, 'H')
+            elif tag == 'F':
+                self.fps = val
+            elif tag == 'A':
+                self.aspect = val
+            elif tag == 'I':
+                interlace = val
+            elif tag == 'C':
+                self.chroma = val
+            elif tag == 'X' and val.upper().startswith('COLORRANGE='):
+                rng = val[len('COLORRANGE='):].upper()
+                if rng not in ('FULL', 'LIMITED'):
+                    raise ValueError(f'XCOLORRANGE is FULL or LIMITED, got {rng!r}')
+                self.range = rng.lower()
+        if self.width is None or self.height is None:
+            raise ValueError('the YUV4MPEG2 header gives no W / H')
+        if interlace not in (None, 'p', '?'):
+            raise ValueError(f'interlaced video (I{interlace}) is not supported: deinterlace first')
+        if self.chroma is not None and self.chroma not in CHROMA_420:
+            raise ValueError(f'C{self.chroma} is not supported: 8-bit 4:2:0 only ({", ".join("C" + c for c in CHROMA_420)})')
+        self.framesize = yuv420_frame_size(self.height, self.width)
+        self.frames_read = 0
+
+    @staticmethod
+    def _positive(val, tag):
+        if not val.isdigit() or int(val) < 1:
+            raise ValueError(f'the YUV4MPEG2 header has {tag}{val}')
+        return int(val)
+
+    def _fill(self, view):
+        """Reads until `view` is full or the stream ends (a pipe returns what it has); the number of bytes read."""
+        got, readinto = 0, getattr(self.stream, 'readinto', None)
+        while got < len(view):
+            if readinto is not None:
+                k = readinto(view[got:])
+            else:
+                piece = self.stream.read(len(view) - got)
+                k = len(piece)
+                view[got:got + k] = piece
+            if not k:
+                break
+            got += k
+        return got
+
+    def read(self, k):
+        """Up to k frames as ONE uint8 (j, 6 + framesize) host buffer (pinned where a device exists), j <= k, j = 0 at the end of the
+        stream: each row is `FRAME\\n` and the frame's planes, so that `buf[:, 6:]` on the device is the batch ops.yuv420_to_rgb reads and
+        the whole buffer is what a Y4MWriter of the same size writes.  Parameters after FRAME are read and dropped."""
+        row = len(FRAME) + self.framesize
+        buf = _host_buffer((max(int(k), 0), row))
+        flat = _bytes_of(buf) if buf.numel() else None
+        j = 0
+        while j < buf.shape[0]:
+            line = self.stream.readline(1024)
+            if not line:
+                break
+            if not (line == FRAME or line.startswith(b'FRAME ')) or not line.endswith(b'\n'):
+                raise ValueError(f'frame {self.frames_read + j}: expected a FRAME line, got {line[:16]!r}')
+            flat[j * row:j * row + len(FRAME)] = FRAME
+            got = self._fill(flat[j * row + len(FRAME):(j + 1) * row])
+            if got != self.framesize:
+                raise ValueError(f'frame {self.frames_read + j} is truncated: {got} of {self.framesize} bytes')
+            j += 1
+        self.frames_read += j
+        return buf[:j]
+
+
+class Y4MWriter:
+    """Writes 8-bit 4:2:0 progressive YUV4MPEG2: the header on construction (`Ip`, `C420jpeg`, F / A as given - strings such as
+    '30000:1001', omitted when None - and XCOLORRANGE=FULL for range 'full'), then `write(buf)` for every uint8 host buffer
+    (k, 6 + framesize) whose rows already begin with `FRAME\\n` - the bytes go out as they are, in one write."""
+
+    def __init__(self, stream, W, H, fps=None, aspect=None, range='limited'):
+        if range not in ops.YUV_RANGES:
+            raise ValueError(f'range must be one of {sorted(ops.YUV_RANGES)}, got {range!r}')
+        if int(W) < 1 or int(H) < 1:
+            raise ValueError(f'a frame has at least one row and column, got {H} x {W}')
+        self.stream, self.width, self.height, self.range = stream, int(W), int(H), range
+        self.framesize = yuv420_frame_size(self.height, self.width)
+        self.frames_written = 0
+        head = [MAGIC.decode(), f'W{self.width}', f'H{self.height}'] + ([f'F{fps}'] if fps else []) + ['Ip'] + ([f'A{aspect}'] if aspect else [])
+        head += ['C420jpeg'] + (['XCOLORRANGE=FULL'] if range == 'full' else [])
+        stream.write((' '.join(head) + '\n').encode('ascii'))
+
+    def write(self, buf):
+        if buf.is_cuda or buf.dtype != torch.uint8 or buf.dim() != 2 or buf.shape[1] != len(FRAME) + self.framesize or not buf.is_contiguous():
+            raise ValueError(f'frames are written from a contiguous uint8 host buffer (k, {len(FRAME) + self.framesize}), got '
+                             f'{buf.dtype} {tuple(buf.shape)}')
+        if buf.shape[0] == 0:
+            return
+        marks = torch.tensor(list(FRAME), dtype=torch.uint8)
+        if not torch.equal(buf[:, :len(FRAME)], marks.expand(buf.shape[0], -1)):
+            raise ValueError('every row of the buffer begins with the FRAME line')
+        self.stream.write(_bytes_of(buf))
+        self.frames_written += buf.shape[0]
+
+
+def restore_y4m(net, src, dst, *, matrix_in=None, matrix_out=None, chroma='bilinear', read_frames=8, **restorer_kwargs):
+    """Restore a Y4M stream with `net` (an EDVR in eval mode, on the GPU) into a Y4M stream; returns the number of frames.  Call it under
+    torch.no_grad().
+
+        src (a binary stream or a Y4MReader) -> read_frames frames per read into pinned memory -> one copy to the device
+            -> ops.yuv420_to_rgb(buf[:, 6:], float32) -> VideoRestorer(net, out_dtype=torch.float32, **restorer_kwargs).restore_chunks
+            -> ops.rgb_to_yuv420(chunk, out=buf[:, 6:]) -> one copy into pinned memory -> dst (a binary stream)
+
+    The frames never exist as RGB bytes and the network's float32 result is quantised once, to YUV bytes.  matrix_in / matrix_out:
+    'bt601' | 'bt709'; None follows `default_matrix` for that side's OWN frame size - a 180 x 320 input is read as BT.601 and its 720 x 1280
+    result written as BT.709, because that is how it will be played.  The range (XCOLORRANGE) is copied from the input, F and A likewise;
+    the output is s W x s H, s = 4 (1 for an hr_in network).  chroma: the upsampling filter of the decode.  restorer_kwargs: chunk,
+    pad_mode, tile, tile_overlap, tile_blend, self_ensemble, time_reverse, ... as VideoRestorer takes them - sizes that are no multiple
+    of 4 (16 with hr_in) need pad_mode.  Memory: read_frames input frames per buffer, the restorer's bank and pieces, two chunks of output.
+    The host writes chunk i while the device works on chunk i + 1; nothing else waits."""
+    from .video import VideoRestorer
+    reader = src if isinstance(src, Y4MReader) else Y4MReader(src)
+    if int(read_frames) < 1:
+        raise ValueError(f'read_frames must be at least 1, got {read_frames}')
+    for name in (matrix_in, matrix_out):
+        if name is not None and name not in ops.YUV_MATRICES:
+            raise ValueError(f'matrix must be one of {sorted(ops.YUV_MATRICES)}, got {name!r}')
+    if chroma not in ('bilinear', 'nearest'):
+        raise ValueError(f"chroma must be 'bilinear' or 'nearest', got {chroma!r}")
+    vr = VideoRestorer(net, out_dtype=torch.float32, **restorer_kwargs)
+    device = next(net.parameters()).device
+    H, W = reader.height, reader.width
+    Ho, Wo = vr.scale * H, vr.scale * W
+    matrix_in = matrix_in or default_matrix(H, W)
+    matrix_out = matrix_out or default_matrix(Ho, Wo)
+    writer = Y4MWriter(dst, Wo, Ho, reader.fps, reader.aspect, reader.range)
+    row = len(FRAME) + writer.framesize
+    marks = torch.tensor(list(FRAME), dtype=torch.uint8).to(device)
+
+    def decoded():
+        while True:
+            host = reader.read(read_frames)
+            if host.shape[0] == 0:
+                return
+            yield ops.yuv420_to_rgb(host.to(device, non_blocking=True)[:, len(FRAME):], H, W, matrix_in, reader.range, chroma)
+
+    pending = None  # (pinned buffer, event after its copy) of the chunk before this one
+
+    def flush():
+        if pending is not None:
+            if pending[1] is not None:
+                pending[1].synchronize()
+            writer.write(pending[0])
+
+    for out in vr.restore_chunks(decoded()):
+        buf = torch.empty((out.shape[0], row), dtype=torch.uint8, device=device)
+        buf[:, :len(FRAME)] = marks
+        ops.rgb_to_yuv420(out, matrix_out, reader.range, out=buf[:, len(FRAME):])
+        host = _host_buffer(tuple(buf.shape))
+        host.copy_(buf, non_blocking=True)
+        done = None
+        if device.type == 'cuda':
+            done = torch.cuda.Event()
+            done.record()
+        flush()
+        pending = (host, done)
+    flush()
+    if hasattr(dst, 'flush'):
+        dst.flush()
+    return writer.frames_written

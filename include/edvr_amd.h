@@ -640,6 +640,29 @@ int edvr_imresize_bicubic_u8_windows(const uint8_t *src, const int32_t *table, c
 int edvr_bd_downsample_u8_windows(const uint8_t *src, const int32_t *table, const int32_t *table_host, uint8_t *dst, int n, int p, int wh, int ww,
                                   int pitch, int scale, edvr_stream_t stream);
 
+/* 8-bit Y'CbCr 4:2:0 <-> RGB (csrc/yuv.hip; definition: DESIGN 4.11).  An I420 frame of (H, W) is H W luma bytes, then Hc Wc bytes of Cb,
+ * then of Cr, Hc = ceil(H / 2), Wc = ceil(W / 2), every plane dense - the payload of a YUV4MPEG2 frame; a batch is n frames yuv_stride >=
+ * framesize bytes apart at ANY base address and stride (a Y4M read buffer: framesize + 6 apart, 6 past its start).  Odd H and W are legal.
+ * coef: 12 HOST floats read before the call returns - a 3 x 3 matrix row-major, then the offsets (yoff, 128, 128): for the decode the
+ * INVERSE of the forward matrix M, for the encode M itself (RGB in 0 ... 255 -> Y, Cb, Cr), computed in float64 by the caller and rounded.
+ * All arithmetic float32, every product and sum rounded on its own in the order of DESIGN 4.11 (no contraction).
+ * yuv420_to_rgb: chroma upsampled by replication (bilinear == 0) or by the centre-sited 1/4 - 3/4 filter, vertical then horizontal,
+ * indices clamped to the plane; v = Mi (Y - yoff, Cb - 128, Cr - 128); _f32: rgb (n, 3, H, W), dense images rgb_img_stride floats apart,
+ * clamp(v, 0, 255) / 255.0f; _u8: rgb (n, H, W, 3) dense bytes, clamp and round half to even.
+ * rgb_to_yuv420: _f32 reads x = clamp(f, 0, 1) * 255.0f (NaN -> 0), _u8 the byte; p = M x + off; Y = round(clamp(p_0)), a chroma sample
+ * the mean of p over its 2 x 2 block (row and column indices clamped to the frame: an odd edge replicates), clamped and rounded.  Bytes
+ * between the frames of the output batch are not written.
+ * 16-byte accesses on a side whose base and strides are 16-byte aligned where W % 16 == 0, scalar ones otherwise; same values either way.
+ * EDVR_ERR_ARG: null pointers, n, H or W < 1, yuv_stride < framesize or rgb_img_stride < 3 H W with n > 1, H W > 2^29.  No allocation,
+ * no wait. */
+int edvr_yuv420_to_rgb_f32(const uint8_t *yuv, float *rgb, int n, int H, int W, int64_t yuv_stride, int64_t rgb_img_stride, const float *coef,
+                           int bilinear, edvr_stream_t stream);
+int edvr_yuv420_to_rgb_u8(const uint8_t *yuv, uint8_t *rgb, int n, int H, int W, int64_t yuv_stride, const float *coef, int bilinear,
+                          edvr_stream_t stream);
+int edvr_rgb_to_yuv420_f32(const float *rgb, uint8_t *yuv, int n, int H, int W, int64_t rgb_img_stride, int64_t yuv_stride, const float *coef,
+                           edvr_stream_t stream);
+int edvr_rgb_to_yuv420_u8(const uint8_t *rgb, uint8_t *yuv, int n, int H, int W, int64_t yuv_stride, const float *coef, edvr_stream_t stream);
+
 /* Multi-tensor Adam step <- torch.optim.Adam.step() as the reference builds it (basicsr/models/edvr_model.py:21-53, parameter
  * groups with dcn_lr_mul; stepped in sr_model.py:112).  `chunk_table` is a DEVICE array of n_chunks records of
  * edvr_adam_chunk_bytes() = 64 bytes: { float *p; const float *g; float *m; float *v; int32 n (<= 65536 elements of one tensor);

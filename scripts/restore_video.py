@@ -1,0 +1,105 @@
+"""Restore a video that has no ground truth: YUV4MPEG2 (8-bit 4:2:0) in, YUV4MPEG2 out, `-` for stdin / stdout.
+
+    ffmpeg -i in.mp4 -f yuv4mpegpipe - | python scripts/restore_video.py - - --weights EDVR_L_x4_SR_REDS_official.pth | ffmpeg -i - out.mp4
+    python scripts/restore_video.py in.y4m out.y4m --weights ... --pad-mode reflect --tile 256 256 --self-ensemble flip4
+
+edvr_amd.y4m.restore_y4m: the frames go to the device as the decoder wrote them, are converted to RGB there (edvr_amd.ops.yuv420_to_rgb),
+restored by VideoRestorer with every frame's features extracted once, converted back (ops.rgb_to_yuv420) and written as they arrive -
+bounded memory, no intermediate files, one quantisation.  The network options are those of scripts/eval_video.py, `--batch` is the
+number of output frames per pass; `--matrix-in` / `--matrix-out` default to the player rule for each side's own size (BT.709 from 1280
+columns or 577 rows, BT.601 below), `--chroma` picks the chroma upsampling filter of the decode.  Everything this script prints goes to
+stderr: stdout may be the video.
+"""
+import argparse
+import os
+import sys
+import time
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..'))
+
+
+def log(*a):
+    print(*a, file=sys.stderr, flush=True)
+
+
+def restore(args, log=log):
+    import torch
+    from edvr_amd import EDVR
+    from edvr_amd.optim import load_network
+    from edvr_amd.y4m import Y4MReader, restore_y4m
+    device = torch.device('cuda', int(os.environ.get('LOCAL_RANK', 0)))
+    torch.cuda.set_device(device)
+    net = EDVR(num_in_ch=3, num_out_ch=3, num_feat=args.num_feat, num_frame=args.num_frame, deformable_groups=8,
+               num_extract_block=5, num_reconstruct_block=args.num_reconstruct_block, center_frame_idx=None, hr_in=args.hr_in,
+               with_predeblur=args.with_predeblur, with_tsa=not args.no_tsa).to(device).eval()
+    if args.weights:
+        load_network(net, args.weights, strict=True)
+    kwargs = {k: (tuple(v) if k == 'tile' else v) for k in ('pad_mode', 'tile', 'tile_overlap', 'tile_blend', 'self_ensemble')
+              for v in [getattr(args, k, None)] if v is not None}
+    if getattr(args, 'time_reverse', False):
+        kwargs['time_reverse'] = True
+    src = sys.stdin.buffer if args.input == '-' else open(args.input, 'rb')
+    dst = sys.stdout.buffer if args.output == '-' else open(args.output, 'wb')
+    try:
+        reader = Y4MReader(src)
+        log(f'{args.input}: {reader.width} x {reader.height}, F{reader.fps}, C{reader.chroma}, {reader.range} range')
+        t0 = time.time()
+        with torch.no_grad():
+            n = restore_y4m(net, reader, dst, matrix_in=args.matrix_in, matrix_out=args.matrix_out, chroma=args.chroma,
+                            read_frames=args.read_frames, num_frame=args.num_frame, padding=args.padding, chunk=args.batch, **kwargs)
+        net.check_offsets()
+        torch.cuda.synchronize()
+        dt = time.time() - t0
+        log(f'{args.output}: {n} frames in {dt:.1f} s ({n / max(dt, 1e-9):.2f} frames/s)')
+    finally:
+        if src is not sys.stdin.buffer:
+            src.close()
+        if dst is not sys.stdout.buffer:
+            dst.close()
+    return n
+
+
+def parse_args(argv=None):
+    ap = argparse.ArgumentParser(description='Restore a YUV4MPEG2 video with EDVR (8-bit 4:2:0 in and out).')
+    ap.add_argument('input', metavar='IN', help='Y4M file, or - for stdin')
+    ap.add_argument('output', metavar='OUT', help='Y4M file, or - for stdout')
+    ap.add_argument('--weights', default=None)
+    ap.add_argument('--num-feat', type=int, default=128)
+    ap.add_argument('--num-reconstruct-block', type=int, default=40)
+    ap.add_argument('--num-frame', type=int, default=5)
+    ap.add_argument('--hr-in', action='store_true')
+    ap.add_argument('--with-predeblur', action='store_true')
+    ap.add_argument('--no-tsa', action='store_true')
+    ap.add_argument('--padding', default='reflection_circle')
+    ap.add_argument('--batch', type=int, default=8, help='output frames per pass (VideoRestorer chunk)')
+    ap.add_argument('--read-frames', type=int, default=8, help='frames per read and per copy to the device')
+    ap.add_argument('--pad-mode', default=None, choices=['reflect', 'replicate'],
+                    help='frames of any size: extend them at the bottom and right to the size multiple (4; 16 with --hr-in), crop the output')
+    ap.add_argument('--tile', type=int, nargs=2, default=None, metavar=('TH', 'TW'), help='restore tile by tile (input pixels, multiples of the size multiple)')
+    ap.add_argument('--tile-overlap', type=int, default=None, help='input pixels neighbouring tiles share (default 8 x the size multiple)')
+    ap.add_argument('--tile-blend', type=int, default=None, metavar='N',
+                    help='with --tile: cross-fade neighbouring tiles over N input pixels around each cut')
+    ap.add_argument('--self-ensemble', default=None, choices=['flip4', 'd4'],
+                    help='restore under the 4 flips / the 8 symmetries of the square and average (n x the time)')
+    ap.add_argument('--time-reverse', action='store_true', help='also restore the video in reversed frame order and average (x2)')
+    ap.add_argument('--matrix-in', default=None, choices=['bt601', 'bt709'], help="the input's matrix (default: by its size)")
+    ap.add_argument('--matrix-out', default=None, choices=['bt601', 'bt709'], help="the output's matrix (default: by ITS size)")
+    ap.add_argument('--chroma', default='bilinear', choices=['bilinear', 'nearest'], help='chroma upsampling of the decode')
+    args = ap.parse_args(argv)
+    if args.tile_blend is not None and args.tile is None:
+        ap.error('--tile-blend needs --tile')
+    if args.tile_overlap is not None and args.tile is None:
+        ap.error('--tile-overlap needs --tile')
+    if args.batch < 1 or args.read_frames < 1:
+        ap.error('--batch and --read-frames are at least 1')
+    if args.input != '-' and args.input == args.output:
+        ap.error('IN and OUT are the same file')
+    return args
+
+
+def main():
+    restore(parse_args())
+
+
+if __name__ == '__main__':
+    main()
