@@ -254,10 +254,15 @@ __global__ __launch_bounds__(256) void act_bwd_kernel(const float *__restrict__ 
     const int ch = (int)((i / hw) % c);
     float g = dy[i];
     if (ch >= act_from) {
-      float v = y[i];
+      float v = y[i], noise = 0.f;
       if (res1) v -= res1[i];  // y = act(z) + res: recover act(z)
+      // relu(z) = 0 comes back exactly as 0 through one residual (0 + r = r), but through two as the rounding errors of
+      // fl(r1 + r2) and of fl(y - r1), of either sign and at most 2^-24 (|y| + |y - r1|): the gate opens above twice that only.
+      // (A truly positive relu output below that threshold - ~1e-6 for residuals of order 1 - gets the gradient 0 too: the
+      // forward's rounding had already made it indistinguishable from 0.)
+      if (res1 && res2) noise = 0x1p-23f * (fabsf(y[i]) + fabsf(v));
       if (res2) v -= res2[i];
-      if (act == EDVR_ACT_RELU) g = v > 0.f ? g : 0.f;
+      if (act == EDVR_ACT_RELU) g = v > noise ? g : 0.f;
       else if (act == EDVR_ACT_LRELU) g = v > 0.f ? g : 0.1f * g;
       else if (act == EDVR_ACT_SIGMOID) g = g * v * (1.f - v);
     }

@@ -1006,7 +1006,9 @@ def add(a, b):
 
 
 def act_backward(dy, y, act, act_from=0, res1=None, res2=None):
-    """dz = dy * act'(.) computed from the activation output; y = act(z) + res1 + res2 as the fused conv wrote it."""
+    """dz = dy * act'(.) computed from the activation output; y = act(z) + res1 + res2 as the fused conv wrote it.  (relu with both
+    residuals: an output of 0 returns from y - res1 - res2 as rounding noise of either sign, so the kernel opens the gate only above
+    2^-23 (|y| + |y - res1|); a positive output below that, ~1e-6 for residuals of order 1, gets the gradient 0 as well.)"""
     require_gpu(dy, y, res1, res2)
     dy_in = dy
     dy, y = dy.contiguous(), y.contiguous()
