@@ -62,6 +62,9 @@ PROTOTYPES = {
     'edvr_psnr_sse_f32': (i32, [vp, vp, vp, i32, i32, i32, i32, i64, i64, i32, i32, i32, vp]),
     'edvr_ssim_partials': (sz, [i32, i32, i32]),
     'edvr_ssim_f32': (i32, [vp, vp, vp, i32, i32, i32, i32, i64, i64, i32, i32, vp]),
+    'edvr_niqe_blocks': (sz, [i32, i32, i32]),
+    'edvr_niqe_moments_f32': (i32, [vp, vp, i32, i32, i32, i32, i64, i32, vp]),
+    'edvr_niqe_moments_u8': (i32, [vp, vp, i32, i32, i32, i64, i32, vp]),
     'edvr_frames_u8_to_f32': (i32, [vp, vp, i32, i32, i32, i32, vp, i32, vp]),
     'edvr_gather_images_f32': (i32, [vp, vp, vp, vp, i32, vp, i32, i32, vp]),
     'edvr_upsample4x_add_u8': (i32, [vp, vp, vp, i32, i32, i32, vp]),

@@ -13,14 +13,8 @@
 
 namespace edvr {
 
-// Y of one pixel as to_y_channel computes it: BGR image of the reference = channels (2, 1, 0) of the RGB tensor; float32 / 255,
-// dot with the BT.601 row in double, + 16, / 255 -> float32, x 255 in float32.  NOT inlined: the two images must run the very
-// same instruction sequence, or identical images stop giving a difference of exactly zero (PSNR = inf in the reference).
-__device__ __noinline__ float y_of_pixel(const float *__restrict__ p, int64_t o, int64_t hw) {
-  const float r = __fdiv_rn(to_u8(p[o]), 255.f), g = __fdiv_rn(to_u8(p[hw + o]), 255.f), bl = __fdiv_rn(to_u8(p[2 * hw + o]), 255.f);
-  const double d = (double)bl * 24.966 + (double)g * 128.553 + (double)r * 65.481 + 16.0;
-  return __fmul_rn((float)(d / 255.0), 255.f);
-}
+// y_of_pixel (pixel.h): Y of one pixel as to_y_channel computes it, one out-of-line instruction sequence shared by both images here and
+// by the NIQE kernel (csrc/niqe.hip).
 
 // partial[img][block] = sum over this block's pixels (inside the crop) of squared differences; channels = 3 (RGB tensors) or 1
 __global__ __launch_bounds__(256) void psnr_sse_kernel(const float *__restrict__ a, const float *__restrict__ b, double *__restrict__ partial,

@@ -18,6 +18,21 @@ __device__ __forceinline__ float div255(unsigned u) {
   return __fmaf_rn(__fmaf_rn(-q, 255.f, f), r, q);
 }
 
+// Y of one pixel as to_y_channel computes it (metric_util.py:34-47, matlab_functions.py:207-240), from the three bytes (integers in
+// [0, 255] held as floats): float32 / 255, dot with the BT.601 row in double, + 16, / 255 -> float32, x 255 in float32.  NOT inlined:
+// every image and every kernel (PSNR, SSIM, NIQE) must run the very same instruction sequence, or identical images stop giving a
+// difference of exactly zero (PSNR = inf in the reference) and the float and byte entries of a metric stop agreeing bit for bit.
+inline __device__ __noinline__ float y_of_bytes(float r8, float g8, float b8) {
+  const float r = __fdiv_rn(r8, 255.f), g = __fdiv_rn(g8, 255.f), bl = __fdiv_rn(b8, 255.f);
+  const double d = (double)bl * 24.966 + (double)g * 128.553 + (double)r * 65.481 + 16.0;
+  return __fmul_rn((float)(d / 255.0), 255.f);
+}
+
+// The same for pixel `o` of a planar (3, h w) RGB float tensor: BGR image of the reference = channels (2, 1, 0) of the RGB tensor.
+__device__ __forceinline__ float y_of_pixel(const float *__restrict__ p, int64_t o, int64_t hw) {
+  return y_of_bytes(to_u8(p[o]), to_u8(p[hw + o]), to_u8(p[2 * hw + o]));
+}
+
 // ---- bilinear upsampling, align_corners=False: src = (dst + 0.5) / S - 0.5, clamped at 0
 template <int S>
 __device__ __forceinline__ void src_index(int dst, int in, int &i0, int &i1, float &l) {

@@ -152,7 +152,7 @@ class Y4MWriter:
         self.frames_written += buf.shape[0]
 
 
-def restore_y4m(net, src, dst, *, matrix_in=None, matrix_out=None, chroma='bilinear', read_frames=8, **restorer_kwargs):
+def restore_y4m(net, src, dst, *, matrix_in=None, matrix_out=None, chroma='bilinear', read_frames=8, on_chunk=None, **restorer_kwargs):
     """Restore a Y4M stream with `net` (an EDVR in eval mode, on the GPU) into a Y4M stream; returns the number of frames.  Call it under
     torch.no_grad().
 
@@ -166,7 +166,9 @@ def restore_y4m(net, src, dst, *, matrix_in=None, matrix_out=None, chroma='bilin
     the output is s W x s H, s = 4 (1 for an hr_in network).  chroma: the upsampling filter of the decode.  restorer_kwargs: chunk,
     pad_mode, tile, tile_overlap, tile_blend, self_ensemble, time_reverse, ... as VideoRestorer takes them - sizes that are no multiple
     of 4 (16 with hr_in) need pad_mode.  Memory: read_frames input frames per buffer, the restorer's bank and pieces, two chunks of output.
-    The host writes chunk i while the device works on chunk i + 1; nothing else waits."""
+    The host writes chunk i while the device works on chunk i + 1; nothing else waits.  on_chunk: called as on_chunk(chunk) with every
+    restored float32 RGB chunk (k, 3, s H, s W) on the device, in order, before it is converted back - for scoring the output
+    (metrics.calculate_niqe) or a preview; it must not modify the chunk.  Without it the launches are unchanged."""
     from .video import VideoRestorer
     reader = src if isinstance(src, Y4MReader) else Y4MReader(src)
     if int(read_frames) < 1:
@@ -204,6 +206,8 @@ def restore_y4m(net, src, dst, *, matrix_in=None, matrix_out=None, chroma='bilin
     for out in vr.restore_chunks(decoded()):
         buf = torch.empty((out.shape[0], row), dtype=torch.uint8, device=device)
         buf[:, :len(FRAME)] = marks
+        if on_chunk is not None:
+            on_chunk(out)
         ops.rgb_to_yuv420(out, matrix_out, reader.range, out=buf[:, len(FRAME):])
         host = _host_buffer(tuple(buf.shape))
         host.copy_(buf, non_blocking=True)

@@ -459,6 +459,21 @@ size_t edvr_ssim_partials(int h, int w, int crop_border);
 int edvr_ssim_f32(const float *a, const float *b, double *partial, int n, int c, int h, int w, int64_t a_img_stride,
                   int64_t b_img_stride, int crop_border, int y_channel, edvr_stream_t stream);
 
+/* NIQE on the device, the per-pixel part <- tensor2img + calculate_niqe / niqe (basicsr/metrics/niqe.py:10-205, convert_to='y').  The
+ * image loses crop_border on every side, then keeps its top-left 96 nbh x 96 nbw pixels; blocks = nbh * nbw = edvr_niqe_blocks(h, w,
+ * crop_border) (0: no block fits -> EDVR_ERR_ARG).  Per scale (0: full size, 1: the 2x2 float32 mean) and 96 / 48-pixel block the MSCN
+ * map z = (x - mu) / (sigma + 1) is computed in float32 as NumPy computes it (7x7 Gaussian, sigma 7/6, 49 products accumulated in
+ * double and rounded once, mode='nearest' at the edge of the KEPT rectangle), and for each of the five maps z, z roll(z,[0,1]),
+ * z roll(z,[1,0]), z roll(z,[1,1]), z roll(z,[1,-1]) (float32 products, the roll wraps inside the block) five doubles leave:
+ *   out[((img * 2 + scale) * blocks + block) * 25 + map * 5 + k],  k: 0 sum v^2 over v < 0, 1 #(v < 0), 2 sum v^2 over v > 0, 3 #(v > 0),
+ *   4 sum |v|;  block = bw * nbh + bh (column-major, the reference's order);  v^2 is the float32 square, the sums run in double in a
+ *   fixed order (no atomics: a frame's numbers do not depend on its place in the batch).
+ * _f32: x (n, c, h, w) fp32 RGB in [0, 1] (clamped, x255, rounded: tensor2img), c = 3 -> Y of to_y_channel, c = 1 -> the byte itself;
+ * _u8: x (n, h, w, 3) RGB bytes.  img_stride in elements, 0 = dense.  One launch: grid (blocks, 2, n). */
+size_t edvr_niqe_blocks(int h, int w, int crop_border);
+int edvr_niqe_moments_f32(const float *x, double *out, int n, int c, int h, int w, int64_t img_stride, int crop_border, edvr_stream_t stream);
+int edvr_niqe_moments_u8(const uint8_t *x, double *out, int n, int h, int w, int64_t img_stride, int crop_border, edvr_stream_t stream);
+
 /* Input pipeline, device side <- imfrombytes(float32=True) (basicsr/utils/img_util.py:101-123: uint8 -> float32 / 255.), augment
  * (basicsr/data/transforms.py:84-151: hflip, then vflip, then transpose, the same state for every image of a clip), img2tensor
  * (img_util.py:9-33: BGR->RGB, HWC->CHW), default collate + CUDAPrefetcher's H2D copy (prefetch_dataloader.py:84-126).

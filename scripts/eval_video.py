@@ -15,7 +15,9 @@ between the two orders); alone it is an ensemble of the two time orders, with `-
 (edvr_amd.data.imresize, 8-bit like a stored dataset); with `--degradation bd` they are DUF's Gaussian blur and subsampling instead
 (edvr_amd.data.duf_downsample, SCALE 2, 3 or 4, float as the reference's VideoTestDUFDataset feeds them).  `--bicubic-baseline` scores the
 bicubic enlargement of the LQ frames beside the model under either degradation, as the published BI and BD tables do (the LQ frames
-themselves for --hr-in networks); `--json FILE` writes what is printed, and the degradation.
+themselves for --hr-in networks); `--json FILE` writes what is printed, and the degradation.  `--niqe PARAMS.npz` also scores every
+output with the no-reference NIQE (metrics.calculate_niqe against BasicSR's niqe_pris_params.npz, lower is better) - the model's, the
+second pass's and the baseline's, next to their PSNRs.
 
 The Vimeo90K-Test list is one window per item - nothing to reuse: use scripts/test_reds.py --vimeo-meta for it.
 """
@@ -38,6 +40,26 @@ def bicubic_baseline(lq, gt, hr_in=False, crop_border=0, test_y_channel=False, c
     for s0 in range(0, lq.shape[0], chunk):
         part = lq[s0:s0 + chunk]
         scores += metrics.calculate_psnr(part if scale == 1 else imresize(part, scale), gt[s0:s0 + chunk], crop_border, test_y_channel)
+    return scores
+
+
+def niqe_scores(frames, params, crop_border=0, chunk=8):
+    """NIQE per frame of (t, 3, H, W) float32 RGB frames on the device, `chunk` frames per launch."""
+    from edvr_amd import metrics
+    scores = []
+    for s0 in range(0, frames.shape[0], chunk):
+        scores += metrics.calculate_niqe(frames[s0:s0 + chunk], crop_border, params=params)
+    return scores
+
+
+def bicubic_niqe(lq, gt, params, hr_in=False, crop_border=0, chunk=8):
+    """NIQE per frame of what bicubic_baseline scores: the bicubic enlargement of `lq` to the size of `gt` (the LQ frames when hr_in)."""
+    from edvr_amd.data import imresize
+    scale = 1 if hr_in else gt.shape[-1] // lq.shape[-1]
+    scores = []
+    for s0 in range(0, lq.shape[0], chunk):
+        part = lq[s0:s0 + chunk]
+        scores += niqe_scores(part if scale == 1 else imresize(part, scale), params, crop_border, chunk)
     return scores
 
 
@@ -70,18 +92,31 @@ def evaluate(args, log=print):
     plus_kw = {**({'self_ensemble': ensemble} if ensemble else {}), **({'time_reverse': True} if reverse else {})}
     label = '+'.join(([ensemble] if ensemble else []) + (['time-reverse'] if reverse else []))
     results, base, plus = {}, {}, {}
+    niqe_path = getattr(args, 'niqe', None)
+    niqe_params = metrics.load_niqe_params(niqe_path) if niqe_path else None
+    niqe, niqe_base, niqe_plus = {}, {}, {}
     for folder in ds.folders[rank::world]:
         lq, gt = ds.clip(folder)
-        _, psnr = metrics.validate_video(net, lq, gt, num_frame=args.num_frame, padding=args.padding, chunk=args.batch,
+        out, psnr = metrics.validate_video(net, lq, gt, num_frame=args.num_frame, padding=args.padding, chunk=args.batch,
                                          crop_border=args.crop_border, test_y_channel=args.test_y_channel, **any_size)
         results[folder] = (sum(psnr), len(psnr))
+        if niqe_params is not None:
+            q = niqe_scores(out, niqe_params, args.crop_border, args.batch)
+            niqe[folder] = (sum(q), len(q))
         if plus_kw:
-            _, p = metrics.validate_video(net, lq, gt, num_frame=args.num_frame, padding=args.padding, chunk=args.batch,
+            out, p = metrics.validate_video(net, lq, gt, num_frame=args.num_frame, padding=args.padding, chunk=args.batch,
                                           crop_border=args.crop_border, test_y_channel=args.test_y_channel, **plus_kw, **any_size)
             plus[folder] = (sum(p), len(p))
+            if niqe_params is not None:
+                q = niqe_scores(out, niqe_params, args.crop_border, args.batch)
+                niqe_plus[folder] = (sum(q), len(q))
+        del out
         if baseline:
             b = bicubic_baseline(lq, gt, args.hr_in, args.crop_border, args.test_y_channel, args.batch)
             base[folder] = (sum(b), len(b))
+            if niqe_params is not None:
+                q = bicubic_niqe(lq, gt, niqe_params, args.hr_in, args.crop_border, args.batch)
+                niqe_base[folder] = (sum(q), len(q))
         ds._cache.pop(folder, None)  # one clip resident at a time
 
     def merged(parts):
@@ -97,14 +132,31 @@ def evaluate(args, log=print):
 
     summary, base = merged(results), merged(base) if baseline else {}
     plus = merged(plus) if plus_kw else {}
+    with_niqe = niqe_params is not None
+    niqe = merged(niqe) if with_niqe else {}
+    niqe_base = merged(niqe_base) if with_niqe and baseline else {}
+    niqe_plus = merged(niqe_plus) if with_niqe and plus_kw else {}
+
+    def mean(d):
+        return sum(d.values()) / max(len(d), 1)
+
     if rank == 0:
         beside = (lambda v: f' (bicubic {v:.4f} dB)') if baseline else (lambda v: '')
         with_plus = (lambda v: f', self-ensemble {label} {v:.4f} dB') if plus_kw else (lambda v: '')
+        nan = float('nan')
+
+        def niqe_part(q, qp, qb):  # the NIQEs in the order of the PSNRs: model, second pass, baseline
+            if not with_niqe:
+                return ''
+            return (f'; NIQE {q:.4f}' + (f', self-ensemble {label} {qp:.4f}' if plus_kw else '') + (f' (bicubic {qb:.4f})' if baseline else ''))
+
         for k, v in summary.items():
-            log(f'{k}: PSNR {v:.4f} dB' + with_plus(plus.get(k, float('nan'))) + beside(base.get(k, float('nan'))))
+            log(f'{k}: PSNR {v:.4f} dB' + with_plus(plus.get(k, nan)) + beside(base.get(k, nan)) +
+                niqe_part(niqe.get(k, nan), niqe_plus.get(k, nan), niqe_base.get(k, nan)))
         if summary:  # the average of the per-folder averages
             log(f'average over {len(summary)} folder(s): {sum(summary.values()) / len(summary):.4f} dB' +
-                with_plus(sum(plus.values()) / max(len(plus), 1)) + beside(sum(base.values()) / max(len(base), 1)))
+                with_plus(sum(plus.values()) / max(len(plus), 1)) + beside(sum(base.values()) / max(len(base), 1)) +
+                niqe_part(mean(niqe), mean(niqe_plus), mean(niqe_base)))
         if getattr(args, 'json', None):
             import json
             record = {'psnr': summary, 'average': sum(summary.values()) / max(len(summary), 1),
@@ -115,6 +167,12 @@ def evaluate(args, log=print):
                     record.update(time_reverse=True)
             if baseline:
                 record.update(bicubic_psnr=base, bicubic_average=sum(base.values()) / max(len(base), 1))
+            if with_niqe:
+                record.update(niqe=niqe, niqe_average=mean(niqe))
+                if plus_kw:
+                    record.update(self_ensemble_niqe=niqe_plus, self_ensemble_niqe_average=mean(niqe_plus))
+                if baseline:
+                    record.update(bicubic_niqe=niqe_base, bicubic_niqe_average=mean(niqe_base))
             with open(args.json, 'w') as f:
                 json.dump(record, f, indent=1)
     return summary
@@ -128,6 +186,8 @@ def parse_args(argv=None):
     ap.add_argument('--degradation', choices=('bi', 'bd'), default='bi',
                     help="with --lq-from-gt: bi = MATLAB bicubic, 8-bit; bd = DUF's Gaussian blur and subsampling, float (SCALE 2, 3 or 4)")
     ap.add_argument('--bicubic-baseline', action='store_true', help='also report the PSNR of the bicubic enlargement of the LQ frames')
+    ap.add_argument('--niqe', default=None, metavar='PARAMS.npz',
+                    help="also report the no-reference NIQE of every output; PARAMS.npz is BasicSR's basicsr/metrics/niqe_pris_params.npz")
     ap.add_argument('--json', default=None, metavar='FILE', help='write the per-folder and average results there')
     ap.add_argument('--gt', required=True)
     ap.add_argument('--weights', default=None)

@@ -7,8 +7,10 @@ edvr_amd.y4m.restore_y4m: the frames go to the device as the decoder wrote them,
 restored by VideoRestorer with every frame's features extracted once, converted back (ops.rgb_to_yuv420) and written as they arrive -
 bounded memory, no intermediate files, one quantisation.  The network options are those of scripts/eval_video.py, `--batch` is the
 number of output frames per pass; `--matrix-in` / `--matrix-out` default to the player rule for each side's own size (BT.709 from 1280
-columns or 577 rows, BT.601 below), `--chroma` picks the chroma upsampling filter of the decode.  Everything this script prints goes to
-stderr: stdout may be the video.
+columns or 577 rows, BT.601 below), `--chroma` picks the chroma upsampling filter of the decode.  `--niqe PARAMS.npz` scores the result with
+the no-reference NIQE (metrics.calculate_niqe against BasicSR's niqe_pris_params.npz; lower is better) on the float32 frames before they
+are converted back, and the decoded input at its own size beside it where at least two 96 x 96 blocks fit; `--niqe-json FILE` writes
+both lists.  Everything this script prints goes to stderr: stdout may be the video.
 """
 import argparse
 import os
@@ -26,7 +28,8 @@ def restore(args, log=log):
     import torch
     from edvr_amd import EDVR
     from edvr_amd.optim import load_network
-    from edvr_amd.y4m import Y4MReader, restore_y4m
+    from edvr_amd import metrics, ops
+    from edvr_amd.y4m import FRAME, Y4MReader, default_matrix, restore_y4m
     device = torch.device('cuda', int(os.environ.get('LOCAL_RANK', 0)))
     torch.cuda.set_device(device)
     net = EDVR(num_in_ch=3, num_out_ch=3, num_feat=args.num_feat, num_frame=args.num_frame, deformable_groups=8,
@@ -43,6 +46,22 @@ def restore(args, log=log):
     try:
         reader = Y4MReader(src)
         log(f'{args.input}: {reader.width} x {reader.height}, F{reader.fps}, C{reader.chroma}, {reader.range} range')
+        niqe_path, niqe_out, niqe_in = getattr(args, 'niqe', None), [], []
+        if niqe_path:
+            params = metrics.load_niqe_params(niqe_path)
+            kwargs['on_chunk'] = lambda chunk: niqe_out.extend(metrics.calculate_niqe(chunk, params=params))
+            H, W = reader.height, reader.width
+            if (H // metrics.NIQE_BLOCK) * (W // metrics.NIQE_BLOCK) >= 2:  # one block leaves no covariance to estimate
+                read, matrix_in = reader.read, args.matrix_in or default_matrix(H, W)
+
+                def scored_read(k):  # the input as restore_y4m decodes it, scored at its own size
+                    host = read(k)
+                    if host.shape[0]:
+                        rgb = ops.yuv420_to_rgb(host.to(device, non_blocking=True)[:, len(FRAME):], H, W, matrix_in, reader.range, args.chroma)
+                        niqe_in.extend(metrics.calculate_niqe(rgb, params=params))
+                    return host
+
+                reader.read = scored_read
         t0 = time.time()
         with torch.no_grad():
             n = restore_y4m(net, reader, dst, matrix_in=args.matrix_in, matrix_out=args.matrix_out, chroma=args.chroma,
@@ -51,12 +70,31 @@ def restore(args, log=log):
         torch.cuda.synchronize()
         dt = time.time() - t0
         log(f'{args.output}: {n} frames in {dt:.1f} s ({n / max(dt, 1e-9):.2f} frames/s)')
+        if niqe_path:
+            report_niqe(args, niqe_out, niqe_in, log)
     finally:
         if src is not sys.stdin.buffer:
             src.close()
         if dst is not sys.stdout.buffer:
             dst.close()
     return n
+
+
+def report_niqe(args, niqe_out, niqe_in, log=log):
+    """Mean and per-frame NIQE of the output, and of the decoded input where it was scored; the same as JSON with --niqe-json."""
+    def mean(v):
+        return sum(v) / len(v) if v else float('nan')
+
+    log(f'{args.output}: NIQE {mean(niqe_out):.4f} over {len(niqe_out)} frames  [' + ' '.join(f'{v:.3f}' for v in niqe_out) + ']')
+    if niqe_in:
+        log(f'{args.input}: NIQE {mean(niqe_in):.4f} over {len(niqe_in)} frames  [' + ' '.join(f'{v:.3f}' for v in niqe_in) + ']')
+    else:
+        log(f'{args.input}: not scored (fewer than two 96 x 96 blocks fit its frames)')
+    if getattr(args, 'niqe_json', None):
+        import json
+        record = {'output': {'niqe': niqe_out, 'average': mean(niqe_out)}, 'input': {'niqe': niqe_in, 'average': mean(niqe_in)} if niqe_in else None}
+        with open(args.niqe_json, 'w') as f:
+            json.dump(record, f, indent=1)
 
 
 def parse_args(argv=None):
@@ -85,7 +123,12 @@ def parse_args(argv=None):
     ap.add_argument('--matrix-in', default=None, choices=['bt601', 'bt709'], help="the input's matrix (default: by its size)")
     ap.add_argument('--matrix-out', default=None, choices=['bt601', 'bt709'], help="the output's matrix (default: by ITS size)")
     ap.add_argument('--chroma', default='bilinear', choices=['bilinear', 'nearest'], help='chroma upsampling of the decode')
+    ap.add_argument('--niqe', default=None, metavar='PARAMS.npz',
+                    help="score the output (and the input, where two 96 x 96 blocks fit) with NIQE; PARAMS.npz is BasicSR's niqe_pris_params.npz")
+    ap.add_argument('--niqe-json', default=None, metavar='FILE', help='with --niqe: write the per-frame and mean NIQE there')
     args = ap.parse_args(argv)
+    if args.niqe_json is not None and args.niqe is None:
+        ap.error('--niqe-json needs --niqe')
     if args.tile_blend is not None and args.tile is None:
         ap.error('--tile-blend needs --tile')
     if args.tile_overlap is not None and args.tile is None:
