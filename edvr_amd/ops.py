@@ -1030,10 +1030,11 @@ def set_wgrad_algo(algo):
     return prev
 
 
-def conv2d_wgrad(x1, x2, x2_map, dz, co, ks, stride, want_db=False):
+def conv2d_wgrad(x1, x2, x2_map, dz, co, ks, stride, want_db=False, into=None):
     """dW (co, c1+c2, ks, ks) of the fused conv: Winograd-domain GEMM over tiles (3x3 / stride 1) or fp32 MFMA implicit GEMM
     over the pixel axis.  want_db: also return db = sum of dz over (n, h, w) -> (dw, db); the Winograd-domain kernel produces it
-    in the same two launches."""
+    in the same two launches.  into: a contiguous fp32 (co, c1+c2, ks, ks) tensor the gradient is ADDED to (into += dW, the
+    `accumulate` flag of the reduction pass) and that is returned in dW's place; db is never accumulated."""
     require_gpu(x1, x2, dz)
     L = _lib.lib()
     x1_in, x2_in, dz_in = x1, x2, dz
@@ -1044,7 +1045,13 @@ def conv2d_wgrad(x1, x2, x2_map, dz, co, ks, stride, want_db=False):
         x2 = _as_planes(x2)
         c2 = x2.shape[1]
     div, mul, add = x2_map if x2_map is not None else (0, 0, 0)
-    dw = torch.empty(co, c1 + c2, ks, ks, dtype=torch.float32, device=x1.device)
+    if into is None:
+        dw = torch.empty(co, c1 + c2, ks, ks, dtype=torch.float32, device=x1.device)
+    else:
+        require_gpu(into)
+        assert into.is_contiguous() and tuple(into.shape) == (co, c1 + c2, ks, ks), \
+            f'into {tuple(into.shape)} / strides {into.stride()}: expected a contiguous {(co, c1 + c2, ks, ks)}'
+        dw = into
     nbytes = L.edvr_conv2d_wgrad_ws_bytes(n, c1 + c2, h, w, co, ks, stride)
     ws = workspace(nbytes, x1.device)
     db = torch.empty(co, dtype=torch.float32, device=x1.device) if want_db else None
@@ -1060,7 +1067,7 @@ def conv2d_wgrad(x1, x2, x2_map, dz, co, ks, stride, want_db=False):
     pad = ks // 2
     ho, wo = (h + 2 * pad - ks) // stride + 1, (w + 2 * pad - ks) // stride + 1
     common = (_ptr(x1), _ptr(x2), _ptr(dz), _ptr(dw), c1, c2, n, h, w, co, ks, stride, _img_stride(x1), _img_stride(x2) if x2 is not None else 0,
-              div, mul, add, _img_stride(dz), 0, _ptr(db), _ptr(ws), nbytes)
+              div, mul, add, _img_stride(dz), 0 if into is None else 1, _ptr(db), _ptr(ws), nbytes)
     if split and ks == 1:  # the 1x1 GEMM is too cheap to pay for a reduction pass: split only with both bounds at hand
         bx, bz = get_bound(x1_in), get_bound(dz_in)
         split = bx is not None and bz is not None
@@ -1076,6 +1083,7 @@ def conv2d_wgrad(x1, x2, x2_map, dz, co, ks, stride, want_db=False):
     else:
         launch = lambda: _lib.check(L.edvr_conv2d_wgrad_f32(*common, _stream()), 'edvr_conv2d_wgrad_f32')
     _run(name, launch, 2.0 * n * ho * wo * co * (c1 + c2) * ks * ks, _nb(x1, dz, dw) + (4.0 * n * c2 * h * w if x2 is not None else 0.0))
+    void_bound(into)  # (rewritten through a raw pointer)
     return (dw, db) if want_db else dw
 
 

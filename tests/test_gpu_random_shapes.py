@@ -78,15 +78,23 @@ def test_winograd_wgrad_equals_direct_on_random_shapes(gpu, case):
     x2 = torch.randn(n, c2, h, w, generator=g).to(gpu) if c2 else None
     dz = torch.randn(n, co, h, w, generator=g).to(gpu)
     out = {}
-    for name, algo in (('direct', ops.CONV_DIRECT), ('winograd', ops.CONV_WINOGRAD), ('auto', ops.CONV_AUTO)):
+    # winograd32: the fp32 Winograd-domain kernel (ops.F4S_TRAINING off: what training runs on after the overflow guard fell back);
+    # with the default on, `winograd` and `auto` are its split-operand form
+    for name, algo in (('direct', ops.CONV_DIRECT), ('winograd', ops.CONV_WINOGRAD), ('auto', ops.CONV_AUTO), ('winograd32', ops.CONV_WINOGRAD)):
         prev = ops.set_wgrad_algo(algo)
+        prev_f4s = ops.set_f4s(training=False) if name == 'winograd32' else None
         try:
             out[name] = ops.conv2d_wgrad(x1, x2, None, dz, co, 3, 1, want_db=True)
         finally:
             ops.set_wgrad_algo(prev)
+            if prev_f4s is not None:
+                ops.set_f4s(*prev_f4s)
     (dw_d, db_d), (dw_w, db_w) = out['direct'], out['winograd']
     assert ((dw_w - dw_d).abs().max() / dw_d.abs().max().clamp_min(1e-30)).item() < 3e-5
     assert ((db_w - db_d).abs().max() / db_d.abs().max().clamp_min(1.0)).item() < 3e-5
+    dw_f, db_f = out['winograd32']
+    assert ((dw_f - dw_d).abs().max() / dw_d.abs().max().clamp_min(1e-30)).item() < 3e-5
+    assert ((db_f - db_d).abs().max() / db_d.abs().max().clamp_min(1.0)).item() < 3e-5
     dw_a, db_a = out['auto']  # AUTO may pick the VALU kernel (co <= 4), the Winograd-domain kernel or the direct one
     assert ((dw_a - dw_d).abs().max() / dw_d.abs().max().clamp_min(1e-30)).item() < 3e-5
     assert ((db_a - db_d).abs().max() / db_d.abs().max().clamp_min(1.0)).item() < 3e-5

@@ -20,11 +20,14 @@ CASES = [  # n, c1, c2, h, w, co, x2_map
 ]
 
 
-@pytest.mark.parametrize('algo', ['winograd', 'direct', 'auto'])
+@pytest.mark.parametrize('algo', ['winograd', 'direct', 'auto', 'winograd_fp32'])
 @pytest.mark.parametrize('case', CASES, ids=lambda c: 'n%d_c%d+%d_%dx%d_co%d%s' % (c[0], c[1], c[2], c[3], c[4], c[5], '_map' if c[6] else ''))
 def test_wgrad_matches_fp64_reference(gpu, case, algo):
     from edvr_amd import ops
     n, c1, c2, h, w, co, x2_map = case
+    fp32 = algo == 'winograd_fp32'  # the fp32 Winograd-domain kernel: `winograd` with ops.F4S_TRAINING off (else its split-operand form runs)
+    if fp32 and n * h * w >= 32 * 64 * 64:
+        pytest.skip('full-size rows: the other three algorithms cover the size; the fp32 kernel is the same code at any size')
     g = torch.Generator().manual_seed(n * 1000 + h * 10 + co)
     x1 = torch.randn(n, c1, h, w, generator=g)
     n2 = n if x2_map is None else n // x2_map[0]
@@ -36,12 +39,15 @@ def test_wgrad_matches_fp64_reference(gpu, case, algo):
     else:
         xcat = x1
     ref = torch.nn.grad.conv2d_weight(xcat.double(), (co, c1 + c2, 3, 3), dz.double(), padding=1)
-    prev = ops.set_wgrad_algo({'winograd': ops.CONV_WINOGRAD, 'direct': ops.CONV_DIRECT, 'auto': ops.CONV_AUTO}[algo])
+    prev = ops.set_wgrad_algo({'winograd': ops.CONV_WINOGRAD, 'direct': ops.CONV_DIRECT, 'auto': ops.CONV_AUTO, 'winograd_fp32': ops.CONV_WINOGRAD}[algo])
+    prev_f4s = ops.set_f4s(training=False) if fp32 else None
     try:
         dw, db = ops.conv2d_wgrad(x1.to(gpu), x2.to(gpu) if c2 else None, x2_map, dz.to(gpu), co, 3, 1, want_db=True)
         dw2 = ops.conv2d_wgrad(x1.to(gpu), x2.to(gpu) if c2 else None, x2_map, dz.to(gpu), co, 3, 1)
     finally:
         ops.set_wgrad_algo(prev)
+        if prev_f4s is not None:
+            ops.set_f4s(*prev_f4s)
     assert torch.equal(dw, dw2), 'split-K reduction must be deterministic'
     err = (dw.cpu().double() - ref).abs().max().item() / ref.abs().max().item()
     assert err < 2e-5, err
