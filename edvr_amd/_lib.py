@@ -48,6 +48,8 @@ PROTOTYPES = {
     'edvr_conv2d_abs_sum_supported': (i32, [ctypes.POINTER(ConvDesc)]),
     'edvr_conv2d_y_amax_supported': (i32, [ctypes.POINTER(ConvDesc)]),
     'edvr_conv2d_pre_supported': (i32, [ctypes.POINTER(ConvDesc)]),
+    'edvr_conv2d_f4s_set_lean': (i32, [i32]),
+    'edvr_conv2d_f4s_lean_items': (i32, [ctypes.POINTER(ConvDesc)]),
     'edvr_conv2d_kernel_name': (i32, [ctypes.POINTER(ConvDesc), ctypes.c_char_p, sz]),
     'edvr_conv2d_executed_flops': (i32, [ctypes.POINTER(ConvDesc), ctypes.POINTER(ctypes.c_double)]),
     'edvr_dcnv2_fwd_ws_bytes': (sz, [i32] * 12),

@@ -24,6 +24,7 @@
 // = (32-channel half, transform row), U straight from global memory in operand order; row pass in the multiplying waves,
 // column pass + epilogue + stores in the staging waves.  The V slab holds one dword (hi | lo << 16) where the fp32 kernel holds
 // a float: same LDS budget, same addresses.
+#include <atomic>
 #include <cstdlib>
 #include <type_traits>
 
@@ -68,6 +69,7 @@ struct WinoF4SArgs {
   const unsigned *U;  // header (16 dwords: s_U, 1 / s_U) + [co block 64][chunk of 8 channels][row 6][co half 2][position 6][lane 64][4 dwords]
   int ci, ci_real, cop, tiles_x, tiles_y, items;
   float ys, ys_gs;
+  int lean;  // the launch may use the lean column-pass instances (f4s_lean_launch: everything that does not depend on the item)
 };
 
 #define F4S_LDS_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
@@ -401,6 +403,9 @@ __global__ __launch_bounds__(1024, 1) void conv3x3_winograd_f4s_kernel(const Win
         auto prefetch = [&](int p) {  // (V) rows oy .. oy + 3 of the residual(s) / gate / pre of channel co_of(p)
           const int co = min(co_of(p), d.co - 1);
           if (V && !SHF && rq) {
+            // everything of the last phase has arrived (its residual is consumed): said HERE, hipcc does not place partial waits
+            // BETWEEN the four loads below, which made each wait out its predecessor's full latency (+14 % on a none + res1 layer)
+            if (!PRE) __builtin_amdgcn_s_waitcnt(0x0f70);  // vmcnt(0) alone, as an instruction the compiler's own wait placement sees
             const float *q1 = rq + (int64_t)co * plane + pix;
 #pragma unroll
             for (int i = 0; i < 4; ++i) rr[i] = i < rows_in ? *reinterpret_cast<const f32x4 *>(q1 + i * d.w) : f32x4{0.f, 0.f, 0.f, 0.f};
@@ -536,7 +541,124 @@ __global__ __launch_bounds__(1024, 1) void conv3x3_winograd_f4s_kernel(const Win
           }
         }
       };
-      if (pq && vec) column_pass(std::true_type{}, std::false_type{}, std::true_type{});
+      // Lean column pass: the same arithmetic for an item whose 64 channels x 32 tiles are all inside the tensor (no row, column or
+      // channel test, no exec masking), with one slope for the block and at most one addend.  y and the addend are addressed as
+      // buffers of the block's 64 planes: one per-lane offset per row, set up once per item, and a scalar offset that steps from
+      // phase to phase.  Every access is inside the block BY CONSTRUCTION (lane channel + phase channel <= 63, rows and columns
+      // inside the image; the host keeps 64 planes below 2^31 bytes): the buffer's range check compares the per-lane offset only,
+      // not the scalar one, and nothing here relies on it.  Bit-identical to the instances above.
+      // FRAGILE: the kernel sits at 128 of 128 scalar spill lanes (two vector registers; hipcc's "SGPRs Spill").  One more spilled scalar
+      // takes a third register, which does not fit beside the multiplying waves' chunk loop: ~120 vector registers are then spilled INSIDE
+      // that loop.  tests/test_abi.py sees this only as scratch above 20 B/lane.  The three empty asm statements of the lean pass (here and
+      // at the uniform factors below) are what keeps its loop-invariant scalars from being hoisted out of the item loop and spilled there:
+      // after any change to this function check -Rpass-analysis=kernel-resource-usage (SGPRs Spill <= 128, VGPRs Spill 4).
+      int lean_f = a.lean, pb = plane_bytes, w4 = d.w * 4;  // a.lean: 1 allowed | 2 y_amax | 4 relu / lrelu | 8 res1 | 16 pre (f4s_lean_launch)
+      asm volatile("" : "+s"(lean_f), "+s"(pb), "+s"(w4));
+      const bool lean_item = (lean_f & 1) && vec && e_ty0 + BH <= d.h && e_co_blk + 64 <= d.co && (!(lean_f & 4) || d.act_from <= e_co_blk);
+      auto column_pass_lean = [&](auto ACT_, auto ADD_) {
+        constexpr bool ACT = decltype(ACT_)::value;  // relu / lrelu, one slope for the whole block; false: no activation code
+        constexpr int ADD = decltype(ADD_)::value;   // 0 none, 1 res1 (after the activation, y * ys + res1), 2 pre (before it)
+        // (what follows is derived from opaque per-item copies `pb`, `w4` of the plane and row sizes: left to itself hipcc hoists every
+        // product of them out of the item loop, for each instance, and spills it there)
+        const int64_t blk = (int64_t)e_co_blk * (pb >> 2);
+        const __amdgpu_buffer_rsrc_t y_rs = uniform_rsrc(y + blk, 64 * pb);
+        const __amdgpu_buffer_rsrc_t q_rs = uniform_rsrc(ADD ? (ADD == 2 ? pq : r1) + blk : y, ADD ? 64 * pb : 0);
+        int voff[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) voff[i] = (co_t - e_co_blk) * pb + pix * 4 + i * w4;
+        // the uniform factors as VECTOR registers made here: as scalars their packed pairs are hoisted out of the item loop, one pair
+        // per instance, and every one of them is spilled (the multiplying waves' chunk loop leaves no room for another spill register)
+        float us1 = unscale, sl1 = slope, ys1 = a.ys;
+        asm volatile("" : "+v"(us1), "+v"(sl1), "+v"(ys1));
+        const f32x2 us = f32x2{us1, us1}, sl2 = f32x2{sl1, sl1};
+        const bool want_amax = (lean_f & 2) != 0;
+        const float *bp = bias_s + (co_t - e_co_blk);
+        const float *Xb = Xs + (cl8 * 32 + tile) * 4;
+        int x_step = XSZ / 2;
+        int soff = 0;         // byte offset of channel (p & 3) + 16 (p >> 2) of the block
+        int pmax = 0;         // y_amax over the RAW bit patterns: the largest non-negative one (signed maximum) ...
+        unsigned umax = 0u;   // ... and the negative one of largest magnitude, if there is any (unsigned maximum)
+        f32x4 rr[4];
+        if (ADD) {
+#pragma unroll
+          for (int i = 0; i < 4; ++i) rr[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(q_rs, voff[i], 0, 0));
+        }
+#pragma unroll 1
+        for (int p = 0; p < 8; ++p) {
+          F4S_BARRIER_AT(1);  // T of this phase is in its half of the exchange area
+          f32x4 T[6];
+#pragma unroll
+          for (int r = 0; r < 6; ++r) T[r] = *reinterpret_cast<const f32x4 *>(Xb + r * (8 * 32 * 4));
+          const float b = *bp;
+          f32x4 Y[4];
+#pragma unroll
+          for (int jp = 0; jp < 2; ++jp) {
+            auto col2 = [&](int r) { return f32x2{T[r][2 * jp], T[r][2 * jp + 1]}; };
+            const f32x2 t0 = col2(0), t1 = col2(1), t2 = col2(2), t3 = col2(3), t4 = col2(4), t5 = col2(5);
+            const f32x2 s1 = t1 + t2, d1 = t1 - t2, s2 = t3 + t4, d2 = t3 - t4;
+            const f32x2 bb = f32x2{b, b};
+            f32x2 y0 = (t0 + s1 + s2) * us + bb;
+            f32x2 y1 = (2.f * d2 + d1) * us + bb;
+            f32x2 y2 = (4.f * s2 + s1) * us + bb;
+            f32x2 y3 = (8.f * d2 + d1 + t5) * us + bb;
+            if (ADD == 2) {
+              y0 += f32x2{rr[0][2 * jp], rr[0][2 * jp + 1]};
+              y1 += f32x2{rr[1][2 * jp], rr[1][2 * jp + 1]};
+              y2 += f32x2{rr[2][2 * jp], rr[2][2 * jp + 1]};
+              y3 += f32x2{rr[3][2 * jp], rr[3][2 * jp + 1]};
+            }
+            if (ACT) {
+              const f32x2 z0 = y0 * sl2, z1 = y1 * sl2, z2 = y2 * sl2, z3 = y3 * sl2;
+              y0 = f32x2{max_raw_s(y0[0], z0[0]), max_raw_s(y0[1], z0[1])};
+              y1 = f32x2{max_raw_s(y1[0], z1[0]), max_raw_s(y1[1], z1[1])};
+              y2 = f32x2{max_raw_s(y2[0], z2[0]), max_raw_s(y2[1], z2[1])};
+              y3 = f32x2{max_raw_s(y3[0], z3[0]), max_raw_s(y3[1], z3[1])};
+            }
+            Y[0][2 * jp] = y0[0]; Y[0][2 * jp + 1] = y0[1];
+            Y[1][2 * jp] = y1[0]; Y[1][2 * jp + 1] = y1[1];
+            Y[2][2 * jp] = y2[0]; Y[2][2 * jp + 1] = y2[1];
+            Y[3][2 * jp] = y3[0]; Y[3][2 * jp + 1] = y3[1];
+          }
+          if (ADD == 1) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+#pragma unroll
+              for (int jj = 0; jj < 4; ++jj) Y[i][jj] = __builtin_fmaf(Y[i][jj], ys1, rr[i][jj]);
+          }
+#pragma unroll
+          for (int i = 0; i < 4; ++i) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(i32x4, Y[i]), y_rs, voff[i], soff, 0);
+          soff += (p & 3) == 3 ? 13 * pb : pb;
+          bp += (p & 3) == 3 ? 13 : 1;
+          Xb += x_step;
+          x_step = -x_step;
+          if (ADD && p != 7) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) rr[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(q_rs, voff[i], soff, 0));
+          }
+          if (want_amax) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+              const i32x4 yb = __builtin_bit_cast(i32x4, Y[i]);
+              pmax = max(max(pmax, yb[0]), yb[1]);
+              pmax = max(max(pmax, yb[2]), yb[3]);
+              umax = max(max(umax, (unsigned)yb[0]), (unsigned)yb[1]);
+              umax = max(max(umax, (unsigned)yb[2]), (unsigned)yb[3]);
+            }
+          }
+        }
+        // = the maximum of (bits & 0x7fffffff): pmax is the largest pattern of a non-negative value (or negative: none stored), umax
+        // has its sign bit set exactly when a negative value was stored and is then the one of largest magnitude
+        amx = max(amx, max((unsigned)max(pmax, 0), umax & 0x7fffffffu));
+      };
+      if (lean_item) {
+        auto with_add = [&](auto ACT_) {
+          if (lean_f & 16) column_pass_lean(ACT_, std::integral_constant<int, 2>{});
+          else if (lean_f & 8) column_pass_lean(ACT_, std::integral_constant<int, 1>{});
+          else column_pass_lean(ACT_, std::integral_constant<int, 0>{});
+        };
+        if (lean_f & 4) with_add(std::true_type{});
+        else with_add(std::false_type{});
+      } else if (pq && vec) column_pass(std::true_type{}, std::false_type{}, std::true_type{});
       else if (pq) column_pass(std::false_type{}, std::false_type{}, std::true_type{});
       else if (vec && shuffle) column_pass(std::true_type{}, std::true_type{}, std::false_type{});
       else if (vec) column_pass(std::true_type{}, std::false_type{}, std::false_type{});
@@ -753,6 +875,45 @@ static int f4s_geometry(const edvr_conv2d_desc &d, int &tiles_x, int &tiles_y, b
   return tiles_x * tiles_y * cdiv(d.co, 64) * d.n;
 }
 
+// EDVR_F4S_LEAN=0 (or edvr_conv2d_f4s_set_lean(0)): every item takes the generic column-pass instances (A/B switch; the results are the same bits)
+static std::atomic<int> &f4s_lean_switch() {
+  static std::atomic<int> on([]() {
+    const char *e = getenv("EDVR_F4S_LEAN");
+    return (e && e[0] == '0') ? 0 : 1;
+  }());
+  return on;
+}
+
+// what the lean column pass needs of a LAUNCH (its per-item conditions are f4s_lean_item's): plain NCHW store, no gate / abs_sum / res2,
+// none / relu / lrelu, at most one addend (res1 and pre exclude each other: winograd_f4s_supported), and the 64 planes of a channel
+// block within the 2^31 bytes a buffer offset spans
+// Returns WinoF4SArgs::lean: 0, or 1 | 2 (y_amax) | 4 (relu / lrelu) | 8 (res1) | 16 (pre).
+static int f4s_lean_launch(const edvr_conv2d_desc &d) {
+  if (!f4s_lean_switch().load(std::memory_order_relaxed)) return 0;
+  if (d.out_mode != EDVR_OUT_NCHW || d.gate || d.abs_sum || d.res2) return 0;
+  if (d.act != EDVR_ACT_NONE && d.act != EDVR_ACT_RELU && d.act != EDVR_ACT_LRELU) return 0;
+  if ((int64_t)d.h * d.w * 4 * 64 >= ((int64_t)1 << 31)) return 0;
+  return 1 | (d.y_amax ? 2 : 0) | (d.act != EDVR_ACT_NONE ? 4 : 0) | (d.pre ? 16 : (d.res1 ? 8 : 0));
+}
+
+// ... and of an ITEM (the kernel's `lean_item`): the block of bw x bh pixels x 64 channels inside the tensor, one slope for the block
+static bool f4s_lean_item(const edvr_conv2d_desc &d, int co_blk, int ty0, int tx0, int bw, int bh) {
+  return tx0 + bw <= d.w && ty0 + bh <= d.h && co_blk + 64 <= d.co && (d.act == EDVR_ACT_NONE || d.act_from <= co_blk);
+}
+
+int winograd_f4s_lean_items(const edvr_conv2d_desc &d) {
+  if (!f4s_lean_launch(d)) return 0;
+  int tiles_x, tiles_y;
+  bool tx8;
+  f4s_geometry(d, tiles_x, tiles_y, tx8);
+  const int bw = tx8 ? 32 : 64, bh = tx8 ? 16 : 8;
+  int per_img = 0;
+  for (int cb = 0; cb < d.co; cb += 64)
+    for (int ty = 0; ty < tiles_y; ++ty)
+      for (int tx = 0; tx < tiles_x; ++tx) per_img += f4s_lean_item(d, cb, ty * bh, tx * bw, bw, bh) ? 1 : 0;
+  return per_img * d.n;
+}
+
 // flops the f16 matrix pipe executes for `d`, padding included: per item and 8-channel chunk 144 v_mfma_f32_32x32x16_f16 of 32768 flops
 double winograd_f4s_executed_flops(const edvr_conv2d_desc &d) {
   int tx, ty;
@@ -772,6 +933,7 @@ int winograd_f4s_launch(const edvr_conv2d_desc &d, hipStream_t stream) {
   a.ys_gs = a.ys * d.gate_slope;
   bool tx8;
   a.items = f4s_geometry(d, a.tiles_x, a.tiles_y, tx8);
+  a.lean = f4s_lean_launch(d);
   static const int n_cu = []() {
     int dev = 0, n = 256;
     hipDeviceProp_t prop;
@@ -798,6 +960,15 @@ int edvr_f4s_prof_read(unsigned long long *host, int reset) {  // host[16 * 8]
   return rc;
 }
 #endif
+
+int edvr_conv2d_f4s_set_lean(int on) { return edvr::f4s_lean_switch().exchange(on ? 1 : 0); }
+
+int edvr_conv2d_f4s_lean_items(const edvr_conv2d_desc *d) {
+  if (!d) return 0;
+  const bool scaled = d->y_scale != 0.f && d->y_scale != 1.f;
+  if ((!d->gate && !scaled && edvr::conv_small_eligible(*d)) || !edvr::winograd_f4s_eligible(*d)) return 0;  // edvr_conv2d_f32's own order
+  return edvr::winograd_f4s_lean_items(*d);
+}
 
 size_t edvr_conv2d_packed_weight_f4s_elems(int co, int ci) { return 16 + (size_t)((co + 63) / 64 * 64) * ((ci + 7) / 8 * 8) * 36; }
 

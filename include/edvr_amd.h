@@ -212,6 +212,13 @@ int edvr_conv2d_abs_sum_supported(const edvr_conv2d_desc *d);
 /* 1 if edvr_conv2d_f32 would run `d` WITH a `pre` operand on a kernel whose epilogue takes it (an F(4x4) Winograd kernel, NCHW output, no
  * gate, no residuals), else 0.  Of the pointers of `d` only those that select the kernel need to be set (wpk_f4 / wpk_f4s, x_amax). */
 int edvr_conv2d_pre_supported(const edvr_conv2d_desc *d);
+/* The split-operand F(4x4) kernel (csrc/winograd_f4s.hip) runs the output pass of a work item (64 channels x 32 tiles) that lies wholly
+ * inside the tensor on lean instances: plain NCHW store, act none / relu / lrelu with one slope for the block, at most one addend
+ * (res1 or pre), no gate / res2 / abs_sum.  Same bits as the generic instances.  edvr_conv2d_f4s_set_lean(0) forces the generic ones
+ * (as EDVR_F4S_LEAN=0 does from the start) and returns the previous setting; edvr_conv2d_f4s_lean_items: how many items of the launch
+ * edvr_conv2d_f32 would make for `d` take a lean instance - 0 when that launch is not the split-operand kernel's.  Host only. */
+int edvr_conv2d_f4s_set_lean(int on);
+int edvr_conv2d_f4s_lean_items(const edvr_conv2d_desc *d);
 /* Name of the kernel template instantiation edvr_conv2d_f32 would launch for `d` (as rocprofv3 prints it),
  * written to buf; returns 0 or EDVR_ERR_*.  Measurement aid only. */
 int edvr_conv2d_kernel_name(const edvr_conv2d_desc *d, char *buf, size_t buf_len);
