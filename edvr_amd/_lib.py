@@ -23,7 +23,7 @@ class ConvDesc(ctypes.Structure):
         ('res2', vp), ('res1_img_stride', i64), ('res2_img_stride', i64), ('y', vp), ('y_img_stride', i64),
         ('out_mode', i32), ('algo', i32), ('gate', vp), ('gate_img_stride', i64), ('gate_slope', f32), ('y_scale', f32),
         ('wpk_f4', vp), ('abs_sum', vp), ('abs_sum_channels', i32), ('wpk_f4s', vp), ('x_amax', vp), ('y_amax', vp),
-        ('pre', vp), ('pre_img_stride', i64), ('pre_div', i32), ('pre_mul', i32), ('pre_add', i32), ('pre_n', i32),
+        ('pre', vp), ('pre_img_stride', i64), ('pre_div', i32), ('pre_mul', i32), ('pre_add', i32), ('pre_n', i32), ('wpk_ds', vp),
     ]
 
 
@@ -40,6 +40,8 @@ PROTOTYPES = {
     'edvr_conv2d_pack_weight_f4s_f32': (i32, [vp, vp, i32, i32, i32, vp]),
     'edvr_conv2d_packed_weight_1x1s_elems': (sz, [i32, i32]),
     'edvr_conv2d_pack_weight_1x1s_f32': (i32, [vp, vp, i32, i32, vp]),
+    'edvr_conv2d_packed_weight_ds_elems': (sz, [i32, i32, i32]),
+    'edvr_conv2d_pack_weight_ds_f32': (i32, [vp, vp, i32, i32, i32, vp]),
     'edvr_amax_f32': (i32, [vp, vp, i32, i64, i64, vp]),
     'edvr_pack_job_bytes': (sz, []),
     'edvr_conv2d_pack_weights_multi': (i32, [vp, i32, i32, i32, vp]),

@@ -76,6 +76,13 @@ int conv1x1_launch(const edvr_conv2d_desc &d, hipStream_t stream);
 bool conv1x1_split_eligible(const edvr_conv2d_desc &d);
 int conv1x1_split_launch(const edvr_conv2d_desc &d, hipStream_t stream);
 
+// conv2d_s.hip: the direct kernel of conv2d.hip with split fp32 operands on the f16 matrix pipe (needs d.wpk_ds and d.x_amax): takes
+// what would reach conv2d_mfma_kernel otherwise (NCHW store, no gate / pre / abs_sum / y_scale, algo != EDVR_CONV_DIRECT)
+bool conv2d_split_eligible(const edvr_conv2d_desc &d);
+int conv2d_split_launch(const edvr_conv2d_desc &d, hipStream_t stream);
+// ... and its weight packing, header (s_W, 1 / s_W) + [quads][kk taps][cop][4 channels] dwords; conv1x1_s.hip's layout with kk = 1
+int conv_split_pack(const float *w, unsigned *wq, int co, int ci, int kk, int cop, int quads, hipStream_t stream);
+
 // wgrad.hip: out[i] (+)= sum_k ws[k * total + i]
 int reduce_partials_launch(const float *ws, float *out, int64_t total, int parts, int accumulate, hipStream_t stream,
                            const float *ws2 = nullptr, float *out2 = nullptr, int total2 = 0, int parts2 = 0);  // second, small array in the same launch

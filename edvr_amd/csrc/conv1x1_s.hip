@@ -22,22 +22,6 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef int c1s_i32x4 __attribute__((ext_vector_type(4)));
 typedef _Float16 c1s_f16x8 __attribute__((ext_vector_type(8)));
 
-namespace {
-__device__ __forceinline__ void c1s_split4(const float (&x)[4], float s, unsigned (&o)[4]) {
-  asm volatile(
-      "v_fma_mixlo_f16 %0, %4, %8, 0\n\tv_fma_mixlo_f16 %1, %5, %8, 0\n\tv_fma_mixlo_f16 %2, %6, %8, 0\n\tv_fma_mixlo_f16 %3, %7, %8, 0\n\t"
-      "v_fma_mixhi_f16 %0, %4, %8, -%0 op_sel_hi:[0,0,1]\n\tv_fma_mixhi_f16 %1, %5, %8, -%1 op_sel_hi:[0,0,1]\n\t"
-      "v_fma_mixhi_f16 %2, %6, %8, -%2 op_sel_hi:[0,0,1]\n\tv_fma_mixhi_f16 %3, %7, %8, -%3 op_sel_hi:[0,0,1]"
-      : "=&v"(o[0]), "=&v"(o[1]), "=&v"(o[2]), "=&v"(o[3])
-      : "v"(x[0]), "v"(x[1]), "v"(x[2]), "v"(x[3]), "s"(s));
-}
-// 2^e with amax * 2^e < 2^15: amax = m 2^k, m in [1, 2) -> e = 14 - k (clamped: a zero / tiny / huge bound stays a normal number)
-__device__ __forceinline__ float c1s_scale(float amax) {
-  const int be = (int)((__builtin_bit_cast(unsigned, amax) >> 23) & 255u);
-  return __builtin_bit_cast(float, (unsigned)min(max(127 + 14 - (be - 127), 7), 215) << 23);
-}
-}  // namespace
-
 struct Conv1x1SArgs {
   edvr_conv2d_desc d;
   const unsigned *wq;          // header (16 dwords: s_W, 1 / s_W) + [channel quad cip / 4][cop][4] dwords
@@ -52,7 +36,7 @@ __global__ __launch_bounds__(256, 2) void conv1x1_split_kernel(const Conv1x1SArg
   constexpr int OOB = (int)0x80000000;
   __shared__ __attribute__((aligned(16))) unsigned wsm[2][CK * MB];
   const edvr_conv2d_desc &d = a.d;
-  const float s_x = c1s_scale(__builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, *d.x_amax))));
+  const float s_x = split_scale(__builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, *d.x_amax))));
   const float inv_sw = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane((int)a.wq[1]));
   const int tid = threadIdx.x, lane = tid & 63, half = lane >> 5, j = lane & 31;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -130,7 +114,7 @@ __global__ __launch_bounds__(256, 2) void conv1x1_split_kernel(const Conv1x1SArg
 #pragma unroll
       for (int m = 0; m < MT; ++m) av[m] = *reinterpret_cast<const c1s_i32x4 *>(ws + ((2 * s) * MB + m * 32) * 4);
       unsigned pk[4];
-      c1s_split4(bq[s % DEPTH], s_x, pk);
+      split4_f16x2(bq[s % DEPTH], s_x, pk);
       load_b(ch * (CK / 8) + s + DEPTH, bq[s % DEPTH]);  // same registers, DEPTH k-steps ahead
       c1s_i32x4 b, br;
 #pragma unroll
@@ -173,42 +157,10 @@ __global__ __launch_bounds__(256, 2) void conv1x1_split_kernel(const Conv1x1SArg
         }
       }
   }
-  if (d.y_amax) {  // max |y| for the next layer's bound: one atomic per wave (non-negative floats order as their bit patterns)
+  if (d.y_amax) {  // max |y| for the next layer's bound: at most one atomic per wave (non-negative floats order as their bit patterns)
 #pragma unroll
     for (int sh = 32; sh > 0; sh >>= 1) vmax = max(vmax, (unsigned)__shfl_xor((int)vmax, sh));
-    if (lane == 0) atomicMax(reinterpret_cast<unsigned *>(d.y_amax), vmax);
-  }
-}
-
-// header[0] = s_W = 2^e with max|w| s_W in [2^14, 2^15), header[1] = 1 / s_W
-__global__ __launch_bounds__(1024) void conv1x1_split_scale_kernel(const float *__restrict__ w, unsigned *__restrict__ wq, int64_t total) {
-  __shared__ float red[16];
-  float m = 0.f;
-  for (int64_t i = threadIdx.x; i < total; i += 1024) m = fmaxf(m, fabsf(w[i]));
-#pragma unroll
-  for (int sh = 32; sh > 0; sh >>= 1) m = fmaxf(m, __shfl_xor(m, sh));
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    for (int i = 1; i < 16; ++i) m = fmaxf(m, red[i]);
-    const unsigned field = f4s_weight_scale_field(__builtin_bit_cast(unsigned, m));
-    wq[0] = field << 23;
-    wq[1] = (254u - field) << 23;
-    for (int i = 2; i < 16; ++i) wq[i] = 0u;
-  }
-}
-
-// w (co, ci) -> [channel quad][cop][4 channels] dwords (hi | lo << 16) of w * s_W, zero beyond co / ci
-__global__ void conv1x1_split_pack_kernel(const float *__restrict__ w, unsigned *__restrict__ wq, int co, int ci, int cop, int quads) {
-  const float s_w = __builtin_bit_cast(float, wq[0]);
-  const int64_t total = (int64_t)quads * cop;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-    const int o = (int)(i % cop), q = (int)(i / cop);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const int c = 4 * q + e;
-      wq[16 + i * 4 + e] = (o < co && c < ci) ? split_f16x2(w[(int64_t)o * ci + c], s_w) : 0u;
-    }
+    if (lane == 0) publish_amax(d.y_amax, vmax);
   }
 }
 
@@ -269,10 +221,7 @@ int edvr_conv2d_pack_weight_1x1s_f32(const float *w, void *wpk, int co, int ci, 
   hipStream_t stream = as_stream(stream_);
   unsigned *wq = static_cast<unsigned *>(wpk);
   const int cop = (co + 127) / 128 * 128, quads = (ci + 63) / 64 * 16;
-  hipLaunchKernelGGL(conv1x1_split_scale_kernel, dim3(1), dim3(1024), 0, stream, w, wq, (int64_t)co * ci);
-  const int64_t total = (int64_t)quads * cop;
-  hipLaunchKernelGGL(conv1x1_split_pack_kernel, dim3((unsigned)std::min<int64_t>(cdiv64(total, 256), 2048)), dim3(256), 0, stream, w, wq, co, ci, cop, quads);
-  return check_launch("conv1x1_split_pack_kernel");
+  return conv_split_pack(w, wq, co, ci, 1, cop, quads, stream);  // (conv2d_s.hip: the layout of its kernel with one tap)
 }
 
 }  // extern "C"

@@ -372,7 +372,7 @@ int conv2d_launch(const edvr_conv2d_desc &d, hipStream_t stream) {
     set_error("conv2d: abs_sum is an epilogue of the F(4x4) Winograd kernel's NCHW store only (ask edvr_conv2d_abs_sum_supported)");
     return EDVR_ERR_UNSUPPORTED;
   }
-  if (d.y_amax && (conv_small_eligible(d) || !(winograd_f4s_eligible(d) || conv1x1_split_eligible(d)))) {
+  if (d.y_amax && !conv2d_split_eligible(d) && (conv_small_eligible(d) || !(winograd_f4s_eligible(d) || conv1x1_split_eligible(d)))) {
     set_error("conv2d: y_amax is an epilogue of the split-operand kernels only (ask edvr_conv2d_y_amax_supported)");
     return EDVR_ERR_UNSUPPORTED;
   }
@@ -398,6 +398,7 @@ int conv2d_launch(const edvr_conv2d_desc &d, hipStream_t stream) {
     const float *U = d.wpk + direct_packed_elems(d.co, a.ci, 3);
     return winograd_launch(d, U, round_up(d.co, 64), stream);
   }
+  if (conv2d_split_eligible(d)) return conv2d_split_launch(d, stream);  // (only what reaches launch_mt below)
   if (d.ks == 3 && d.stride == 1) return launch_mt<3, 1>(a, stream);
   if (d.ks == 3 && d.stride == 2) return launch_mt<3, 2>(a, stream);
   if (conv1x1_split_eligible(d)) return conv1x1_split_launch(d, stream);
@@ -458,7 +459,7 @@ int edvr_conv2d_kernel_name(const edvr_conv2d_desc *d, char *buf, size_t buf_len
   }
   const int mt = d->co >= 128 ? 4 : edvr::cdiv(d->co, 32);  // the launch carrying most of the work
   const int ns = mt >= 3 ? 1 : 2;
-  snprintf(buf, buf_len, "conv2d_mfma_kernel<%d, %d, %d, %d, %d>", d->ks, d->stride, mt, edvr::use_sw16(ho, wo, ns) ? 16 : 32, ns);
+  snprintf(buf, buf_len, "%s<%d, %d, %d, %d, %d>", edvr::conv2d_split_eligible(*d) ? "conv2d_split_kernel" : "conv2d_mfma_kernel", d->ks, d->stride, mt, edvr::use_sw16(ho, wo, ns) ? 16 : 32, ns);
   return EDVR_OK;
 }
 
@@ -470,6 +471,7 @@ int edvr_conv2d_executed_flops(const edvr_conv2d_desc *d, double *flops) {
   else if (!edvr::conv_small_eligible(*d) && edvr::winograd_f4_eligible(*d)) *flops = edvr::winograd_f4_executed_flops(*d);
   else if (!edvr::conv_small_eligible(*d) && edvr::winograd_eligible(*d)) *flops = edvr::winograd_executed_flops(*d);
   else if (edvr::conv1x1_split_eligible(*d)) *flops = 8.0 * d->n * ho * wo * d->co * (d->c1 + d->c2);  // four f16 products per fp32 one
+  else if (edvr::conv2d_split_eligible(*d)) *flops = 8.0 * d->n * ho * wo * d->co * (d->c1 + d->c2) * d->ks * d->ks;  // the same
   else *flops = 2.0 * d->n * ho * wo * d->co * (d->c1 + d->c2) * d->ks * d->ks;  // direct algorithm (tile padding not counted)
   return EDVR_OK;
 }
@@ -491,6 +493,7 @@ int edvr_conv2d_pre_supported(const edvr_conv2d_desc *d) {
 
 int edvr_conv2d_y_amax_supported(const edvr_conv2d_desc *d) {
   if (!d) return 0;
+  if (edvr::conv2d_split_eligible(*d)) return 1;
   return (!edvr::conv_small_eligible(*d) && (edvr::winograd_f4s_eligible(*d) || edvr::conv1x1_split_eligible(*d))) ? 1 : 0;
 }
 

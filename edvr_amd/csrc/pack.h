@@ -96,6 +96,29 @@ __device__ __forceinline__ unsigned split_f16x2(float x, float s) {
   return __builtin_bit_cast(unsigned, pk_f16x2{hi, lo});
 }
 
+// the same for four activations at once, in the two instructions per element the hardware has for it (s in a scalar register)
+__device__ __forceinline__ void split4_f16x2(const float (&x)[4], float s, unsigned (&o)[4]) {
+  asm volatile(
+      "v_fma_mixlo_f16 %0, %4, %8, 0\n\tv_fma_mixlo_f16 %1, %5, %8, 0\n\tv_fma_mixlo_f16 %2, %6, %8, 0\n\tv_fma_mixlo_f16 %3, %7, %8, 0\n\t"
+      "v_fma_mixhi_f16 %0, %4, %8, -%0 op_sel_hi:[0,0,1]\n\tv_fma_mixhi_f16 %1, %5, %8, -%1 op_sel_hi:[0,0,1]\n\t"
+      "v_fma_mixhi_f16 %2, %6, %8, -%2 op_sel_hi:[0,0,1]\n\tv_fma_mixhi_f16 %3, %7, %8, -%3 op_sel_hi:[0,0,1]"
+      : "=&v"(o[0]), "=&v"(o[1]), "=&v"(o[2]), "=&v"(o[3])
+      : "v"(x[0]), "v"(x[1]), "v"(x[2]), "v"(x[3]), "s"(s));
+}
+// activation scale 2^e with amax * 2^e < 2^15: amax = m 2^k, m in [1, 2) -> e = 14 - k (clamped: a zero / tiny / huge bound stays a normal number)
+__device__ __forceinline__ float split_scale(float amax) {
+  const int be = (int)((__builtin_bit_cast(unsigned, amax) >> 23) & 255u);
+  return __builtin_bit_cast(float, (unsigned)min(max(127 + 14 - (be - 127), 7), 215) << 23);
+}
+
+// Fold a wave's max |y| (bit pattern of a non-negative float; NaNs order above +inf) into the launch's `y_amax` slot, from ONE lane.  A
+// launch of thousands of workgroups would queue as many atomics on one address in L2 (on a 10 x 128 x 180 x 320 output they cost a
+// third of a 1x1 conv).  The slot only grows, so a wave that does not exceed what it reads there (device scope, past L1) has nothing to add.
+__device__ __forceinline__ void publish_amax(float *y_amax, unsigned vmax) {
+  unsigned *slot = reinterpret_cast<unsigned *>(y_amax);
+  if (vmax > __hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(slot, vmax);
+}
+
 // biased exponent field of s_U = 2^e with max|w| s_U in [2^14, 2^15) (|G g G^T| <= max|w|): m = f 2^k, f in [1, 2) -> e = 14 - k
 __device__ __forceinline__ unsigned f4s_weight_scale_field(unsigned amax_bits) {
   const int be = (int)((amax_bits >> 23) & 255u);

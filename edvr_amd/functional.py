@@ -61,10 +61,17 @@ def conv(m, x, *, x2=None, x2_map=None, act=ACT_NONE, act_from=0, res1=None, res
     wf4s = ops.pack_conv_weight(m.weight, f4s=True, ci_range=ci_range) if f4s else None
     if ops.F4S_INFERENCE and ks == 1 and stride == 1 and cin >= 320 and x.shape[1] % 8 == 0 and cin % 8 == 0:
         wf4s = ops.pack_conv_weight(m.weight, f4s=True, ci_range=ci_range)  # the streaming 1x1 kernel's split form (csrc/conv1x1_s.hip; the C side decides)
+    # the split-operand form of the DIRECT kernel (csrc/conv2d_s.hip) for what neither a Winograd nor the streaming kernel takes: 3x3 /
+    # stride 2 (the pyramid), 3x3 / stride 1 on at most 8 input channels (conv_first: one chunk, what was measured), 1x1 below 320
+    # channels (TSA); the C side decides.  Other small 3x3 / stride-1 layers (narrow test networks) keep the fp32 kernels.
+    wds = None
+    if ops.F4S_INFERENCE and m.out_channels > 4 and (x2 is None or x.shape[1] % 4 == 0) and (
+            (ks == 3 and (stride == 2 or cin <= 8)) or (ks == 1 and cin < 320)):
+        wds = ops.pack_conv_weight(m.weight, ds=True, ci_range=ci_range)
     bias = m.bias.detach() if (m.bias is not None and use_bias) else None
     r = ops.conv2d(x, wpk, bias, m.out_channels, ks, x2=x2, x2_map=x2_map, stride=stride, act=act, act_from=act_from,
                    res1=res1, res2=res2, out_mode=out_mode, y_scale=y_scale, wpk_f4=wf4, abs_sum_channels=abs_sum_channels,
-                   wpk_f4s=wf4s, pre=pre, pre_map=pre_map, out=out)
+                   wpk_f4s=wf4s, pre=pre, pre_map=pre_map, out=out, wpk_ds=wds)
     y = r[0] if abs_sum_channels > 0 else r
     if ops.F4S_INFERENCE and ops.get_bound(y) is None:  # a kernel without the y_amax epilogue: the bound from the weights' norms
         # (of the WHOLE weight also where a channel range of it ran: a sum over more channels, still a bound)

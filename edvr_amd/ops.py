@@ -92,15 +92,18 @@ def workspace(nbytes, device, tag=None):
 _PACKED = {}  # id(parameter) -> (weakref, {transpose_flip: (version, packed, data_ptr)})
 
 
-def pack_conv_weight(weight, transpose_flip=False, f4=False, f4s=False, ci_range=None):
+def pack_conv_weight(weight, transpose_flip=False, f4=False, f4s=False, ci_range=None, ds=False):
     """(co, ci, k, k) parameter -> MFMA-friendly [ci_pad][k*k][co_pad] array, cached per parameter version.
     ci_range = (lo, hi): the packing of weight[:, lo:hi] alone - one half of a two-input conv whose other half is convolved apart
     (conv2d's `pre`); cached in a slot of its own under the same parameter, version and pointer, so it is invalidated and pinned with the rest.
     f4: the F(4x4,3x3) Winograd weights of a 3x3 kernel instead (conv2d's `wpk_f4`), a separate buffer with its own cache slot.
     f4s: the same weights for the split-operand kernel (conv2d's `wpk_f4s`: scaled, split into f16 (hi, lo) pairs; int32 buffer); of a
-    1x1 kernel: the split-operand packing of the streaming 1x1 kernel (csrc/conv1x1_s.hip), same field."""
+    1x1 kernel: the split-operand packing of the streaming 1x1 kernel (csrc/conv1x1_s.hip), same field.
+    ds: the split-operand packing of the DIRECT kernel (conv2d's `wpk_ds`, csrc/conv2d_s.hip: 3x3 or 1x1, forward orientation only; int32
+    buffer), a cache slot of its own."""
     require_gpu(weight)
-    key, wid, ver = (bool(transpose_flip), 2 if f4s else bool(f4)), id(weight), weight._version
+    assert not (ds and (f4 or f4s or transpose_flip)), 'ds is a layout of its own, of the forward orientation'
+    key, wid, ver = (bool(transpose_flip), 3 if ds else (2 if f4s else bool(f4))), id(weight), weight._version
     if ci_range is not None:
         assert not transpose_flip, 'input-channel ranges serve forward convs'
         key = key + ((int(ci_range[0]), int(ci_range[1])),)
@@ -121,7 +124,10 @@ def pack_conv_weight(weight, transpose_flip=False, f4=False, f4s=False, ci_range
     o, i, k, k2 = w.shape
     assert k == k2, 'square kernels only'
     co, ci = (i, o) if transpose_flip else (o, i)
-    if f4s and k == 1:  # the split-operand packing of a 1x1 conv (csrc/conv1x1_s.hip)
+    if ds:
+        out = torch.empty(L.edvr_conv2d_packed_weight_ds_elems(co, ci, k), dtype=torch.int32, device=w.device)
+        _lib.check(L.edvr_conv2d_pack_weight_ds_f32(_ptr(w), _ptr(out), co, ci, k, _stream()), 'edvr_conv2d_pack_weight_ds_f32')
+    elif f4s and k == 1:  # the split-operand packing of a 1x1 conv (csrc/conv1x1_s.hip)
         assert not transpose_flip, 'the split 1x1 kernel serves forward convs'
         n_el = L.edvr_conv2d_packed_weight_1x1s_elems(co, ci)
         stale = ent[1].get(key)  # this layout is not part of prepack_conv_weights' table: rewritten in place here under the same rule
@@ -387,7 +393,9 @@ def reserve_amax_slots(device):
 
 
 BOUND_CHECK = os.environ.get('EDVR_BOUND_CHECK', '0') == '1'  # verify every x_amax against the data (tests / debugging)
-BOUND_CHECK_LOG = []  # (shape, bound / true maximum) of every checked conv input
+BOUND_CHECK_LOG = []  # (shape, bound / true maximum) of every checked conv input of the kernels that both paths have (a split conv of the
+#                       no-grad path has a forward and a data-gradient twin in training: consumers compare the counts of the two)
+BOUND_CHECK_LOG_DIRECT = []  # the same records for the split-operand DIRECT kernel (csrc/conv2d_s.hip), which the no-grad path alone launches
 AMAX_LOG = None  # a list: every reduction pass of input_bound() is recorded there (shape, calling functions)
 AMAX_PASSES = 0  # how often input_bound() had to run the reduction kernel (measurement: bench.py reports it per forward)
 
@@ -572,12 +580,14 @@ def amax(x, out=None):
 
 def conv2d(x1, wpk, bias, co, ks, *, x2=None, x2_map=None, stride=1, act=ACT_NONE, act_from=0, res1=None, res2=None,
            out_mode=OUT_NCHW, out=None, algo=None, gate=None, gate_slope=0.0, y_scale=1.0, wpk_f4=None, abs_sum_channels=0,
-           wpk_f4s=None, x_amax=None, want_y_amax=True, pre=None, pre_map=None):
+           wpk_f4s=None, x_amax=None, want_y_amax=True, pre=None, pre_map=None, wpk_ds=None):
     """y = y_scale * act(conv(cat(x1, x2)) + bias [+ pre]) + res1 + res2 on the fp32 MFMA kernel.
     pre (n_pre, co, h, w), pre_map = (div, mul, add) as x2_map: a pre-activation addend, image i of x1 takes image (i // div) * mul + add
     of it (edvr_conv2d_desc.pre: the F(4x4) Winograd kernels only, no gate / residuals / PixelShuffle - the C side rejects the rest).
     algo: CONV_AUTO (default; module-level CONV_ALGO overrides it, used by tests), CONV_DIRECT, CONV_WINOGRAD or CONV_WINOGRAD_F4.
     wpk_f4: pack_conv_weight(w, f4=True) - allows the F(4x4,3x3) Winograd kernel (inference; ~1e-6 relative rounding error).
+    wpk_ds: pack_conv_weight(w, ds=True) - allows the split-operand direct kernel (csrc/conv2d_s.hip) where the launch would run on the
+    fp32 direct kernel otherwise; like wpk_f4s it needs a bound of the inputs (x_amax, or the one travelling with them) and leaves one on y.
 
     x2_map = (div, mul, add): image i of x2 is (i // div) * mul + add (broadcast of a reference frame).
     gate (n, co, ho, wo): y *= gate > 0 ? 1 : gate_slope - the backward of a ReLU / LeakyReLU fused into the data-gradient conv
@@ -643,10 +653,10 @@ def conv2d(x1, wpk, bias, co, ks, *, x2=None, x2_map=None, stride=1, act=ACT_NON
         d.wpk_f4 = _ptr(wpk_f4)
     d.algo = CONV_ALGO if algo is None else algo
     split = False
-    if wpk_f4s is not None:  # the split-operand F(4x4) kernel: its weights + a bound of the input's magnitude
-        require_gpu(wpk_f4s, dtypes=(torch.int32,))
-        d.wpk_f4s = _ptr(wpk_f4s)
-        d.x_amax = _ptr(wpk_f4s)  # (any non-null pointer: only asks whether the launch would run on that kernel)
+    if wpk_f4s is not None or wpk_ds is not None:  # a split-operand kernel (F(4x4) / streaming 1x1; direct): its weights + a bound of the input's magnitude
+        require_gpu(wpk_f4s, wpk_ds, dtypes=(torch.int32,))
+        d.wpk_f4s, d.wpk_ds = _ptr(wpk_f4s), _ptr(wpk_ds)
+        d.x_amax = _ptr(wpk_f4s if wpk_f4s is not None else wpk_ds)  # (any non-null pointer: only asks whether the launch would run on that kernel)
         split = bool(L.edvr_conv2d_y_amax_supported(ctypes.byref(d)))
         if split:
             if x_amax is None:
@@ -658,13 +668,18 @@ def conv2d(x1, wpk, bias, co, ks, *, x2=None, x2_map=None, stride=1, act=ACT_NON
                 true = amax(x1).item() if x2 is None else max(amax(x1).item(), amax(x2).item())
                 if not (x_amax.item() >= true):
                     raise AssertionError(f'magnitude bound {x_amax.item():.6g} < max |x| = {true:.6g} for a conv input of shape {tuple(x1.shape)}')
-                BOUND_CHECK_LOG.append((tuple(x1.shape), x_amax.item() / max(true, 1e-30)))
+                direct = False
+                if wpk_ds is not None:  # which kernel takes the launch: the direct one if nothing is left without its packing
+                    d.wpk_ds = None
+                    direct = not L.edvr_conv2d_y_amax_supported(ctypes.byref(d))
+                    d.wpk_ds = _ptr(wpk_ds)
+                (BOUND_CHECK_LOG_DIRECT if direct else BOUND_CHECK_LOG).append((tuple(x1.shape), x_amax.item() / max(true, 1e-30)))
             d.x_amax = _ptr(x_amax)
             if want_y_amax:
                 y_bound = _arena(x1.device).slot(x1.device)
                 d.y_amax = _ptr(y_bound)
         else:
-            d.wpk_f4s, d.x_amax = None, None
+            d.wpk_f4s, d.wpk_ds, d.x_amax = None, None, None
     sums = None
     if abs_sum_channels > 0 and L.edvr_conv2d_abs_sum_supported(ctypes.byref(d)):
         sums = torch.zeros(2, n, dtype=torch.float32, device=x1.device)

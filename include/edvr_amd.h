@@ -160,6 +160,14 @@ typedef struct edvr_conv2d_desc {
   int64_t pre_img_stride; /* elements between consecutive images of pre (>= co*h*w) */
   int pre_div, pre_mul, pre_add; /* image map of pre, as x2's: ip = (i / pre_div) * pre_mul + pre_add; pre_div = 0 -> ip = i */
   int pre_n;              /* images in pre: the map of the last image, n - 1, must stay below it (EDVR_ERR_ARG) */
+  const void *wpk_ds;     /* optional: the weights packed by edvr_conv2d_pack_weight_ds_f32 (csrc/conv2d_s.hip).  Together with `x_amax` it
+                           * ALLOWS the split-operand form of the DIRECT kernel for a launch that no other kernel takes - 3x3 / stride 2,
+                           * 3x3 / stride 1 where the Winograd kernels do not apply (few input channels), 1x1 below the streaming kernel's
+                           * 320 channels: NCHW output, no gate / pre / abs_sum, y_scale 0 or 1, algo != EDVR_CONV_DIRECT, c1 % 4 == 0 when
+                           * x2 is set.  Everything else runs as if it were NULL.  A field of its own (not wpk_f4s): a caller may hand both,
+                           * the launch takes the one its kernel reads.  Same bound contract as wpk_f4s: `x_amax` >= max |x1|, |x2| (too
+                           * small: infinities, which `y_amax` keeps as a sticky non-finite pattern); `y_amax` is supported
+                           * (edvr_conv2d_y_amax_supported) and covers every stored element, residuals included. */
 } edvr_conv2d_desc;
 
 size_t edvr_conv2d_packed_weight_elems(int co, int ci, int ks);
@@ -186,6 +194,13 @@ int edvr_conv2d_pack_weight_f4s_f32(const float *w, void *wpk_f4s, int co, int c
  * (edvr_arch.py:190-193,229).  edvr_conv2d_packed_weight_1x1s_elems(co, ci) dwords, 16-byte aligned. */
 size_t edvr_conv2d_packed_weight_1x1s_elems(int co, int ci);
 int edvr_conv2d_pack_weight_1x1s_f32(const float *w, void *wpk_1x1s, int co, int ci, edvr_stream_t stream);
+/* The split-operand packing for the direct kernel (csrc/conv2d_s.hip; ks = 1 or 3, forward orientation): the same 64-byte header
+ * (s_W = the power of two that puts max |w| in [2^14, 2^15), and 1 / s_W) followed by [channel quad][tap][co padded to 32][4 channels]
+ * dwords (f16 hi | f16 lo << 16) of w * s_W, the channels zero-filled up to a multiple of 8 (ks = 3) or 32 (ks = 1).  Passed as
+ * edvr_conv2d_desc.wpk_ds.  Replaces: the cuDNN algorithm choice under the stride-2 nn.Conv2d of the pyramid (edvr_arch.py:37-66), conv_first
+ * (:322) and the 1x1 convs of TSAFusion (:190-244).  edvr_conv2d_packed_weight_ds_elems(co, ci, ks) dwords, 16-byte aligned. */
+size_t edvr_conv2d_packed_weight_ds_elems(int co, int ci, int ks);
+int edvr_conv2d_pack_weight_ds_f32(const float *w, void *wpk_ds, int co, int ci, int ks, edvr_stream_t stream);
 /* amax[0] = max(amax[0], max |x|) over n images of per_img contiguous floats, img_stride elements apart (the caller zeroes amax
  * before the first call; several tensors may be folded into one bound).  Feeds edvr_conv2d_desc.x_amax. */
 int edvr_amax_f32(const float *x, float *amax, int n, int64_t per_img, int64_t img_stride, edvr_stream_t stream);
@@ -205,7 +220,7 @@ int edvr_conv2d_f32(const edvr_conv2d_desc *d, edvr_stream_t stream);
  * kernel - correct, slower).  Callers that fuse an activation backward into a data-gradient conv ask first and keep the
  * two-launch form otherwise.  Pointers of `d` need not be set. */
 int edvr_conv2d_gate_supported(const edvr_conv2d_desc *d);
-/* 1 if edvr_conv2d_f32 would run `d` on the split-operand kernel, whose epilogue takes `y_amax`, else 0. */
+/* 1 if edvr_conv2d_f32 would run `d` on a split-operand kernel (F(4x4), streaming 1x1 or direct), whose epilogue takes `y_amax`, else 0. */
 int edvr_conv2d_y_amax_supported(const edvr_conv2d_desc *d);
 /* 1 if edvr_conv2d_f32 would run `d` on a kernel whose epilogue takes `abs_sum` (the F(4x4) Winograd kernel), else 0. */
 int edvr_conv2d_abs_sum_supported(const edvr_conv2d_desc *d);
