@@ -46,6 +46,7 @@ PROTOTYPES = {
     'edvr_pack_job_bytes': (sz, []),
     'edvr_conv2d_pack_weights_multi': (i32, [vp, i32, i32, i32, vp]),
     'edvr_conv2d_f32': (i32, [ctypes.POINTER(ConvDesc), vp]),
+    'edvr_conv2d_kernel': (i32, [ctypes.POINTER(ConvDesc)]),
     'edvr_conv2d_gate_supported': (i32, [ctypes.POINTER(ConvDesc)]),
     'edvr_conv2d_abs_sum_supported': (i32, [ctypes.POINTER(ConvDesc)]),
     'edvr_conv2d_y_amax_supported': (i32, [ctypes.POINTER(ConvDesc)]),
@@ -140,6 +141,8 @@ PROTOTYPES = {
 ACT_NONE, ACT_RELU, ACT_LRELU, ACT_SIGMOID = 0, 1, 2, 3
 OUT_NCHW, OUT_PIXEL_SHUFFLE2 = 0, 1
 CONV_AUTO, CONV_DIRECT, CONV_WINOGRAD, CONV_WINOGRAD_F4, CONV_WINOGRAD_F4S = 0, 1, 2, 3, 4
+(CONV_KERNEL_SMALL, CONV_KERNEL_F4S, CONV_KERNEL_F4, CONV_KERNEL_F2, CONV_KERNEL_1X1_SPLIT, CONV_KERNEL_1X1_STREAM,
+ CONV_KERNEL_DIRECT_SPLIT, CONV_KERNEL_DIRECT) = range(8)  # EDVR_CONV_KERNEL_*: what edvr_conv2d_kernel returns
 DTYPE_F32, DTYPE_F64, DTYPE_F16 = 0, 1, 2  # EDVR_DTYPE_*
 DCN_HALO_TAPWIN = 16  # EDVR_DCN_HALO_TAPWIN
 

@@ -29,7 +29,7 @@ def _hipcc():
 
 
 def _deps():
-    return [os.path.join(CSRC, 'common.h'), os.path.join(CSRC, 'pack.h'), os.path.join(CSRC, 'dcn_tap.h'), os.path.join(CSRC, 'pixel.h'), os.path.join(CSRC, 'lq_window.h'), os.path.join(HERE, '..', 'include', 'edvr_amd.h')]
+    return [os.path.join(CSRC, 'common.h'), os.path.join(CSRC, 'pack.h'), os.path.join(CSRC, 'conv_launch.h'), os.path.join(CSRC, 'dcn_tap.h'), os.path.join(CSRC, 'pixel.h'), os.path.join(CSRC, 'lq_window.h'), os.path.join(HERE, '..', 'include', 'edvr_amd.h')]
 
 
 def _stale(target, sources):

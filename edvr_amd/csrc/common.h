@@ -27,6 +27,18 @@ inline int64_t cdiv64(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
 // internal C++ entry used by dcn.hip for its GEMMs (same as the C ABI, no re-validation of wpk)
 int conv2d_launch(const edvr_conv2d_desc &d, hipStream_t stream);
+// the kernels behind conv2d_launch, and the one that takes `d` (conv2d.hip: the only place that states their precedence)
+enum conv_kernel {
+  CONV_SMALL = EDVR_CONV_KERNEL_SMALL,
+  CONV_F4S = EDVR_CONV_KERNEL_F4S,
+  CONV_F4 = EDVR_CONV_KERNEL_F4,
+  CONV_F2 = EDVR_CONV_KERNEL_F2,
+  CONV_1X1_SPLIT = EDVR_CONV_KERNEL_1X1_SPLIT,
+  CONV_1X1_STREAM = EDVR_CONV_KERNEL_1X1_STREAM,
+  CONV_DIRECT_SPLIT = EDVR_CONV_KERNEL_DIRECT_SPLIT,
+  CONV_DIRECT = EDVR_CONV_KERNEL_DIRECT,
+};
+conv_kernel conv2d_select(const edvr_conv2d_desc &d);
 
 // C[M,N] (+)= A[M,K] * B[N,K]^T with K contiguous in both (pixel axis); deterministic split-K.
 // ws must hold splits*M*N floats.  Used for dW of DCN (and conv wgrad on explicit columns).
@@ -76,8 +88,8 @@ int conv1x1_launch(const edvr_conv2d_desc &d, hipStream_t stream);
 bool conv1x1_split_eligible(const edvr_conv2d_desc &d);
 int conv1x1_split_launch(const edvr_conv2d_desc &d, hipStream_t stream);
 
-// conv2d_s.hip: the direct kernel of conv2d.hip with split fp32 operands on the f16 matrix pipe (needs d.wpk_ds and d.x_amax): takes
-// what would reach conv2d_mfma_kernel otherwise (NCHW store, no gate / pre / abs_sum / y_scale, algo != EDVR_CONV_DIRECT)
+// conv2d_s.hip: the direct kernel of conv2d.hip with split fp32 operands on the f16 matrix pipe (needs d.wpk_ds and d.x_amax, NCHW
+// store, no gate / pre / abs_sum / y_scale, algo != EDVR_CONV_DIRECT); conv2d_select places it just before conv2d_mfma_kernel
 bool conv2d_split_eligible(const edvr_conv2d_desc &d);
 int conv2d_split_launch(const edvr_conv2d_desc &d, hipStream_t stream);
 // ... and its weight packing, header (s_W, 1 / s_W) + [quads][kk taps][cop][4 channels] dwords; conv1x1_s.hip's layout with kk = 1

@@ -22,6 +22,7 @@
 //   Epilogue (bias, activation, residuals, pixel-shuffle) is applied on the
 //   accumulators, so none of those ops costs an HBM pass.
 #include "common.h"
+#include "conv_launch.h"
 
 namespace edvr {
 
@@ -293,51 +294,57 @@ __global__ void pack_weight_kernel(const float *__restrict__ w, float *__restric
   }
 }
 
-static inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
 static inline size_t direct_packed_elems(int co, int ci, int ks) {
   return (size_t)round_up(ci, ks == 1 ? 32 : 16) * ks * ks * round_up(co, 32);
 }
 
-template <int KS, int STRIDE, int MT, int SW>
-static int launch_one(const ConvArgs &a, int co_start, int co_blocks, hipStream_t stream) {
-  constexpr int NS = MT >= 3 ? 1 : 2;
-  constexpr int SH = 32 / SW, TH = 4 * NS * SH, TW = SW;
-  ConvArgs b = a;
-  b.tiles_x = cdiv(a.wo, TW);
-  b.tiles_y = cdiv(a.ho, TH);
-  b.co_start = co_start;
-  dim3 grid(b.tiles_x * b.tiles_y, co_blocks, a.d.n);
-  hipLaunchKernelGGL((conv2d_mfma_kernel<KS, STRIDE, MT, SW, NS>), grid, dim3(256), 0, stream, b);
-  return check_launch("conv2d_mfma_kernel");
-}
-
-static inline bool use_sw16(int ho, int wo, int ns = 2) {
-  // pick the tile geometry (4ns x 32 or 8ns x 16) that wastes fewer lanes on this output size
-  const int64_t w32 = (int64_t)cdiv(ho, 4 * ns) * 4 * ns * cdiv(wo, 32) * 32;
-  const int64_t w16 = (int64_t)cdiv(ho, 8 * ns) * 8 * ns * cdiv(wo, 16) * 16;
-  return w16 < w32;
-}
-
-template <int KS, int STRIDE, int MT>
-static int launch_sw(const ConvArgs &a, int co_start, int co_blocks, hipStream_t stream) {
-  return use_sw16(a.ho, a.wo, MT >= 3 ? 1 : 2) ? launch_one<KS, STRIDE, MT, 16>(a, co_start, co_blocks, stream)
-                                               : launch_one<KS, STRIDE, MT, 32>(a, co_start, co_blocks, stream);
-}
-
-template <int KS, int STRIDE>
-static int launch_mt(const ConvArgs &a, hipStream_t stream) {
-  // full 128-channel blocks with MT = 4, then one exact-size tail launch (no masked MFMA work)
-  const int full = a.d.co / 128, rem_tiles = cdiv(a.d.co - full * 128, 32);
-  int rc = EDVR_OK;
-  if (full > 0) rc = launch_sw<KS, STRIDE, 4>(a, 0, full, stream);
-  if (rc || rem_tiles == 0) return rc;
-  switch (rem_tiles) {
-    case 1: return launch_sw<KS, STRIDE, 1>(a, full * 128, 1, stream);
-    case 2: return launch_sw<KS, STRIDE, 2>(a, full * 128, 1, stream);
-    case 3: return launch_sw<KS, STRIDE, 3>(a, full * 128, 1, stream);
-    default: return launch_sw<KS, STRIDE, 4>(a, full * 128, 1, stream);  // 97..127 channels left
+struct MfmaLaunch {  // conv_launch.h
+  template <int KS, int STRIDE, int MT, int SW, int NS>
+  static int launch(dim3 grid, const ConvArgs &a, hipStream_t stream) {
+    hipLaunchKernelGGL((conv2d_mfma_kernel<KS, STRIDE, MT, SW, NS>), grid, dim3(256), 0, stream, a);
+    return check_launch("conv2d_mfma_kernel");
   }
+};
+
+// ---- which kernel takes a descriptor.  The *_eligible functions (one per kernel, in its own file) say what each kernel can do;
+// this ladder alone says who goes first.  The launch, its UNSUPPORTED checks and every query below derive from it and the table.
+conv_kernel conv2d_select(const edvr_conv2d_desc &d) {
+  const bool scaled = d.y_scale != 0.f && d.y_scale != 1.f;
+  if (!d.gate && !scaled && conv_small_eligible(d)) return CONV_SMALL;  // (the VALU kernel has neither epilogue)
+  if (winograd_f4s_eligible(d)) return CONV_F4S;
+  if (winograd_f4_eligible(d)) return CONV_F4;
+  if (winograd_eligible(d)) return CONV_F2;
+  if (conv1x1_split_eligible(d)) return CONV_1X1_SPLIT;
+  if (conv1x1_eligible(d)) return CONV_1X1_STREAM;
+  if (conv2d_split_eligible(d)) return CONV_DIRECT_SPLIT;
+  return CONV_DIRECT;
 }
+
+// direct algorithm (tile padding not counted); on split operands four f16 products per fp32 one
+static double direct_flops(const edvr_conv2d_desc &d, double per_mac) {
+  const int pad = d.ks / 2;
+  const double ho = (d.h + 2 * pad - d.ks) / d.stride + 1, wo = (d.w + 2 * pad - d.ks) / d.stride + 1;
+  return per_mac * d.n * ho * wo * d.co * (d.c1 + d.c2) * d.ks * d.ks;
+}
+static double direct_fp32_flops(const edvr_conv2d_desc &d) { return direct_flops(d, 2.0); }
+static double direct_split_flops(const edvr_conv2d_desc &d) { return direct_flops(d, 8.0); }
+
+struct conv_kernel_info {
+  const char *name;            // as rocprofv3 prints it; the two direct kernels append their template arguments
+  bool y_amax, abs_sum, pre;   // the epilogues the kernel has
+  double (*executed_flops)(const edvr_conv2d_desc &);
+};
+static const conv_kernel_info conv_kernels[] = {
+    /* CONV_SMALL        */ {"conv3x3_smallco_kernel", false, false, false, direct_fp32_flops},
+    /* CONV_F4S          */ {"conv3x3_winograd_f4s_kernel", true, true, true, winograd_f4s_executed_flops},
+    /* CONV_F4           */ {"conv3x3_winograd_f4_kernel", false, true, true, winograd_f4_executed_flops},
+    /* CONV_F2           */ {"conv3x3_winograd_kernel", false, false, false, winograd_executed_flops},
+    /* CONV_1X1_SPLIT    */ {"conv1x1_split_kernel", true, false, false, direct_split_flops},
+    /* CONV_1X1_STREAM   */ {"conv1x1_stream_kernel", false, false, false, direct_fp32_flops},
+    /* CONV_DIRECT_SPLIT */ {"conv2d_split_kernel", true, false, false, direct_split_flops},
+    /* CONV_DIRECT       */ {"conv2d_mfma_kernel", false, false, false, direct_fp32_flops},
+};
+static inline const conv_kernel_info &conv2d_info(const edvr_conv2d_desc &d) { return conv_kernels[conv2d_select(d)]; }
 
 int conv2d_launch(const edvr_conv2d_desc &d, hipStream_t stream) {
   EDVR_REQUIRE(d.x1 && d.wpk && d.y, "conv2d: null x1/wpk/y");
@@ -368,11 +375,13 @@ int conv2d_launch(const edvr_conv2d_desc &d, hipStream_t stream) {
     set_error("conv2d: gate together with a sigmoid epilogue is not supported");
     return EDVR_ERR_UNSUPPORTED;
   }
-  if (d.abs_sum && (conv_small_eligible(d) || !(winograd_f4_eligible(d) || winograd_f4s_eligible(d)) || d.out_mode != EDVR_OUT_NCHW)) {
+  const conv_kernel kernel = conv2d_select(d);
+  const conv_kernel_info &has = conv_kernels[kernel];
+  if (d.abs_sum && !(has.abs_sum && d.out_mode == EDVR_OUT_NCHW)) {
     set_error("conv2d: abs_sum is an epilogue of the F(4x4) Winograd kernel's NCHW store only (ask edvr_conv2d_abs_sum_supported)");
     return EDVR_ERR_UNSUPPORTED;
   }
-  if (d.y_amax && !conv2d_split_eligible(d) && (conv_small_eligible(d) || !(winograd_f4s_eligible(d) || conv1x1_split_eligible(d)))) {
+  if (d.y_amax && !has.y_amax) {
     set_error("conv2d: y_amax is an epilogue of the split-operand kernels only (ask edvr_conv2d_y_amax_supported)");
     return EDVR_ERR_UNSUPPORTED;
   }
@@ -386,24 +395,22 @@ int conv2d_launch(const edvr_conv2d_desc &d, hipStream_t stream) {
       set_error("conv2d: pre excludes gate, res1 / res2 and the pixel-shuffle output (it rides in their registers of the NCHW epilogue)");
       return EDVR_ERR_UNSUPPORTED;
     }
-    if (conv_small_eligible(d) || !(winograd_f4s_eligible(d) || winograd_f4_eligible(d))) {
+    if (!has.pre) {
       set_error("conv2d: pre is an epilogue of the F(4x4) Winograd kernels only, 16-byte aligned (ask edvr_conv2d_pre_supported)");
       return EDVR_ERR_UNSUPPORTED;
     }
   }
-  if (!d.gate && !scaled && conv_small_eligible(d)) return conv_small_launch(d, stream);
-  if (winograd_f4s_eligible(d)) return winograd_f4s_launch(d, stream);
-  if (winograd_f4_eligible(d)) return winograd_f4_launch(d, stream);
-  if (winograd_eligible(d)) {
-    const float *U = d.wpk + direct_packed_elems(d.co, a.ci, 3);
-    return winograd_launch(d, U, round_up(d.co, 64), stream);
+  switch (kernel) {
+    case CONV_SMALL: return conv_small_launch(d, stream);
+    case CONV_F4S: return winograd_f4s_launch(d, stream);
+    case CONV_F4: return winograd_f4_launch(d, stream);
+    case CONV_F2: return winograd_launch(d, d.wpk + direct_packed_elems(d.co, a.ci, 3), round_up(d.co, 64), stream);
+    case CONV_1X1_SPLIT: return conv1x1_split_launch(d, stream);
+    case CONV_1X1_STREAM: return conv1x1_launch(d, stream);
+    case CONV_DIRECT_SPLIT: return conv2d_split_launch(d, stream);
+    case CONV_DIRECT: break;
   }
-  if (conv2d_split_eligible(d)) return conv2d_split_launch(d, stream);  // (only what reaches launch_mt below)
-  if (d.ks == 3 && d.stride == 1) return launch_mt<3, 1>(a, stream);
-  if (d.ks == 3 && d.stride == 2) return launch_mt<3, 2>(a, stream);
-  if (conv1x1_split_eligible(d)) return conv1x1_split_launch(d, stream);
-  if (conv1x1_eligible(d)) return conv1x1_launch(d, stream);
-  return launch_mt<1, 1>(a, stream);
+  return launch_direct<MfmaLaunch>(a, stream);
 }
 
 }  // namespace edvr
@@ -429,74 +436,46 @@ int edvr_conv2d_pack_weight_f32(const float *w, float *wpk, int co, int ci, int 
   return edvr::check_launch("pack_weight_kernel");
 }
 
+int edvr_conv2d_kernel(const edvr_conv2d_desc *d) { return d ? (int)edvr::conv2d_select(*d) : -1; }
+
 int edvr_conv2d_kernel_name(const edvr_conv2d_desc *d, char *buf, size_t buf_len) {
   EDVR_REQUIRE(d && buf && buf_len > 0, "kernel_name: bad arguments");
+  const edvr::conv_kernel kernel = edvr::conv2d_select(*d);
+  const char *name = edvr::conv_kernels[kernel].name;
+  if (kernel != edvr::CONV_DIRECT && kernel != edvr::CONV_DIRECT_SPLIT) {
+    snprintf(buf, buf_len, "%s", name);
+    return EDVR_OK;
+  }
   const int pad = d->ks / 2;
   const int ho = (d->h + 2 * pad - d->ks) / d->stride + 1, wo = (d->w + 2 * pad - d->ks) / d->stride + 1;
-  if (edvr::conv_small_eligible(*d)) {
-    snprintf(buf, buf_len, "conv3x3_smallco_kernel");
-    return EDVR_OK;
-  }
-  if (edvr::winograd_f4s_eligible(*d)) {
-    snprintf(buf, buf_len, "conv3x3_winograd_f4s_kernel");
-    return EDVR_OK;
-  }
-  if (edvr::winograd_f4_eligible(*d)) {
-    snprintf(buf, buf_len, "conv3x3_winograd_f4_kernel");
-    return EDVR_OK;
-  }
-  if (edvr::winograd_eligible(*d)) {
-    snprintf(buf, buf_len, "conv3x3_winograd_kernel");
-    return EDVR_OK;
-  }
-  if (edvr::conv1x1_split_eligible(*d)) {
-    snprintf(buf, buf_len, "conv1x1_split_kernel");
-    return EDVR_OK;
-  }
-  if (edvr::conv1x1_eligible(*d)) {
-    snprintf(buf, buf_len, "conv1x1_stream_kernel");
-    return EDVR_OK;
-  }
   const int mt = d->co >= 128 ? 4 : edvr::cdiv(d->co, 32);  // the launch carrying most of the work
   const int ns = mt >= 3 ? 1 : 2;
-  snprintf(buf, buf_len, "%s<%d, %d, %d, %d, %d>", edvr::conv2d_split_eligible(*d) ? "conv2d_split_kernel" : "conv2d_mfma_kernel", d->ks, d->stride, mt, edvr::use_sw16(ho, wo, ns) ? 16 : 32, ns);
+  snprintf(buf, buf_len, "%s<%d, %d, %d, %d, %d>", name, d->ks, d->stride, mt, edvr::use_sw16(ho, wo, ns) ? 16 : 32, ns);
   return EDVR_OK;
 }
 
 int edvr_conv2d_executed_flops(const edvr_conv2d_desc *d, double *flops) {
   EDVR_REQUIRE(d && flops, "executed_flops: bad arguments");
-  const int pad = d->ks / 2;
-  const double ho = (d->h + 2 * pad - d->ks) / d->stride + 1, wo = (d->w + 2 * pad - d->ks) / d->stride + 1;
-  if (!edvr::conv_small_eligible(*d) && edvr::winograd_f4s_eligible(*d)) *flops = edvr::winograd_f4s_executed_flops(*d);
-  else if (!edvr::conv_small_eligible(*d) && edvr::winograd_f4_eligible(*d)) *flops = edvr::winograd_f4_executed_flops(*d);
-  else if (!edvr::conv_small_eligible(*d) && edvr::winograd_eligible(*d)) *flops = edvr::winograd_executed_flops(*d);
-  else if (edvr::conv1x1_split_eligible(*d)) *flops = 8.0 * d->n * ho * wo * d->co * (d->c1 + d->c2);  // four f16 products per fp32 one
-  else if (edvr::conv2d_split_eligible(*d)) *flops = 8.0 * d->n * ho * wo * d->co * (d->c1 + d->c2) * d->ks * d->ks;  // the same
-  else *flops = 2.0 * d->n * ho * wo * d->co * (d->c1 + d->c2) * d->ks * d->ks;  // direct algorithm (tile padding not counted)
+  *flops = edvr::conv2d_info(*d).executed_flops(*d);
   return EDVR_OK;
 }
 
 int edvr_conv2d_abs_sum_supported(const edvr_conv2d_desc *d) {
-  if (!d) return 0;
-  return (!edvr::conv_small_eligible(*d) && (edvr::winograd_f4_eligible(*d) || edvr::winograd_f4s_eligible(*d)) && d->out_mode == EDVR_OUT_NCHW) ? 1 : 0;  // (the PixelShuffle store has no such sum)
+  return (d && edvr::conv2d_info(*d).abs_sum && d->out_mode == EDVR_OUT_NCHW) ? 1 : 0;  // (the PixelShuffle store has no such sum)
 }
 
 int edvr_conv2d_pre_supported(const edvr_conv2d_desc *d) {
   if (!d) return 0;
   edvr_conv2d_desc q = *d;
   if (!q.pre) q.pre_img_stride = 0;  // callers probe with the pointer unset: only the eligibility rules are evaluated
-  return (!q.gate && !q.res1 && !q.res2 && q.out_mode == EDVR_OUT_NCHW && !edvr::conv_small_eligible(q) &&
-          (edvr::winograd_f4s_eligible(q) || edvr::winograd_f4_eligible(q)))
-             ? 1
-             : 0;
+  return (!q.gate && !q.res1 && !q.res2 && q.out_mode == EDVR_OUT_NCHW && edvr::conv2d_info(q).pre) ? 1 : 0;
 }
 
-int edvr_conv2d_y_amax_supported(const edvr_conv2d_desc *d) {
-  if (!d) return 0;
-  if (edvr::conv2d_split_eligible(*d)) return 1;
-  return (!edvr::conv_small_eligible(*d) && (edvr::winograd_f4s_eligible(*d) || edvr::conv1x1_split_eligible(*d))) ? 1 : 0;
-}
+int edvr_conv2d_y_amax_supported(const edvr_conv2d_desc *d) { return (d && edvr::conv2d_info(*d).y_amax) ? 1 : 0; }
 
+// Deliberately not over conv2d_select: callers probe with no pointer set and ask whether a Winograd kernel's fused gate epilogue
+// applies at all.  That is the F(2x2) kernel's own rule (the F(4x4) kernels only add packing / alignment conditions to it), whichever
+// kernel would win the launch; nothing here repeats the ladder.
 int edvr_conv2d_gate_supported(const edvr_conv2d_desc *d) {
   if (!d) return 0;
   edvr_conv2d_desc q = *d;

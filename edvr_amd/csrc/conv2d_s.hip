@@ -17,6 +17,7 @@
 #include <algorithm>
 
 #include "common.h"
+#include "conv_launch.h"
 #include "pack.h"
 
 namespace edvr {
@@ -320,49 +321,15 @@ int conv_split_pack(const float *w, unsigned *wq, int co, int ci, int kk, int co
   return check_launch("conv_split_pack_kernel");
 }
 
-static inline int ds_round_up(int v, int m) { return (v + m - 1) / m * m; }
-static inline int ds_quads(int ci, int ks) { return ds_round_up(ci, ks == 1 ? 32 : 8) / 4; }  // whole chunks: the slab copy never leaves the buffer
+static inline int ds_quads(int ci, int ks) { return round_up(ci, ks == 1 ? 32 : 8) / 4; }  // whole chunks: the slab copy never leaves the buffer
 
-// the tile geometry choice of conv2d.hip (use_sw16)
-static inline bool ds_use_sw16(int ho, int wo, int ns) {
-  const int64_t w32 = (int64_t)cdiv(ho, 4 * ns) * 4 * ns * cdiv(wo, 32) * 32;
-  const int64_t w16 = (int64_t)cdiv(ho, 8 * ns) * 8 * ns * cdiv(wo, 16) * 16;
-  return w16 < w32;
-}
-
-template <int KS, int STRIDE, int MT, int SW>
-static int ds_launch_one(const ConvSArgs &a, int co_start, int co_blocks, hipStream_t stream) {
-  constexpr int NS = MT >= 3 ? 1 : 2;
-  constexpr int SH = 32 / SW, TH = 4 * NS * SH, TW = SW;
-  ConvSArgs b = a;
-  b.tiles_x = cdiv(a.wo, TW);
-  b.tiles_y = cdiv(a.ho, TH);
-  b.co_start = co_start;
-  dim3 grid(b.tiles_x * b.tiles_y, co_blocks, a.d.n);
-  hipLaunchKernelGGL((conv2d_split_kernel<KS, STRIDE, MT, SW, NS>), grid, dim3(256), 0, stream, b);
-  return check_launch("conv2d_split_kernel");
-}
-
-template <int KS, int STRIDE, int MT>
-static int ds_launch_sw(const ConvSArgs &a, int co_start, int co_blocks, hipStream_t stream) {
-  return ds_use_sw16(a.ho, a.wo, MT >= 3 ? 1 : 2) ? ds_launch_one<KS, STRIDE, MT, 16>(a, co_start, co_blocks, stream)
-                                                  : ds_launch_one<KS, STRIDE, MT, 32>(a, co_start, co_blocks, stream);
-}
-
-template <int KS, int STRIDE>
-static int ds_launch_mt(const ConvSArgs &a, hipStream_t stream) {
-  // full 128-channel blocks with MT = 4, then one exact-size tail launch (no masked MFMA work)
-  const int full = a.d.co / 128, rem_tiles = cdiv(a.d.co - full * 128, 32);
-  int rc = EDVR_OK;
-  if (full > 0) rc = ds_launch_sw<KS, STRIDE, 4>(a, 0, full, stream);
-  if (rc || rem_tiles == 0) return rc;
-  switch (rem_tiles) {
-    case 1: return ds_launch_sw<KS, STRIDE, 1>(a, full * 128, 1, stream);
-    case 2: return ds_launch_sw<KS, STRIDE, 2>(a, full * 128, 1, stream);
-    case 3: return ds_launch_sw<KS, STRIDE, 3>(a, full * 128, 1, stream);
-    default: return ds_launch_sw<KS, STRIDE, 4>(a, full * 128, 1, stream);  // 97..127 channels left
+struct SplitLaunch {  // conv_launch.h
+  template <int KS, int STRIDE, int MT, int SW, int NS>
+  static int launch(dim3 grid, const ConvSArgs &a, hipStream_t stream) {
+    hipLaunchKernelGGL((conv2d_split_kernel<KS, STRIDE, MT, SW, NS>), grid, dim3(256), 0, stream, a);
+    return check_launch("conv2d_split_kernel");
   }
-}
+};
 
 bool conv2d_split_eligible(const edvr_conv2d_desc &d) {
   if (!d.wpk_ds || !d.x_amax || d.algo == EDVR_CONV_DIRECT) return false;
@@ -371,9 +338,6 @@ bool conv2d_split_eligible(const edvr_conv2d_desc &d) {
   if (d.out_mode != EDVR_OUT_NCHW || d.gate || d.pre || d.abs_sum) return false;
   if (d.y_scale != 0.f && d.y_scale != 1.f) return false;
   if (d.x2 && (d.c1 & 3)) return false;  // a channel quad must not straddle x1 / x2
-  // only what would reach the fp32 direct kernel otherwise: every other kernel keeps its launches
-  if (conv_small_eligible(d) || winograd_f4s_eligible(d) || winograd_f4_eligible(d) || winograd_eligible(d)) return false;
-  if (d.ks == 1 && (conv1x1_split_eligible(d) || conv1x1_eligible(d))) return false;
   return true;
 }
 
@@ -382,15 +346,13 @@ int conv2d_split_launch(const edvr_conv2d_desc &d, hipStream_t stream) {
   a.d = d;
   a.wq = reinterpret_cast<const unsigned *>(d.wpk_ds);
   a.ci = d.c1 + d.c2;
-  a.cop = ds_round_up(d.co, 32);
+  a.cop = round_up(d.co, 32);
   const int pad = d.ks / 2;
   a.ho = (d.h + 2 * pad - d.ks) / d.stride + 1;
   a.wo = (d.w + 2 * pad - d.ks) / d.stride + 1;
   a.tiles_x = a.tiles_y = 0;
   a.co_start = 0;
-  if (d.ks == 3 && d.stride == 1) return ds_launch_mt<3, 1>(a, stream);
-  if (d.ks == 3) return ds_launch_mt<3, 2>(a, stream);
-  return ds_launch_mt<1, 1>(a, stream);
+  return launch_direct<SplitLaunch>(a, stream);
 }
 
 }  // namespace edvr
@@ -399,14 +361,14 @@ extern "C" {
 
 size_t edvr_conv2d_packed_weight_ds_elems(int co, int ci, int ks) {
   if (co <= 0 || ci <= 0 || (ks != 1 && ks != 3)) return 0;
-  return 16 + (size_t)edvr::ds_quads(ci, ks) * ks * ks * edvr::ds_round_up(co, 32) * 4;
+  return 16 + (size_t)edvr::ds_quads(ci, ks) * ks * ks * edvr::round_up(co, 32) * 4;
 }
 
 int edvr_conv2d_pack_weight_ds_f32(const float *w, void *wpk_ds, int co, int ci, int ks, edvr_stream_t stream) {
   using namespace edvr;
   EDVR_REQUIRE(w && wpk_ds && co > 0 && ci > 0 && (ks == 1 || ks == 3), "pack_weight_ds: bad arguments");
   EDVR_REQUIRE((reinterpret_cast<uintptr_t>(wpk_ds) & 15) == 0, "pack_weight_ds: wpk_ds must be 16-byte aligned");
-  return conv_split_pack(w, static_cast<unsigned *>(wpk_ds), co, ci, ks * ks, ds_round_up(co, 32), ds_quads(ci, ks), as_stream(stream));
+  return conv_split_pack(w, static_cast<unsigned *>(wpk_ds), co, ci, ks * ks, round_up(co, 32), ds_quads(ci, ks), as_stream(stream));
 }
 
 }  // extern "C"

@@ -964,10 +964,7 @@ int edvr_f4s_prof_read(unsigned long long *host, int reset) {  // host[16 * 8]
 int edvr_conv2d_f4s_set_lean(int on) { return edvr::f4s_lean_switch().exchange(on ? 1 : 0); }
 
 int edvr_conv2d_f4s_lean_items(const edvr_conv2d_desc *d) {
-  if (!d) return 0;
-  const bool scaled = d->y_scale != 0.f && d->y_scale != 1.f;
-  if ((!d->gate && !scaled && edvr::conv_small_eligible(*d)) || !edvr::winograd_f4s_eligible(*d)) return 0;  // edvr_conv2d_f32's own order
-  return edvr::winograd_f4s_lean_items(*d);
+  return (d && edvr::conv2d_select(*d) == edvr::CONV_F4S) ? edvr::winograd_f4s_lean_items(*d) : 0;
 }
 
 size_t edvr_conv2d_packed_weight_f4s_elems(int co, int ci) { return 16 + (size_t)((co + 63) / 64 * 64) * ((ci + 7) / 8 * 8) * 36; }

@@ -668,11 +668,7 @@ def conv2d(x1, wpk, bias, co, ks, *, x2=None, x2_map=None, stride=1, act=ACT_NON
                 true = amax(x1).item() if x2 is None else max(amax(x1).item(), amax(x2).item())
                 if not (x_amax.item() >= true):
                     raise AssertionError(f'magnitude bound {x_amax.item():.6g} < max |x| = {true:.6g} for a conv input of shape {tuple(x1.shape)}')
-                direct = False
-                if wpk_ds is not None:  # which kernel takes the launch: the direct one if nothing is left without its packing
-                    d.wpk_ds = None
-                    direct = not L.edvr_conv2d_y_amax_supported(ctypes.byref(d))
-                    d.wpk_ds = _ptr(wpk_ds)
+                direct = L.edvr_conv2d_kernel(ctypes.byref(d)) == _lib.CONV_KERNEL_DIRECT_SPLIT
                 (BOUND_CHECK_LOG_DIRECT if direct else BOUND_CHECK_LOG).append((tuple(x1.shape), x_amax.item() / max(true, 1e-30)))
             d.x_amax = _ptr(x_amax)
             if want_y_amax:

@@ -215,6 +215,17 @@ int edvr_amax_f32(const float *x, float *amax, int n, int64_t per_img, int64_t i
 size_t edvr_pack_job_bytes(void);
 int edvr_conv2d_pack_weights_multi(const void *jobs, int n_jobs, int total_blocks, int split_parity, edvr_stream_t stream);
 int edvr_conv2d_f32(const edvr_conv2d_desc *d, edvr_stream_t stream);
+/* The kernel edvr_conv2d_f32 would run `d` on, in order of precedence (the first whose own rules accept `d` takes the launch): the one
+ * selection the launch and every query below derive from.  Nothing is dereferenced; -1 for a NULL descriptor. */
+#define EDVR_CONV_KERNEL_SMALL 0        /* conv3x3_smallco_kernel: 3x3 / stride 1, co <= 4, EDVR_CONV_AUTO, no gate / y_scale */
+#define EDVR_CONV_KERNEL_F4S 1          /* conv3x3_winograd_f4s_kernel: F(4x4) on split operands (wpk_f4s + x_amax) */
+#define EDVR_CONV_KERNEL_F4 2           /* conv3x3_winograd_f4_kernel (wpk_f4) */
+#define EDVR_CONV_KERNEL_F2 3           /* conv3x3_winograd_kernel: F(2x2) */
+#define EDVR_CONV_KERNEL_1X1_SPLIT 4    /* conv1x1_split_kernel: streaming 1x1 on split operands (wpk_f4s + x_amax) */
+#define EDVR_CONV_KERNEL_1X1_STREAM 5   /* conv1x1_stream_kernel */
+#define EDVR_CONV_KERNEL_DIRECT_SPLIT 6 /* conv2d_split_kernel: the direct kernel on split operands (wpk_ds + x_amax) */
+#define EDVR_CONV_KERNEL_DIRECT 7       /* conv2d_mfma_kernel: takes everything else */
+int edvr_conv2d_kernel(const edvr_conv2d_desc *d);
 /* 1 if `d` with a `gate` (and no residuals) would run in a Winograd kernel's fused epilogue (that kernel applies under d->algo,
  * the sizes and the EDVR_CONV_WINOGRAD environment switch), else 0 (edvr_conv2d_f32 still accepts the gate on the direct
  * kernel - correct, slower).  Callers that fuse an activation backward into a data-gradient conv ask first and keep the

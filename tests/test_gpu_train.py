@@ -145,6 +145,33 @@ def test_conv_gate_on_the_direct_kernel(gpu, res):
     assert not ops.conv_gate_supported(2, 64, 9, 14, 64, ops.CONV_DIRECT) and ops.conv_gate_supported(2, 64, 20, 36, 64)
 
 
+@pytest.mark.parametrize('epilogue', ['gate', 'y_scale'])
+def test_conv_gate_or_scale_with_few_output_channels(gpu, monkeypatch, epilogue):
+    """co <= 4 under CONV_AUTO is the small-co VALU kernel's, which has neither a gate nor a scale: with one of them the launch is the
+    direct kernel's, and the name reported to LAUNCH_HOOK is that of the kernel that ran."""
+    from edvr_amd import ops
+    g = torch.Generator().manual_seed(16)
+    x = torch.randn(1, 16, 9, 14, generator=g)
+    w = torch.randn(4, 16, 3, 3, generator=g) * 0.1
+    b = torch.randn(4, generator=g)
+    gate = torch.randn(1, 4, 9, 14, generator=g).relu()
+    r1 = torch.randn(1, 4, 9, 14, generator=g)
+    z = F.conv2d(x.double(), w.double(), b.double(), 1, 1)
+    xg, wpk, bg = x.to(gpu), ops.pack_conv_weight(w.to(gpu)), b.to(gpu)
+    names = []
+    monkeypatch.setattr(ops, 'LAUNCH_HOOK', lambda name, flops, launch, *a: (names.append(name), launch()))
+    if epilogue == 'gate':
+        got = ops.conv2d(xg, wpk, bg, 4, 3, gate=gate.to(gpu), gate_slope=0.1, algo=ops.CONV_AUTO)
+        ref = torch.where(gate.double() > 0, z, 0.1 * z)
+    else:
+        got = ops.conv2d(xg, wpk, bg, 4, 3, y_scale=0.2, res1=r1.to(gpu), algo=ops.CONV_AUTO)
+        ref = 0.2 * z + r1.double()
+    plain = ops.conv2d(xg, wpk, bg, 4, 3, algo=ops.CONV_AUTO)
+    print(f'{epilogue}: rel {_rel(got, ref):.3g}, plain rel {_rel(plain, z):.3g}, launches {names}')
+    assert _rel(got, ref) < 2e-5 and _rel(plain, z) < 2e-5
+    assert len(names) == 2 and names[0].startswith('conv2d_mfma_kernel<3, 1, 1,') and names[1] == 'conv3x3_smallco_kernel', names
+
+
 @pytest.mark.parametrize('algo', ['direct', 'winograd'])
 @pytest.mark.parametrize('scale', [0.2, -1.5])
 def test_conv_y_scale(gpu, algo, scale):
