@@ -36,6 +36,12 @@
 #ifndef F4S_PLAIN
 #define F4S_PLAIN 1
 #endif
+// 1 = a staging wave moves its load cursor and rebuilds the DMA buffer resource (~28 scalar instructions per chunk) while the patch
+// reads of the chunk are in flight, so that the six LDS-DMA requests of the next-but-one chunk leave right behind the reads' wait;
+// 0 = first the wait, then the scalar work, then the requests (as it was; the A/B switch of profiles/dma_placement)
+#ifndef F4S_DMA_EARLY
+#define F4S_DMA_EARLY 1
+#endif
 
 namespace edvr {
 
@@ -238,7 +244,7 @@ __global__ __launch_bounds__(1024, 1) void conv3x3_winograd_f4s_kernel(const Win
     f32x2 pp[6][3];  // raw patch: row r, columns (2 cp, 2 cp + 1)
     f32x2 tp[6][3];  // B^T d, same pairing
     const float *patch = Rw + ((half * RROWS + 4 * p_ty) * RPIECES + p_tx) * 4 + 4;  // patch row r, column c: patch[r * 4 RPIECES + c]
-    auto read_patch = [&]() {
+    auto read_patch_begin = [&]() {
       F4S_WAIT_DMA();  // s_waitcnt vmcnt(0): the requested chunk is in the region
 #pragma unroll
       for (int r = 0; r < 6; ++r) {
@@ -247,7 +253,13 @@ __global__ __launch_bounds__(1024, 1) void conv3x3_winograd_f4s_kernel(const Win
         pp[r][1] = f32x2{m[2], m[3]};
         pp[r][2] = *reinterpret_cast<const f32x2 *>(patch + r * (4 * RPIECES) + 4);
       }
+    };
+    auto read_patch_end = [&]() {
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // ... and in registers: the region may be overwritten
+    };
+    auto read_patch = [&]() {
+      read_patch_begin();
+      read_patch_end();
     };
 #if F4S_PLAIN
     // experiment: the same arithmetic on plain fp32 instructions (v_fma_f32 / v_add_f32 overlap with the f16 matrix pipe of the other
@@ -362,9 +374,20 @@ __global__ __launch_bounds__(1024, 1) void conv3x3_winograd_f4s_kernel(const Win
 #pragma unroll 1
       for (int k = 0; k < n_chunks; ++k) {
         unsigned *Vd = Vst + (par ^ 1) * VSLAB;
+#if F4S_DMA_EARLY
+        // The scalar work between the patch reads and their wait: it needs nothing of the patch, and the requests - which must stay
+        // behind that wait, the region is overwritten - then leave without the wave that sets the kernel's pace idling through the
+        // LDS latency first (-1.5 to -3.5 % per layer).  The requests themselves stay one burst in the builtin form: spread over the
+        // step they gained nothing, issued from inline assembly they cost 3-4 % (profiles/dma_placement/README.md).
+        read_patch_begin();
+        advance();
+        load_begin(l_k * CK);
+        read_patch_end();
+#else
         read_patch();
         advance();
         load_begin(l_k * CK);
+#endif
         dma_issue();
 #pragma unroll
         for (int cp = 0; cp < 3; ++cp) transform_cols(cp);
