@@ -18,5 +18,6 @@ from .dcn import (DeformConv, DeformConvFunction, DeformConvPack, ModulatedDefor
                   ModulatedDeformConvFunction, ModulatedDeformConvPack, deform_conv, modulated_deform_conv)
 from .edvr_arch import EDVR, PCDAlignment, PredeblurModule, TSAFusion  # noqa: F401
 from .video import VideoRestorer, WindowSchedule, ensemble_elements, tile_bands, tile_grid, window_table  # noqa: F401
+from .shots import ShotDetector, cut_scores, select_cuts  # noqa: F401
 
 __version__ = '0.1.0'

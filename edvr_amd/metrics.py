@@ -282,19 +282,22 @@ def validate_clip(net, lq, gt=None, num_frame=5, padding='reflection_circle', ba
 
 @torch.no_grad()
 def validate_video(net, lq, gt=None, num_frame=5, padding='reflection_circle', chunk=8, crop_border=0, test_y_channel=False, pad_mode=None,
-                   tile=None, tile_overlap=None, self_ensemble=None, tile_blend=None, time_reverse=False):
+                   tile=None, tile_overlap=None, self_ensemble=None, tile_blend=None, time_reverse=False, cuts=None,
+                   cut_threshold=None):
     """validate_clip with every frame's features extracted once (edvr_amd/video.py: VideoRestorer) instead of once per window it
     appears in; `chunk` output frames per alignment / fusion / reconstruction pass.  Same arguments otherwise, same return value:
     (outputs (t, c, H, W), [PSNR per frame] or None).  pad_mode / tile / tile_overlap: VideoRestorer's, for frames of any size - the
     outputs and `gt` are (s H, s W) for LQ frames of (H, W), whatever they were padded to.  self_ensemble: VideoRestorer's ('flip4', 'd4' or
     element ids): the outputs and their PSNRs are those of the averaged result, at n times the cost.  tile_blend: VideoRestorer's (input
     pixels): the outputs and their PSNRs are those of the tiles cross-faded around their cuts.  time_reverse: VideoRestorer's - every
-    element also runs on the video in reversed frame order (the alignment is shared); composes with self_ensemble."""
+    element also runs on the video in reversed frame order (the alignment is shared); composes with self_ensemble.  cuts:
+    VideoRestorer's (None | 'auto' | frame indices; cut_threshold with 'auto') - every shot is restored as a video of its own."""
     from .video import VideoRestorer
     outs, scores, s0 = [], [], 0
     vr = VideoRestorer(net, num_frame=num_frame, padding=padding, chunk=chunk, pad_mode=pad_mode, tile=tile, tile_overlap=tile_overlap,
                        self_ensemble=self_ensemble, **({} if tile_blend is None else dict(tile_blend=tile_blend)),
-                       **(dict(time_reverse=True) if time_reverse else {}))
+                       **(dict(time_reverse=True) if time_reverse else {}), **({} if cuts is None else dict(cuts=cuts)),
+                       **({} if cut_threshold is None else dict(cut_threshold=cut_threshold)))
     for out in vr.restore_chunks(lq.split(chunk), length=lq.shape[0]):
         outs.append(out)
         if gt is not None:

@@ -1997,3 +1997,43 @@ def rgb_to_yuv420(rgb, matrix='bt601', range='limited', out=None):
         _run('rgb_to_yuv420', lambda: _lib.check(_lib.lib().edvr_rgb_to_yuv420_f32(_ptr(rgb), _ptr(out), n, H, W, _img_stride(rgb), stride, coef, _stream()),
                                                  'edvr_rgb_to_yuv420_f32'), 0, nbytes)
     return out
+
+
+# ------------------------------------------------------------------------------------------------ scene cuts
+def frame_sad(frames, prev=None, out=None):
+    """How much consecutive frames differ, for scene-cut detection (edvr_amd/shots.py), in ONE kernel launch.
+    frames: uint8 (n, H, W, 3) or float32 (n, 3, H, W) RGB on the GPU - each frame dense, the frames any distance apart at any base
+    address (a slice of a longer video works as it is).  Per pixel, in integers, Y8 = ((66 R + 129 G + 25 B + 128) >> 8) + 16 of the
+    bytes - a float frame's are its tensor2img bytes rint(clamp(x, 0, 1) * 255), NaN -> 0, so a frame holding byte / 255 gives what the
+    bytes give.  Returns int64 (n,) on the device: [j] = sum over the pixels of |Y8 of frame j - Y8 of frame j - 1|, [0] against `prev`
+    (one frame of the same type and size, (H, W, 3) / (3, H, W) or with a leading 1: the last frame of the batch before) or 0 without
+    one.  Exact (at most 219 H W), whatever the batching.  out: an int64 (n,) contiguous tensor to write into instead."""
+    for t in (frames, prev, out):
+        if t is not None and not t.is_cuda:
+            raise NotImplementedError('edvr_amd ops run on the GPU only (HIP/gfx950); got a CPU tensor')
+    u8 = frames.dtype == torch.uint8
+    if not u8 and frames.dtype != torch.float32:
+        raise NotImplementedError(f'edvr_amd: {frames.dtype} frames are not supported here (float32 CHW in [0, 1] or uint8 HWC)')
+    if frames.dim() != 4 or frames.shape[-1 if u8 else 1] != 3:
+        raise ValueError(f'frames are uint8 (n, H, W, 3) or float32 (n, 3, H, W), got {frames.dtype} {tuple(frames.shape)}')
+    n = frames.shape[0]
+    H, W = (frames.shape[1], frames.shape[2]) if u8 else (frames.shape[2], frames.shape[3])
+    if n < 1 or H < 1 or W < 1:
+        raise ValueError(f'frame_sad: no frames or empty frames, got {tuple(frames.shape)}')
+    if not (frames[0].is_contiguous() and (n == 1 or frames.stride(0) >= 3 * H * W)):
+        frames = frames.contiguous()
+    if prev is not None:
+        if prev.dim() == 4 and prev.shape[0] == 1:
+            prev = prev[0]
+        if prev.dtype != frames.dtype or tuple(prev.shape) != tuple(frames.shape[1:]):
+            raise ValueError(f'prev is one frame like those of `frames` ({frames.dtype} {tuple(frames.shape[1:])}), got {prev.dtype} {tuple(prev.shape)}')
+        prev = prev.contiguous()
+    if out is None:
+        out = torch.empty(n, dtype=torch.int64, device=frames.device)
+    elif out.dtype != torch.int64 or tuple(out.shape) != (n,) or not out.is_contiguous() or not out.is_cuda:
+        raise ValueError(f'out is a contiguous int64 ({n},) tensor on the GPU, got {out.dtype} {tuple(out.shape)}')
+    stride = frames.stride(0) if n > 1 else 3 * H * W
+    name = 'edvr_frame_sad_rgb_u8' if u8 else 'edvr_frame_sad_rgb_f32'
+    nbytes = float(n + (prev is not None)) * 3 * H * W * frames.element_size() + 8.0 * n  # each frame once
+    _run('frame_sad', lambda: _lib.check(getattr(_lib.lib(), name)(_ptr(frames), _ptr(prev), _ptr(out), n, H, W, stride, _stream()), name), 0, nbytes)
+    return out

@@ -326,10 +326,27 @@ class VideoRestorer:
     WHAT IT COSTS: shared, 2 x fusion, reconstruction and upsampling and 1 x alignment and attention per element (by the module
     definitions about 15 of 115 conv-units per output frame saved for each of the T frames of a window; DESIGN 4.10 has the
     measurement), the second copy of the modulated features (chunk x T x C x h x w float32) while the first tail runs, no further bank;
-    unshared, 2 x everything after the per-frame stage.  With uint8 output the float32 accumulator, as with an ensemble."""
+    unshared, 2 x everything after the per-frame stage.  With uint8 output the float32 accumulator, as with an ensemble.
+
+    cuts None | 'auto' | a strictly increasing sequence of frame indices c_1 < ... < c_k (frame c_j begins a new shot): windows stay
+    inside a shot.  The result is the concatenation of what this configuration WITHOUT cuts returns for each shot [c_j, c_(j+1))
+    restored as a video of its own - its own temporal padding, chunks (the last ones of a shot may be short, no chunk straddles a cut)
+    and temporal reversal; every other argument only ever sees one shot.  'auto' finds the cuts: ops.frame_sad measures
+    the 8-bit luma change between consecutive frames, shots.cut_scores turns it into ffmpeg's scene score on the 0 ... 255 scale, and
+    a frame scoring at least cut_threshold (default 10.0) begins a shot unless that would leave a shot shorter than min_shot (default
+    and lower bound max(num_frame, 2): what the circle paddings ask of a video) - shots.select_cuts.  Explicit cuts are checked
+    against the same lower bound: ValueError at construction, for the last shot where the length becomes known (`restore`: before any
+    launch; a stream: at its end); cut_threshold / min_shot without cuts='auto' likewise.  After a run `cuts_found` holds the cuts,
+    with 'auto' `cut_scores` and `cut_mafd` every frame's score and mean absolute difference.
+    WHERE THE HOST WAITS: explicit cuts - nowhere; 'auto' in `restore` - once, up front, for one launch over the whole video; 'auto'
+    on a stream - per arriving piece for its 8 k bytes, behind an event recorded right after that piece's frame_sad, i.e. before any
+    restoration work the piece leads to; the restorer pulls ONE piece ahead (measures piece p + 1 before it waits for piece p's
+    numbers), so that this event also lies ahead of the work of piece p - 1 and the GPU does not drain at every piece.  Beyond
+    today's, at most min_shot - 1 decided-upon frames and that one piece are held (as views of the caller's pieces)."""
 
     def __init__(self, net, num_frame=None, padding='reflection_circle', chunk=8, out_dtype=torch.float32, pad_mode=None, tile=None,
-                 tile_overlap=None, self_ensemble=None, tile_blend=None, time_reverse=False, share_alignment=None):
+                 tile_overlap=None, self_ensemble=None, tile_blend=None, time_reverse=False, share_alignment=None, cuts=None,
+                 cut_threshold=None, min_shot=None):
         if out_dtype not in (torch.float32, torch.uint8):
             raise ValueError(f'out_dtype must be torch.float32 or torch.uint8, got {out_dtype}')
         if pad_mode not in (None, 'reflect', 'replicate'):
@@ -364,7 +381,27 @@ class VideoRestorer:
         if ctr != self.num_frame // 2:
             raise ValueError(f'windows are centred on the frame they restore: center_frame_idx {ctr} != num_frame // 2 = {self.num_frame // 2}')
         self.capacity = WindowSchedule(self.num_frame, padding, self.chunk).capacity
-        self.bank = None        # [f1, f2, f3] rings of `slots` images; frame f lives in image f % slots
+        # scene cuts: None | 'auto' | a checked list; a shot is never shorter than what window_table asks of a video in the circle modes
+        floor = max(self.num_frame, 2)
+        auto = isinstance(cuts, str) and cuts == 'auto'
+        if not auto and (cut_threshold is not None or min_shot is not None):
+            raise ValueError("cut_threshold and min_shot steer the detector: they need cuts='auto'")
+        if min_shot is not None and (isinstance(min_shot, bool) or not isinstance(min_shot, int) or min_shot < floor):
+            raise ValueError(f'min_shot must be an integer of at least max(num_frame, 2) = {floor}, got {min_shot!r}')
+        self.min_shot = floor if min_shot is None else min_shot
+        self.cut_threshold = 10.0 if cut_threshold is None else float(cut_threshold)
+        if self.cut_threshold != self.cut_threshold:
+            raise ValueError('cut_threshold is NaN')
+        if cuts is not None and not auto:
+            if isinstance(cuts, str):
+                raise ValueError(f"cuts must be None, 'auto' or a strictly increasing sequence of frame indices, got {cuts!r}")
+            from .shots import check_cuts
+            cuts = check_cuts(cuts, self.min_shot)
+        self.cuts = cuts
+        self.cuts_found = None  # after a run with cuts: the cuts, in order; and with 'auto' ...
+        self.cut_scores = None  # ... every frame's score ...
+        self.cut_mafd = None    # ... and mean absolute frame difference (shots.cut_scores)
+        self.bank = None       # [f1, f2, f3] rings of `slots` images; frame f lives in image f % slots
         self.slots = 0
         self.schedule = None    # the WindowSchedule of the running restore
         self._groups = []       # (first frame, count, [bound or None per level], [depth per level]) of every extract call with live frames
@@ -601,26 +638,155 @@ class VideoRestorer:
                 self._pieces = [(f, p) for f, p in self._pieces if f + p.shape[0] > nxt]
                 yield out
 
+    # one shot = one video: a fresh schedule, bank(s) and piece list (_begin_shot), frames in (_feed), the end (_end_shot), clean-up (_clear)
+    def _begin_shot(self):
+        self.schedule = WindowSchedule(self.num_frame, self.padding, self.chunk, _probe=False)
+        self.bank, self._groups, self._pieces = None, [], []
+        self.grid = self.blend_grid = self.pairs = self.banks = self._tile_groups = None
+
+    def _feed(self, piece, length):
+        """`piece` (what _as_frames returned; with cuts a view of it that ends at the cut) joins the running shot."""
+        if self.tiled and self._pieces and piece.dtype != self._pieces[-1][1].dtype:
+            raise ValueError(f'the frames of one video share one dtype: {piece.dtype} after {self._pieces[-1][1].dtype}')
+        self._pieces.append((self.schedule.arrived, piece))
+        yield from self._run(self.schedule.push(piece.shape[0]), length)
+
+    def _end_shot(self, length):
+        yield from self._run(self.schedule.finish(), length)
+
+    def _clear(self):
+        self.bank, self._groups, self._pieces = None, [], []  # (the schedule and the tile grid stay for inspection)
+        self.banks = self._tile_groups = None
+
     def restore_chunks(self, frames, length=None):
         """restore_iter that yields each chunk's output tensor ((b, 3, H', W') or (b, H', W', 3)) instead of single frames.
         length: the number of frames if known - a video shorter than `capacity` then gets a smaller bank."""
         self._check_mode()
-        self.schedule = sched = WindowSchedule(self.num_frame, self.padding, self.chunk, _probe=False)
-        self.bank, self._groups, self._pieces = None, [], []
-        self.grid = self.blend_grid = self.pairs = self.banks = self._tile_groups = None
+        if self.cuts is not None:
+            yield from self._restore_shots(frames, length, self.cuts)
+            return
+        self._begin_shot()
         try:
             for item in frames:
                 piece = self._as_frames(item)
                 if piece.shape[0] == 0:
                     continue
-                if self.tiled and self._pieces and piece.dtype != self._pieces[-1][1].dtype:
-                    raise ValueError(f'the frames of one video share one dtype: {piece.dtype} after {self._pieces[-1][1].dtype}')
-                self._pieces.append((sched.arrived, piece))
-                yield from self._run(sched.push(piece.shape[0]), length)
-            yield from self._run(sched.finish(), length)
+                yield from self._feed(piece, length)
+            yield from self._end_shot(length)
         finally:
-            self.bank, self._groups, self._pieces = None, [], []  # (the schedule and the tile grid stay for inspection)
-            self.banks = self._tile_groups = None
+            self._clear()
+
+    # ---- scene cuts: every shot is a video of its own
+    def _sad_to_host(self, piece, prev):
+        """ops.frame_sad of an arriving piece against the last frame before it, on its way into pinned memory: (host int64 (k,), event).
+        Launched BEFORE any restoration work the piece leads to, so the event waits for nothing that comes after the piece."""
+        sad = ops.frame_sad(piece, prev)
+        host = torch.empty(sad.shape, dtype=torch.int64, pin_memory=True)
+        host.copy_(sad, non_blocking=True)
+        event = torch.cuda.Event()
+        event.record()
+        return host, event
+
+    def _wait_sad(self, host, event):
+        event.synchronize()  # the one place the host waits with cuts='auto'
+        return host.tolist()
+
+    def _restore_shots(self, frames, length, cuts):
+        """restore_chunks with cuts: the pieces are split at the cuts, each shot runs through _begin_shot / _feed / _end_shot as a video
+        of its own (its own temporal padding, chunks and - per tile and element - banks), and no chunk straddles a cut.  cuts: a checked
+        list, or 'auto' - then an arriving piece is measured (ops.frame_sad against the last frame of the piece before, which is kept
+        alive) as soon as it is pulled, one piece ahead of the one being decided, a ShotDetector decides, and a frame joins its shot
+        once no undecided candidate precedes it (at most min_shot - 1 frames wait, as views of the caller's pieces)."""
+        from .shots import ShotDetector, check_cuts
+        auto = isinstance(cuts, str)
+        det = ShotDetector(self.cut_threshold, self.min_shot) if auto else None
+        if not auto and length is not None:
+            check_cuts(cuts, self.min_shot, int(length))  # the last shot too, before any launch
+        self.cuts_found, self.cut_scores, self.cut_mafd = [], ([] if auto else None), ([] if auto else None)
+        pending = list(cuts) if not auto else []  # cuts not reached yet
+        held = []        # (first frame, piece): arrived frames that have not joined a shot yet
+        arrived = fed = start = 0
+        last = None      # auto: the last frame that arrived
+        dtype = None
+
+        def shot_length(begin):
+            if auto or length is None:
+                return None
+            return (pending[0] if pending else int(length)) - begin
+
+        def release(upto, new_cuts):
+            """frames [fed, upto) join their shots; new_cuts: the cuts among them (each ends the running shot)"""
+            nonlocal fed, start, held
+            stops = [c for c in new_cuts if fed <= c <= upto] + [upto]  # (a cut at `fed`: the piece before ended where the shot does)
+            for stop in stops:
+                for first, piece in held:
+                    lo, hi = max(fed, first), min(stop, first + piece.shape[0])
+                    if lo < hi:
+                        yield from self._feed(piece[lo - first:hi - first], shot_length(start))
+                fed = max(fed, stop)
+                if stop in new_cuts:
+                    yield from self._end_shot(shot_length(start))
+                    self._clear()
+                    self.cuts_found.append(stop)
+                    if pending and pending[0] == stop:
+                        pending.pop(0)
+                    start = stop
+                    self._begin_shot()
+            held = [(f, p) for f, p in held if f + p.shape[0] > fed]
+
+        def pieces():
+            nonlocal dtype
+            for item in frames:
+                piece = self._as_frames(item)
+                if piece.shape[0] == 0:
+                    continue
+                if dtype is not None and piece.dtype != dtype:
+                    raise ValueError(f'the frames of one video share one dtype: {piece.dtype} after {dtype}')
+                dtype = piece.dtype
+                yield piece
+
+        def measured():
+            """auto: (piece, host, event) - a piece leaves when the piece AFTER it has been pulled and measured (or the input has ended),
+            so its event lies ahead of the restoration work of the piece before it in the stream: the host's wait for it ends while
+            that work still runs, and the GPU does not drain at every piece."""
+            nonlocal last
+            ahead = None
+            for piece in pieces():
+                now = (piece,) + self._sad_to_host(piece, last)
+                last = piece[-1]
+                if ahead is not None:
+                    yield ahead
+                ahead = now
+            if ahead is not None:
+                yield ahead
+
+        self._begin_shot()
+        try:
+            for item in (measured() if auto else pieces()):
+                piece = item[0] if auto else item
+                held.append((arrived, piece))
+                arrived += piece.shape[0]
+                if auto:
+                    size = self._frame_size(piece) if piece.dtype == torch.uint8 else tuple(piece.shape[2:4])
+                    new = det.push_sad(self._wait_sad(*item[1:]), size[0] * size[1])
+                    upto = det.released
+                else:
+                    new = [c for c in pending if c < arrived]  # a cut at `arrived` is acted on when its frame is here
+                    upto = arrived
+                yield from release(upto, new)
+            if auto:
+                new = det.finish()
+                self.cut_scores, self.cut_mafd = list(det.scores), list(det.mafd)
+            else:
+                new = []
+                check_cuts(cuts, self.min_shot, arrived)  # the stream has ended: cuts beyond it, or a last shot too short
+            if arrived:
+                yield from release(arrived, new)
+                yield from self._end_shot(shot_length(start))
+        finally:
+            if auto:
+                self.cut_scores, self.cut_mafd = list(det.scores), list(det.mafd)
+            self._clear()
 
     def restore_iter(self, frames, length=None):
         """Streaming form: `frames` is an iterable of frames ((3, H, W) float32 / (H, W, 3) uint8) or of small batches of them, of
@@ -637,5 +803,23 @@ class VideoRestorer:
             raise ValueError(f'expected (N, 3, H, W) float32 or (N, H, W, 3) uint8 frames, got {tuple(lq.shape)}')
         if lq.shape[0] == 0:
             raise ValueError('restore: no frames')
-        outs = list(self.restore_chunks(lq.split(self.chunk), length=lq.shape[0]))
+        n = lq.shape[0]
+        if self.cuts is None:
+            outs = list(self.restore_chunks(lq.split(self.chunk), length=n))
+        else:
+            from .shots import check_cuts, cut_scores, select_cuts
+            if self.cuts == 'auto':  # the length is known: one launch over the whole video and one wait, up front
+                u8 = lq.dtype == torch.uint8
+                if lq.dtype not in (torch.uint8, torch.float32) or lq.shape[-1 if u8 else 1] != 3:
+                    raise ValueError(f'expected (N, 3, H, W) float32 or (N, H, W, 3) uint8 frames, got {lq.dtype} {tuple(lq.shape)}')
+                H, W = self._frame_size(lq)
+                mafd, scores = cut_scores(self._wait_sad(*self._sad_to_host(lq, None)), H * W)
+                cuts = select_cuts(scores, n, self.cut_threshold, self.min_shot)
+            else:
+                cuts, mafd, scores = check_cuts(self.cuts, self.min_shot, n), None, None
+            # every shot arrives as restore() of the shot alone would hand it in: the same launches on the same data
+            bounds = [0] + cuts + [n]
+            pieces = [p for a, b in zip(bounds, bounds[1:]) for p in lq[a:b].split(self.chunk)]
+            outs = list(self._restore_shots(pieces, n, cuts))
+            self.cut_mafd, self.cut_scores = mafd, scores
         return outs[0] if len(outs) == 1 else torch.cat(outs, 0)

@@ -152,7 +152,7 @@ class Y4MWriter:
         self.frames_written += buf.shape[0]
 
 
-def restore_y4m(net, src, dst, *, matrix_in=None, matrix_out=None, chroma='bilinear', read_frames=8, on_chunk=None, **restorer_kwargs):
+def restore_y4m(net, src, dst, *, matrix_in=None, matrix_out=None, chroma='bilinear', read_frames=8, on_chunk=None, stats=None, **restorer_kwargs):
     """Restore a Y4M stream with `net` (an EDVR in eval mode, on the GPU) into a Y4M stream; returns the number of frames.  Call it under
     torch.no_grad().
 
@@ -168,7 +168,11 @@ def restore_y4m(net, src, dst, *, matrix_in=None, matrix_out=None, chroma='bilin
     of 4 (16 with hr_in) need pad_mode.  Memory: read_frames input frames per buffer, the restorer's bank and pieces, two chunks of output.
     The host writes chunk i while the device works on chunk i + 1; nothing else waits.  on_chunk: called as on_chunk(chunk) with every
     restored float32 RGB chunk (k, 3, s H, s W) on the device, in order, before it is converted back - for scoring the output
-    (metrics.calculate_niqe) or a preview; it must not modify the chunk.  Without it the launches are unchanged."""
+    (metrics.calculate_niqe) or a preview; it must not modify the chunk.  Without it the launches are unchanged.
+    cuts (a restorer_kwarg, with cut_threshold / min_shot): None | 'auto' | frame indices - windows stay inside a shot (VideoRestorer);
+    'auto' scores the decoded float32 RGB, piece by piece as it is read.  The chunks that leave are then short at the end of every shot;
+    nothing here depends on their size.  stats: a dict that receives 'frames' and, with cuts, 'cuts', 'cut_scores' and 'cut_mafd' (the
+    restorer's cuts_found / cut_scores / cut_mafd) when the stream has ended."""
     from .video import VideoRestorer
     reader = src if isinstance(src, Y4MReader) else Y4MReader(src)
     if int(read_frames) < 1:
@@ -220,4 +224,8 @@ def restore_y4m(net, src, dst, *, matrix_in=None, matrix_out=None, chroma='bilin
     flush()
     if hasattr(dst, 'flush'):
         dst.flush()
+    if stats is not None:
+        stats['frames'] = writer.frames_written
+        if getattr(vr, 'cuts', None) is not None:
+            stats.update(cuts=vr.cuts_found, cut_scores=vr.cut_scores, cut_mafd=vr.cut_mafd)
     return writer.frames_written

@@ -711,6 +711,19 @@ int edvr_rgb_to_yuv420_f32(const float *rgb, uint8_t *yuv, int n, int H, int W, 
                            edvr_stream_t stream);
 int edvr_rgb_to_yuv420_u8(const uint8_t *rgb, uint8_t *yuv, int n, int H, int W, int64_t yuv_stride, const float *coef, edvr_stream_t stream);
 
+/* Frame-to-frame change for scene-cut detection (csrc/shots.hip; definition: DESIGN 4.13).  The bytes R, G, B of a pixel are the input's
+ * own (_u8: x (n, H, W, 3)) or its tensor2img bytes (_f32: x (n, 3, H, W); clamp to [0, 1], x 255, round half to even, NaN -> 0); in
+ * integers Y8 = ((66 R + 129 G + 25 B + 128) >> 8) + 16, and
+ *   sad[j] = sum over the H W pixels of |Y8 of frame j - Y8 of frame j - 1| for j >= 1;  sad[0] the same against the frame `prev` (one
+ *   dense frame of x's type, e.g. the last one of the batch before), or 0 where prev == NULL.
+ * Exact 64-bit integers (at most 219 H W): a pair's number does not depend on the batch it was computed in.  Each frame is dense; the
+ * frames of the batch lie img_stride ELEMENTS (bytes / floats) apart at any base address, 0 = dense.  16-byte loads where x, prev and
+ * the stride in bytes are multiples of 16 (_f32: and H W of 4), single bytes / floats otherwise; same values either way.  ONE kernel
+ * launch, grid (blocks per frame, pairs), behind a clear of sad[0 ... n) on the same stream; one 64-bit integer atomic add per block.
+ * EDVR_ERR_ARG: x or sad NULL, n, H or W < 1, H W > 2^31 - 1, 0 < img_stride < 3 H W with n > 1.  No allocation, no wait. */
+int edvr_frame_sad_rgb_u8(const uint8_t *x, const uint8_t *prev, uint64_t *sad, int n, int H, int W, int64_t img_stride, edvr_stream_t stream);
+int edvr_frame_sad_rgb_f32(const float *x, const float *prev, uint64_t *sad, int n, int H, int W, int64_t img_stride, edvr_stream_t stream);
+
 /* Multi-tensor Adam step <- torch.optim.Adam.step() as the reference builds it (basicsr/models/edvr_model.py:21-53, parameter
  * groups with dcn_lr_mul; stepped in sr_model.py:112).  `chunk_table` is a DEVICE array of n_chunks records of
  * edvr_adam_chunk_bytes() = 64 bytes: { float *p; const float *g; float *m; float *v; int32 n (<= 65536 elements of one tensor);

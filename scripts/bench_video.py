@@ -32,6 +32,12 @@ Temporal reversal (VideoRestorer time_reverse), same method, merged into profile
 
     python scripts/bench_video.py --time-reverse --config L_T5 [--self-ensemble flip4]   # plain against both arms (share_alignment True /
                                                                                          # False): frames/s, peak memory, the pair kernel's share
+
+Scene cuts (VideoRestorer cuts), merged into profiles/video/bench_video_cuts.json:
+
+    python scripts/bench_video.py --scene-cuts --config L_T5   # ops.frame_sad alone (time, share of the HBM rate); a restore streamed in
+                                                               # pieces of 8 with cuts=None, cuts='auto' on the same cut-free video and
+                                                               # cuts='auto' on a video with a cut every 25 frames: frames/s, host waits
 """
 import argparse
 import json
@@ -380,6 +386,112 @@ def leg_time(args, net, kwargs, dev, frames, chunk):
             'max_abs_difference_to_plain_output': (outs['shared'].float() - outs['plain'].float()).abs().max().item(), **res}
 
 
+HBM_MEASURED_TBS = 6.29  # the rate the copy benchmark of this project reaches on an MI355X
+
+
+def _moving_texture(n, h, w, seed, dev, k=17):
+    """One shot: a smooth random texture seen through a window that moves one pixel down and right per frame, float32 (n, 3, h, w)."""
+    import torch.nn.functional as F
+    base = torch.rand(1, 3, h + n + k - 1, w + n + k - 1, generator=torch.Generator().manual_seed(seed)).to(dev)
+    x = F.pad(base, (k // 2,) * 4, mode='reflect')
+    x = F.avg_pool2d(F.avg_pool2d(x, k, stride=1), k, stride=1)
+    x = (x - x.min()) / (x.max() - x.min())
+    return torch.stack([x[0, :, t:t + h, t:t + w] for t in range(n)]).contiguous()
+
+
+def _time_frame_sad(make, copies, launches=200):
+    """Mean time of one ops.frame_sad call (the clear of the result and the kernel) over `launches` calls that walk through `copies`
+    distinct inputs - more bytes than the caches hold, so that every call reads its frames from memory."""
+    from edvr_amd import ops
+    bufs = [make(i) for i in range(copies)]
+    out = torch.empty(bufs[0].shape[0], dtype=torch.int64, device=bufs[0].device)
+    for b in bufs[:4]:
+        ops.frame_sad(b, out=out)
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for i in range(launches):
+        ops.frame_sad(bufs[i % copies], out=out)
+    e1.record()
+    e1.synchronize()
+    us = e0.elapsed_time(e1) * 1e3 / launches
+    n, per = bufs[0].shape[0], bufs[0][0].numel() * bufs[0].element_size()
+    once, asked = n * per, 2 * (n - 1) * per  # every frame once; what the n - 1 pairs load (each inner frame twice, the second time from a cache)
+    return {'shape': list(bufs[0].shape), 'dtype': str(bufs[0].dtype).replace('torch.', ''), 'distinct_inputs': copies, 'launches': launches,
+            'microseconds': round(us, 2), 'bytes_each_frame_once': once, 'bytes_loaded': asked,
+            'share_of_hbm_rate_each_frame_once': round(once / (us * 1e-6) / (HBM_MEASURED_TBS * 1e12), 4),
+            'share_of_hbm_rate_bytes_loaded': round(asked / (us * 1e-6) / (HBM_MEASURED_TBS * 1e12), 4)}
+
+
+def leg_cuts(args, net, kwargs, dev, frames, chunk):
+    """Scene cuts: ops.frame_sad on its own, and what cuts='auto' costs a streamed restore - (a) cuts=None, (b) cuts='auto' on the same
+    cut-free video (the detector's whole cost: its launches and the host's waits), (c) cuts='auto' on a video with a cut every 25 frames
+    (the short chunks at the shots' ends on top).  Pieces of 8 frames, the arms alternated, median and spread of `repeats` runs."""
+    import time
+    from edvr_amd import VideoRestorer
+    h, w = CONFIGS[args.config][1]
+    g = torch.Generator().manual_seed(0)
+    sad = {'f32_8x3x180x320': _time_frame_sad(lambda i: torch.rand(8, 3, 180, 320, generator=g).to(dev), 64),
+           'u8_8x720x1280x3': _time_frame_sad(lambda i: torch.randint(0, 256, (8, 720, 1280, 3), generator=g, dtype=torch.uint8).to(dev), 24)}
+    one_shot = _moving_texture(frames, h, w, 100, dev)
+    shot = 25
+    several = torch.cat([_moving_texture(min(shot, frames - a), h, w, 200 + a, dev) for a in range(0, frames, shot)])
+    want_cuts = list(range(shot, frames, shot)) if frames % shot == 0 or frames % shot >= kwargs['num_frame'] else None
+    base = dict(padding=args.padding, chunk=chunk, out_dtype=getattr(torch, args.out_dtype))
+    plain, auto = VideoRestorer(net, **base), VideoRestorer(net, cuts='auto', **base)
+    waited = [0.0]
+    wait_sad = auto._wait_sad
+
+    def timed_wait(host, event):
+        t0 = time.perf_counter()
+        v = wait_sad(host, event)
+        waited[0] += time.perf_counter() - t0
+        return v
+
+    auto._wait_sad = timed_wait
+
+    def stream(vr, lq):
+        def run():
+            for out in vr.restore_chunks(lq.split(8)):
+                del out
+        return run
+
+    arms = {'a_cuts_none': stream(plain, one_shot), 'b_auto_no_cut': stream(auto, one_shot), 'c_auto_cut_every_25': stream(auto, several)}
+    res = {k: {'s': [], 'host_wait_s': []} for k in arms}
+    for k, fn in arms.items():  # warm-up, and what the detector found
+        fn()
+        torch.cuda.synchronize()
+        if k != 'a_cuts_none':
+            res[k]['cuts_found'] = list(auto.cuts_found)
+            res[k]['largest_score_off_the_cuts'] = round(max(s for i, s in enumerate(auto.cut_scores) if i not in auto.cuts_found), 3)
+            if auto.cuts_found:
+                res[k]['smallest_score_at_a_cut'] = round(min(auto.cut_scores[i] for i in auto.cuts_found), 3)
+    assert res['b_auto_no_cut']['cuts_found'] == [], res['b_auto_no_cut']
+    assert want_cuts is None or res['c_auto_cut_every_25']['cuts_found'] == want_cuts, res['c_auto_cut_every_25']
+    for _ in range(args.repeats):
+        for k, fn in arms.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            waited[0] = 0.0
+            e0.record()
+            fn()
+            e1.record()
+            e1.synchronize()
+            res[k]['s'].append(e0.elapsed_time(e1) * 1e-3)
+            res[k]['host_wait_s'].append(round(waited[0], 4))
+    net.check_offsets()
+    for r in res.values():
+        sec = r.pop('s')
+        r['seconds'] = [round(v, 4) for v in sec]
+        r['frames_per_s'] = round(frames / statistics.median(sec), 3)
+        r['spread'] = round((max(sec) - min(sec)) / statistics.median(sec), 4)
+    res['a_cuts_none'].pop('host_wait_s')
+    a, b, c = (res[k]['frames_per_s'] for k in ('a_cuts_none', 'b_auto_no_cut', 'c_auto_cut_every_25'))
+    return {'leg': 'cuts', 'hw': [h, w], 'piece': 8, 'hbm_measured_tbs': HBM_MEASURED_TBS, 'frame_sad': sad,
+            'detector_cost_b_over_a': round(1.0 - b / a, 4), 'detector_cost_beyond_spread_of_a': bool(1.0 - b / a > res['a_cuts_none']['spread']),
+            'short_chunks_cost_c_over_a': round(1.0 - c / a, 4), **res}
+
+
 def main_leg(args):
     from edvr_amd import _lib
     from edvr_amd.build import source_hash
@@ -389,13 +501,13 @@ def main_leg(args):
     net = _build_net(kwargs, dev)
     with torch.no_grad():
         legs = {'pad': leg_pad, 'tiles': leg_tiles, 'seam': leg_seam, 'large': leg_large, 'ensemble': leg_ensemble, 'blend': leg_blend,
-                'time': leg_time}
+                'time': leg_time, 'cuts': leg_cuts}
         result = legs[args.leg](args, net, kwargs, dev, frames, chunk)
     result = {'config': args.config, 'edvr': dict(kwargs), 'frames': frames, 'chunk': chunk, 'padding': args.padding, 'out_dtype': args.out_dtype,
               'repeats': args.repeats, **result, 'csrc_sha16': source_hash(), 'library': _lib.lib().edvr_version().decode(),
               'device': torch.cuda.get_device_name(0)}
     default = {'ensemble': 'bench_video_ensemble.json', 'blend': 'bench_video_blend.json',
-               'time': 'bench_video_time.json'}.get(args.leg, 'bench_video_tiles.json')
+               'time': 'bench_video_time.json', 'cuts': 'bench_video_cuts.json'}.get(args.leg, 'bench_video_tiles.json')
     path = os.path.abspath(args.json or os.path.join(os.path.dirname(os.path.abspath(__file__)), '..', 'profiles', 'video', default))
     os.makedirs(os.path.dirname(path), exist_ok=True)
     merged = json.load(open(path)) if os.path.exists(path) else {}
@@ -425,7 +537,15 @@ def parse_args(argv=None):
     ap.add_argument('--time-reverse', action='store_true',
                     help='timing arm: time_reverse (both share_alignment arms) against the VideoRestorer without it, with --self-ensemble on '
                          'top of that ensemble (profiles/video/bench_video_time.json)')
+    ap.add_argument('--scene-cuts', action='store_true',
+                    help="ops.frame_sad on its own, and a streamed restore with cuts=None against cuts='auto' without and with cuts "
+                         '(profiles/video/bench_video_cuts.json)')
     args = ap.parse_args(argv)
+    if args.scene_cuts:
+        if args.leg or args.self_ensemble or args.time_reverse or args.tile_blend is not None:
+            ap.error('--scene-cuts is a leg of its own: give it without --leg / --self-ensemble / --time-reverse / --tile-blend')
+        args.leg = 'cuts'
+        return args
     if args.tile_blend is not None:
         if args.leg or args.self_ensemble or args.time_reverse:
             ap.error('--tile-blend is a leg of its own: give it without --leg / --self-ensemble / --time-reverse')

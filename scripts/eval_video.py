@@ -87,6 +87,8 @@ def evaluate(args, log=print):
     # frames of any size (--pad-mode / --tile / --tile-overlap / --tile-blend): passed on only where given
     any_size = {k: (tuple(v) if k == 'tile' else v) for k in ('pad_mode', 'tile', 'tile_overlap', 'tile_blend')
                 for v in [getattr(args, k, None)] if v is not None}
+    if getattr(args, 'scene_cuts', None) is not None:  # --scene-cuts [THR]: folders that hold more than one shot
+        any_size.update(cuts='auto', cut_threshold=float(args.scene_cuts))
     ensemble, reverse = getattr(args, 'self_ensemble', None), bool(getattr(args, 'time_reverse', False))
     # what the second pass runs, and how it is called in the report
     plus_kw = {**({'self_ensemble': ensemble} if ensemble else {}), **({'time_reverse': True} if reverse else {})}
@@ -211,6 +213,9 @@ def parse_args(argv=None):
                          'at most the overlap)')
     ap.add_argument('--self-ensemble', default=None, choices=['flip4', 'd4'],
                     help='also restore under the 4 flips / the 8 symmetries of the square and average; reported beside the plain PSNR (n x the time)')
+    ap.add_argument('--scene-cuts', type=float, nargs='?', const=10.0, default=None, metavar='THR',
+                    help="find scene cuts in every clip (VideoRestorer's cuts='auto': a frame whose scene score reaches THR, default 10, "
+                         'begins a shot) and restore every shot as a video of its own')
     ap.add_argument('--time-reverse', action='store_true',
                     help='also restore the video in reversed frame order and average (x2; composes with --self-ensemble); reported beside the '
                          'plain PSNR')

@@ -10,7 +10,10 @@ number of output frames per pass; `--matrix-in` / `--matrix-out` default to the 
 columns or 577 rows, BT.601 below), `--chroma` picks the chroma upsampling filter of the decode.  `--niqe PARAMS.npz` scores the result with
 the no-reference NIQE (metrics.calculate_niqe against BasicSR's niqe_pris_params.npz; lower is better) on the float32 frames before they
 are converted back, and the decoded input at its own size beside it where at least two 96 x 96 blocks fit; `--niqe-json FILE` writes
-both lists.  Everything this script prints goes to stderr: stdout may be the video.
+both lists.  `--scene-cuts [THR]` finds hard cuts (VideoRestorer's cuts='auto': ffmpeg's scene score on the 0 ... 255 scale, default 10) and
+restores every shot as a video of its own, so that no frame's window mixes two scenes; `--min-shot N` bounds the shot length from below,
+`--cuts I [I ...]` gives the cuts instead, `--cuts-json FILE` writes the cuts, every frame's mafd and score, the threshold and min_shot.
+Everything this script prints goes to stderr: stdout may be the video.
 """
 import argparse
 import os
@@ -41,6 +44,8 @@ def restore(args, log=log):
               for v in [getattr(args, k, None)] if v is not None}
     if getattr(args, 'time_reverse', False):
         kwargs['time_reverse'] = True
+    kwargs.update(cut_kwargs(args))
+    stats = {}
     src = sys.stdin.buffer if args.input == '-' else open(args.input, 'rb')
     dst = sys.stdout.buffer if args.output == '-' else open(args.output, 'wb')
     try:
@@ -65,11 +70,14 @@ def restore(args, log=log):
         t0 = time.time()
         with torch.no_grad():
             n = restore_y4m(net, reader, dst, matrix_in=args.matrix_in, matrix_out=args.matrix_out, chroma=args.chroma,
-                            read_frames=args.read_frames, num_frame=args.num_frame, padding=args.padding, chunk=args.batch, **kwargs)
+                            read_frames=args.read_frames, num_frame=args.num_frame, padding=args.padding, chunk=args.batch, stats=stats,
+                            **kwargs)
         net.check_offsets()
         torch.cuda.synchronize()
         dt = time.time() - t0
         log(f'{args.output}: {n} frames in {dt:.1f} s ({n / max(dt, 1e-9):.2f} frames/s)')
+        if 'cuts' in stats:
+            report_cuts(args, stats, log)
         if niqe_path:
             report_niqe(args, niqe_out, niqe_in, log)
     finally:
@@ -78,6 +86,32 @@ def restore(args, log=log):
         if dst is not sys.stdout.buffer:
             dst.close()
     return n
+
+
+def cut_kwargs(args):
+    """VideoRestorer's scene-cut arguments from --scene-cuts / --min-shot / --cuts ({} without them)."""
+    if getattr(args, 'cuts', None) is not None:
+        return {'cuts': list(args.cuts)}
+    if getattr(args, 'scene_cuts', None) is None:
+        return {}
+    out = {'cuts': 'auto', 'cut_threshold': float(args.scene_cuts)}
+    if getattr(args, 'min_shot', None) is not None:
+        out['min_shot'] = args.min_shot
+    return out
+
+
+def report_cuts(args, stats, log=log):
+    """The cuts a run found or was given; with --cuts-json the cuts, every frame's mafd and score, the threshold and min_shot."""
+    cuts = stats['cuts']
+    log(f'{args.input}: {len(cuts) + 1} shot(s) in {stats["frames"]} frames, cuts at {cuts}')
+    if getattr(args, 'cuts_json', None):
+        import json
+        auto = getattr(args, 'cuts', None) is None
+        record = {'frames': stats['frames'], 'cuts': cuts, 'mafd': stats['cut_mafd'], 'score': stats['cut_scores'],
+                  'threshold': float(args.scene_cuts) if auto else None,
+                  'min_shot': (args.min_shot if args.min_shot is not None else max(args.num_frame, 2))}
+        with open(args.cuts_json, 'w') as f:
+            json.dump(record, f, indent=1)
 
 
 def report_niqe(args, niqe_out, niqe_in, log=log):
@@ -126,7 +160,25 @@ def parse_args(argv=None):
     ap.add_argument('--niqe', default=None, metavar='PARAMS.npz',
                     help="score the output (and the input, where two 96 x 96 blocks fit) with NIQE; PARAMS.npz is BasicSR's niqe_pris_params.npz")
     ap.add_argument('--niqe-json', default=None, metavar='FILE', help='with --niqe: write the per-frame and mean NIQE there')
+    ap.add_argument('--scene-cuts', type=float, nargs='?', const=10.0, default=None, metavar='THR',
+                    help='find scene cuts and restore every shot as a video of its own: a frame whose scene score (ffmpeg\'s, 0 ... 255 scale) '
+                         'reaches THR (default 10) begins a shot')
+    ap.add_argument('--min-shot', type=int, default=None, metavar='N',
+                    help='with --scene-cuts: no shot shorter than N frames (default and lower bound: max(--num-frame, 2))')
+    ap.add_argument('--cuts', type=int, nargs='+', default=None, metavar='I', help='the cuts themselves: frame I begins a new shot')
+    ap.add_argument('--cuts-json', default=None, metavar='FILE',
+                    help='with --scene-cuts or --cuts: write the cuts, every frame\'s mafd and score, the threshold and min_shot there')
     args = ap.parse_args(argv)
+    if args.cuts is not None and args.scene_cuts is not None:
+        ap.error('--cuts and --scene-cuts exclude each other')
+    if args.min_shot is not None and args.scene_cuts is None:
+        ap.error('--min-shot needs --scene-cuts')
+    if args.min_shot is not None and args.min_shot < max(args.num_frame, 2):
+        ap.error(f'--min-shot is at least max(--num-frame, 2) = {max(args.num_frame, 2)}')
+    if args.cuts_json is not None and args.cuts is None and args.scene_cuts is None:
+        ap.error('--cuts-json needs --scene-cuts or --cuts')
+    if args.cuts is not None and (args.cuts[0] < 1 or any(b <= a for a, b in zip(args.cuts, args.cuts[1:]))):
+        ap.error('--cuts are strictly increasing frame indices, at least 1')
     if args.niqe_json is not None and args.niqe is None:
         ap.error('--niqe-json needs --niqe')
     if args.tile_blend is not None and args.tile is None:
