@@ -100,6 +100,8 @@ PROTOTYPES = {
     'edvr_yuv420_to_rgb_u8': (i32, [vp, vp, i32, i32, i32, i64, vp, i32, vp]),
     'edvr_rgb_to_yuv420_f32': (i32, [vp, vp, i32, i32, i32, i64, i64, vp, vp]),
     'edvr_rgb_to_yuv420_u8': (i32, [vp, vp, i32, i32, i32, i64, vp, vp]),
+    'edvr_yuv_to_rgb_f32': (i32, [vp, vp, i32, i32, i32, i32, i32, i32, i64, i64, vp, i32, vp]),
+    'edvr_rgb_to_yuv_f32': (i32, [vp, vp, i32, i32, i32, i32, i32, i32, i64, i64, vp, vp]),
     'edvr_frame_sad_rgb_u8': (i32, [vp, vp, vp, i32, i32, i32, i64, vp]),
     'edvr_frame_sad_rgb_f32': (i32, [vp, vp, vp, i32, i32, i32, i64, vp]),
     'edvr_adam_chunk_bytes': (sz, []),

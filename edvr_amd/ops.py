@@ -1881,22 +1881,31 @@ def yuv420_frame_size(H, W):
     return H * W + 2 * ((H + 1) // 2) * ((W + 1) // 2)
 
 
-def yuv_coeffs(matrix='bt601', range='limited'):
-    """(M, Mi, off) in float64 (nested lists): M maps RGB in 0 ... 255 to (Y, Cb, Cr) before the offsets off = (yoff, 128, 128), Mi is its
-    inverse (adjugate over determinant, every step one float64 operation).  The kernels get both rounded to float32."""
+def yuv_coeffs(matrix='bt601', range='limited', depth=8):
+    """(M, Mi, off) in float64 (nested lists): M maps RGB in 0 ... 255 to (Y, Cb, Cr) before the offsets off = (yoff, coff, coff), Mi is its
+    inverse (adjugate over determinant, every step one float64 operation).  The kernels get both rounded to float32.  depth 8 ... 16
+    (DESIGN 4.14), k = 2^(depth - 8): 'limited' scales luma to 219 k and chroma to 224 k with offsets (16 k, 128 k), 'full' both to
+    2^depth - 1 with offsets (0, 2^(depth - 1)); at depth 8 these are the 8-bit numbers, (yoff, 128, 128)."""
     if matrix not in YUV_MATRICES:
         raise ValueError(f'matrix must be one of {sorted(YUV_MATRICES)}, got {matrix!r}')
     if range not in YUV_RANGES:
         raise ValueError(f'range must be one of {sorted(YUV_RANGES)}, got {range!r}')
+    if depth != int(depth) or not 8 <= depth <= 16:
+        raise ValueError(f'depth must be 8 ... 16, got {depth!r}')
     kr, kb = YUV_MATRICES[matrix]
     kg = 1.0 - kr - kb
     ys, cs, yoff = YUV_RANGES[range]
+    k = float(1 << (int(depth) - 8))
+    if range == 'full':
+        ys = cs = float((1 << int(depth)) - 1)
+    else:
+        ys, cs, yoff = ys * k, cs * k, yoff * k
     sy, scb, scr = ys / 255.0, cs / 255.0 / (2.0 * (1.0 - kb)), cs / 255.0 / (2.0 * (1.0 - kr))
     m = [[sy * kr, sy * kg, sy * kb], [scb * -kr, scb * -kg, scb * (1.0 - kb)], [scr * (1.0 - kr), scr * -kg, scr * -kb]]
     (a, b, c), (d, e, f), (g, h, i) = m
     adj = [[e * i - f * h, c * h - b * i, b * f - c * e], [f * g - d * i, a * i - c * g, c * d - a * f], [d * h - e * g, b * g - a * h, a * e - b * d]]
     det = a * adj[0][0] + b * adj[1][0] + c * adj[2][0]
-    return m, [[v / det for v in row] for row in adj], [yoff, 128.0, 128.0]
+    return m, [[v / det for v in row] for row in adj], [yoff, 128.0 * k, 128.0 * k]
 
 
 def _yuv_coef_arg(mat, off):
@@ -1996,6 +2005,111 @@ def rgb_to_yuv420(rgb, matrix='bt601', range='limited', out=None):
     else:
         _run('rgb_to_yuv420', lambda: _lib.check(_lib.lib().edvr_rgb_to_yuv420_f32(_ptr(rgb), _ptr(out), n, H, W, _img_stride(rgb), stride, coef, _stream()),
                                                  'edvr_rgb_to_yuv420_f32'), 0, nbytes)
+    return out
+
+
+# ------------------------------------------------------------------------------------------------ every Y4M format (csrc/yuv_formats.hip)
+YUV_SUBSAMPLINGS = {'420': (1, 1), '422': (1, 0), '444': (0, 0)}                    # (sx, sy): log2 of the chroma decimation per axis
+_YUV_ALIASES = {'420jpeg': '420', '420mpeg2': '420', '420paldv': '420'}
+
+
+def yuv_format(name):
+    """A Y4M format name -> (sx, sy, depth, canonical): '420' | '422' | '444' (chroma planes ((H + sy) >> sy, (W + sx) >> sx)) with an
+    optional suffix p9 ... p16 for the bit depth (none: 8 bits; p8 is not a Y4M tag).  '420jpeg', '420mpeg2' and '420paldv' are
+    aliases of '420'.  canonical: '420', '422p10', '444p16' ...  ValueError for anything else."""
+    if not isinstance(name, str):
+        raise ValueError(f'a format is a name such as 420, 422p10 or 444p16, got {name!r}')
+    base, sep, bits = _YUV_ALIASES.get(name, name).partition('p')
+    depth = 8
+    if sep:
+        if not (bits.isascii() and bits.isdigit()) or bits != str(int(bits)) or not 9 <= int(bits) <= 16:
+            raise ValueError(f'format {name!r}: the depth suffix is p9 ... p16')
+        depth = int(bits)
+    if base not in YUV_SUBSAMPLINGS:
+        raise ValueError(f'format {name!r}: the subsampling is one of {sorted(YUV_SUBSAMPLINGS)} (mono, 4:1:1, 4:4:0 and alpha are not supported)')
+    sx, sy = YUV_SUBSAMPLINGS[base]
+    return sx, sy, depth, base + (f'p{depth}' if depth > 8 else '')
+
+
+def yuv_frame_size(H, W, fmt='420'):
+    """BYTES of one frame of (H, W) in format `fmt`: the luma plane and two chroma planes of ((H + sy) >> sy, (W + sx) >> sx), one
+    byte per sample at 8 bits and two above."""
+    sx, sy, depth, _ = yuv_format(fmt)
+    return (H * W + 2 * ((H + sy) >> sy) * ((W + sx) >> sx)) * (2 if depth > 8 else 1)
+
+
+def _yuv_fmt_batch(yuv, H, W, fmt, what):
+    if yuv.dim() != 2:
+        raise ValueError(f'{what} is a 2-D uint8 batch (n, >= framesize), got {tuple(yuv.shape)}')
+    if H < 1 or W < 1:
+        raise ValueError(f'a frame has at least one row and column, got {H} x {W}')
+    sx, sy, depth, canonical = yuv_format(fmt)
+    fs = yuv_frame_size(H, W, canonical)
+    if yuv.shape[1] < fs:
+        raise ValueError(f'{what}: rows of {yuv.shape[1]} bytes are shorter than the {fs} bytes of a {H} x {W} {canonical} frame')
+    if yuv.stride(1) != 1:
+        raise ValueError(f'{what}: the bytes of a frame must be contiguous (stride(1) == 1), got stride {yuv.stride(1)}')
+    n = yuv.shape[0]
+    if n < 1:
+        raise ValueError(f'{what}: no frames')
+    if n > 1 and yuv.stride(0) < fs:
+        raise ValueError(f'{what}: frames {yuv.stride(0)} bytes apart overlap')
+    if depth > 8 and (yuv.data_ptr() % 2 or (n > 1 and yuv.stride(0) % 2)):
+        raise ValueError(f'{what}: the 16-bit samples of {canonical} need an even base address and an even row stride, got address '
+                         f'{yuv.data_ptr():#x}, stride {yuv.stride(0)}')
+    return n, fs, (yuv.stride(0) if n > 1 else fs), (sx, sy, depth)
+
+
+def yuv_to_rgb(yuv, H, W, fmt='420', matrix='bt601', range='limited', chroma='bilinear'):
+    """Planar Y'CbCr frames of any Y4M format -> float32 RGB (n, 3, H, W) in [0, 1], in ONE launch.  fmt: `yuv_format` - 4:2:0, 4:2:2 or
+    4:4:4 at 8 ... 16 bits.  yuv: uint8 (n, >= yuv_frame_size(H, W, fmt)) on the GPU with stride(1) == 1 and any row stride and base
+    offset (`buf[:, 6:]` of a Y4MReader buffer works as it is); above 8 bits a sample is a little-endian 16-bit word, whose bits above
+    the depth are NOT masked, and the base address and row stride are even.  matrix, range: `yuv_coeffs` at the format's depth; chroma:
+    'bilinear' (the centre-sited 1/4 - 3/4 filter along each subsampled axis, vertical then horizontal, indices clamped) | 'nearest'.
+    The definition is DESIGN 4.14; at '420' it is that of yuv420_to_rgb, bit for bit.  ValueError for bad names and layouts."""
+    if chroma not in ('bilinear', 'nearest'):
+        raise ValueError(f"chroma must be 'bilinear' or 'nearest', got {chroma!r}")
+    depth = yuv_format(fmt)[2]
+    _, mi, off = yuv_coeffs(matrix, range, depth)
+    require_gpu(yuv, dtypes=(torch.uint8,))
+    H, W = int(H), int(W)
+    n, fs, stride, (sx, sy, depth) = _yuv_fmt_batch(yuv, H, W, fmt, 'yuv')
+    out = torch.empty((n, 3, H, W), dtype=torch.float32, device=yuv.device)
+    coef, bil = _yuv_coef_arg(mi, off), int(chroma == 'bilinear')
+    _run('yuv_to_rgb', lambda: _lib.check(_lib.lib().edvr_yuv_to_rgb_f32(_ptr(yuv), _ptr(out), n, H, W, sx, sy, depth, stride, 3 * H * W, coef, bil,
+                                                                         _stream()), 'edvr_yuv_to_rgb_f32'), 0, float(n) * (fs + 12 * H * W))
+    return out
+
+
+def rgb_to_yuv(rgb, fmt='420', matrix='bt601', range='limited', out=None):
+    """float32 RGB (n, 3, H, W) -> planar Y'CbCr frames of any Y4M format in ONE launch (clamped to [0, 1], x 255, NOT rounded before
+    the matrix: the only quantisation is the one to samples of the format's depth; dense images, a slice of a longer video works).
+    Returns uint8 (n, yuv_frame_size(H, W, fmt)): luma, then Cb and Cr - the mean of a 2 x 2 block (4:2:0) or of a pair of columns
+    (4:2:2), an odd edge replicating, or the sample itself (4:4:4) - clamped to [0, 2^depth - 1] and rounded half to even, a byte or a
+    little-endian 16-bit word each.  out: a uint8 (n, >= framesize) batch to write into instead, stride(1) == 1, any row stride and base
+    offset (even ones above 8 bits; `buf[:, 6:]` of a Y4M write buffer); bytes past a frame's end are left alone and `out` is returned.
+    uint8 RGB stays with rgb_to_yuv420.  The definition is DESIGN 4.14.  ValueError for bad names, layouts and an `out` that overlaps
+    the input."""
+    depth = yuv_format(fmt)[2]
+    m, _, off = yuv_coeffs(matrix, range, depth)
+    require_gpu(rgb)
+    if rgb.dim() != 4 or rgb.shape[1] != 3:
+        raise ValueError(f'float32 frames are (n, 3, H, W), got {tuple(rgb.shape)}')
+    rgb = _as_planes(rgb)
+    n, _, H, W = rgb.shape
+    if out is None:
+        out = torch.empty((n, yuv_frame_size(H, W, fmt)), dtype=torch.uint8, device=rgb.device)
+    else:
+        require_gpu(out, dtypes=(torch.uint8,))
+        if out.dim() == 2 and out.shape[0] != n:
+            raise ValueError(f'out holds {out.shape[0]} frames, the input {n}')
+    n, fs, stride, (sx, sy, depth) = _yuv_fmt_batch(out, H, W, fmt, 'out')
+    (a0, a1), (b0, b1) = _byte_span(rgb), _byte_span(out)
+    if a0 < b1 and b0 < a1:
+        raise ValueError('out overlaps the input')
+    coef = _yuv_coef_arg(m, off)
+    _run('rgb_to_yuv', lambda: _lib.check(_lib.lib().edvr_rgb_to_yuv_f32(_ptr(rgb), _ptr(out), n, H, W, sx, sy, depth, _img_stride(rgb), stride, coef,
+                                                                         _stream()), 'edvr_rgb_to_yuv_f32'), 0, float(n) * (fs + 12 * H * W))
     return out
 
 

@@ -1,20 +1,26 @@
-"""YUV4MPEG2 ("Y4M") in, YUV4MPEG2 out: the container around ops.yuv420_to_rgb / VideoRestorer / ops.rgb_to_yuv420, with no dependency.
+"""YUV4MPEG2 ("Y4M") in, YUV4MPEG2 out: the container around ops.yuv420_to_rgb / VideoRestorer / ops.rgb_to_yuv420 (8-bit 4:2:0) and
+ops.yuv_to_rgb / ops.rgb_to_yuv (4:2:0, 4:2:2 and 4:4:4 at 8 ... 16 bits), with no dependency.
 
     ffmpeg -i in.mp4 -f yuv4mpegpipe - | python scripts/restore_video.py - - --weights ... | ffmpeg -i - out.mp4
 
+(ffmpeg's yuv4mpegpipe muxer writes anything but 8-bit 4:2:0 only with `-strict -1`.)
+
 A Y4M stream is one text line `YUV4MPEG2 W<width> H<height> F<num>:<den> I<interlacing> A<num>:<den> C<chroma> X<comment>...`, then per
 frame a line `FRAME[ parameters]` and the raw planes: for 8-bit 4:2:0 the H W luma bytes, then the (ceil(H / 2), ceil(W / 2)) Cb and Cr
-planes - exactly the batch row ops.yuv420_to_rgb reads.  Everything here works on non-seekable streams (pipes), holds a bounded number
-of frames and uses no threads: pinned host buffers and non_blocking copies keep the device busy while the host reads and writes.
+planes - exactly the batch row ops.yuv420_to_rgb reads; for the other formats the chroma planes are full-size along an
+axis that is not subsampled and a sample above 8 bits is a little-endian 16-bit word - the batch row ops.yuv_to_rgb reads.  Everything
+here works on non-seekable streams (pipes), holds a bounded number of frames and uses no threads: pinned host buffers and non_blocking
+copies keep the device busy while the host reads and writes.
 """
 import torch
 
 from . import ops
-from .ops import yuv420_frame_size
 
 MAGIC = b'YUV4MPEG2'
 FRAME = b'FRAME\n'
 CHROMA_420 = ('420jpeg', '420mpeg2', '420paldv', '420')
+# every format ops.yuv_to_rgb / ops.rgb_to_yuv convert, by its canonical name: '420', '420p9' ... '420p16', '422' ..., '444' ... '444p16'
+ALL_FORMATS = tuple(base + (f'p{d}' if d > 8 else '') for base in ('420', '422', '444') for d in range(8, 17))
 
 
 def default_matrix(H, W):
@@ -32,18 +38,23 @@ def _bytes_of(t):
 
 
 class Y4MReader:
-    """Reads 8-bit 4:2:0 progressive YUV4MPEG2 from a binary stream (a file, a pipe, sys.stdin.buffer, io.BytesIO): nothing seeks.
+    """Reads progressive YUV4MPEG2 from a binary stream (a file, a pipe, sys.stdin.buffer, io.BytesIO): nothing seeks.
+
+    formats: None - 8-bit 4:2:0 only, the format ops.yuv420_to_rgb reads - or a collection of format names (`ops.yuv_format`), such as
+    ALL_FORMATS: 4:2:0, 4:2:2 and 4:4:4 at 8 ... 16 bits, which ops.yuv_to_rgb reads.
 
     Accepted: C420jpeg, C420mpeg2, C420paldv, C420 and no C tag - ALL treated as centre-sited chroma (the 'bilinear' filter of
     ops.yuv420_to_rgb; the left-sited filter of mpeg2 / the co-sited rows of paldv are not implemented, the difference is a quarter-sample
-    chroma shift); Ip, I? and no I tag; XCOLORRANGE=FULL | LIMITED (no tag: limited).  ValueError: a bad magic, a missing or non-positive
-    W / H, interlaced video (It, Ib, Im), C422 / C444 / Cmono / C411 ..., any high-bit-depth format (C420p10, p12, p16 ...), a frame line
-    that is not `FRAME`, and a truncated frame (the message names the frame index).
+    chroma shift); with `formats`, also those of C422, C444 and C420p9 ... C444p16 that it names; Ip, I? and no I tag;
+    XCOLORRANGE=FULL | LIMITED (no tag: limited).  ValueError: a bad magic, a missing or non-positive W / H, interlaced video (It, Ib,
+    Im), a format that `formats` does not name (without it: C422, C444 and every high-bit-depth format), Cmono / C411 / C440 / C444alpha
+    and depths outside 8 ... 16 always, a frame line that is not `FRAME`, and a truncated frame (the message names the frame index).
 
     width, height, fps ('30000:1001' as written, or None), aspect (likewise), range ('limited' | 'full'), chroma (the tag's value or
-    None), framesize; `frames_read` counts what read() returned so far."""
+    None), format (the canonical name: '420', '422p10' ...), depth, subsampling ((sx, sy): log2 of the chroma decimation per axis),
+    framesize (bytes, by the format); `frames_read` counts what read() returned so far."""
 
-    def __init__(self, stream):
+    def __init__(self, stream, formats=None):
         self.stream = stream
         line = stream.readline(1024)
         if not line.startswith(MAGIC + b' ') or not line.endswith(b'\n'):
@@ -73,9 +84,20 @@ class Y4MReader:
             raise ValueError('the YUV4MPEG2 header gives no W / H')
         if interlace not in (None, 'p', '?'):
             raise ValueError(f'interlaced video (I{interlace}) is not supported: deinterlace first')
-        if self.chroma is not None and self.chroma not in CHROMA_420:
-            raise ValueError(f'C{self.chroma} is not supported: 8-bit 4:2:0 only ({", ".join("C" + c for c in CHROMA_420)})')
-        self.framesize = yuv420_frame_size(self.height, self.width)
+        if formats is None:
+            if self.chroma is not None and self.chroma not in CHROMA_420:
+                raise ValueError(f'C{self.chroma} is not supported: 8-bit 4:2:0 only ({", ".join("C" + c for c in CHROMA_420)})')
+            sx, sy, self.depth, self.format = 1, 1, 8, '420'
+        else:
+            accepted = {ops.yuv_format(f)[3] for f in formats}
+            try:
+                sx, sy, self.depth, self.format = ops.yuv_format('420' if self.chroma is None else self.chroma)
+            except ValueError:
+                raise ValueError(f'C{self.chroma} is not supported: 4:2:0, 4:2:2 and 4:4:4 at 8 ... 16 bits are') from None
+            if self.format not in accepted:
+                raise ValueError(f'C{self.chroma} is not among the accepted formats ({", ".join(sorted(accepted))})')
+        self.subsampling = (sx, sy)
+        self.framesize = ops.yuv_frame_size(self.height, self.width, self.format)
         self.frames_read = 0
 
     @staticmethod
@@ -123,20 +145,22 @@ class Y4MReader:
 
 
 class Y4MWriter:
-    """Writes 8-bit 4:2:0 progressive YUV4MPEG2: the header on construction (`Ip`, `C420jpeg`, F / A as given - strings such as
-    '30000:1001', omitted when None - and XCOLORRANGE=FULL for range 'full'), then `write(buf)` for every uint8 host buffer
-    (k, 6 + framesize) whose rows already begin with `FRAME\\n` - the bytes go out as they are, in one write."""
+    """Writes progressive YUV4MPEG2: the header on construction (`Ip`, `C420jpeg` for format '420' and `C<canonical name>` for any
+    other of `ops.yuv_format`, F / A as given - strings such as '30000:1001', omitted when None - and XCOLORRANGE=FULL for range
+    'full'), then `write(buf)` for every uint8 host buffer (k, 6 + framesize) whose rows already begin with `FRAME\\n` - the bytes go
+    out as they are, in one write."""
 
-    def __init__(self, stream, W, H, fps=None, aspect=None, range='limited'):
+    def __init__(self, stream, W, H, fps=None, aspect=None, range='limited', format='420'):
         if range not in ops.YUV_RANGES:
             raise ValueError(f'range must be one of {sorted(ops.YUV_RANGES)}, got {range!r}')
         if int(W) < 1 or int(H) < 1:
             raise ValueError(f'a frame has at least one row and column, got {H} x {W}')
         self.stream, self.width, self.height, self.range = stream, int(W), int(H), range
-        self.framesize = yuv420_frame_size(self.height, self.width)
+        self.format = ops.yuv_format(format)[3]
+        self.framesize = ops.yuv_frame_size(self.height, self.width, self.format)
         self.frames_written = 0
         head = [MAGIC.decode(), f'W{self.width}', f'H{self.height}'] + ([f'F{fps}'] if fps else []) + ['Ip'] + ([f'A{aspect}'] if aspect else [])
-        head += ['C420jpeg'] + (['XCOLORRANGE=FULL'] if range == 'full' else [])
+        head += ['C420jpeg' if self.format == '420' else 'C' + self.format] + (['XCOLORRANGE=FULL'] if range == 'full' else [])
         stream.write((' '.join(head) + '\n').encode('ascii'))
 
     def write(self, buf):
@@ -152,7 +176,8 @@ class Y4MWriter:
         self.frames_written += buf.shape[0]
 
 
-def restore_y4m(net, src, dst, *, matrix_in=None, matrix_out=None, chroma='bilinear', read_frames=8, on_chunk=None, stats=None, **restorer_kwargs):
+def restore_y4m(net, src, dst, *, matrix_in=None, matrix_out=None, chroma='bilinear', read_frames=8, on_chunk=None, stats=None, out_format=None,
+                **restorer_kwargs):
     """Restore a Y4M stream with `net` (an EDVR in eval mode, on the GPU) into a Y4M stream; returns the number of frames.  Call it under
     torch.no_grad().
 
@@ -172,9 +197,16 @@ def restore_y4m(net, src, dst, *, matrix_in=None, matrix_out=None, chroma='bilin
     cuts (a restorer_kwarg, with cut_threshold / min_shot): None | 'auto' | frame indices - windows stay inside a shot (VideoRestorer);
     'auto' scores the decoded float32 RGB, piece by piece as it is read.  The chunks that leave are then short at the end of every shot;
     nothing here depends on their size.  stats: a dict that receives 'frames' and, with cuts, 'cuts', 'cut_scores' and 'cut_mafd' (the
-    restorer's cuts_found / cut_scores / cut_mafd) when the stream has ended."""
+    restorer's cuts_found / cut_scores / cut_mafd) when the stream has ended.
+    Formats: a raw stream is opened with ALL_FORMATS - 4:2:0, 4:2:2 and 4:4:4 at 8 ... 16 bits.  out_format: None writes the
+    input's format, a name of `ops.yuv_format` that one: `out_format='420p10'` (or '444p10') on 8-bit input quantises the network's
+    float32 result once, to 10 bits, instead of banding it at 8.  8-bit 4:2:0 in and out goes through ops.yuv420_to_rgb / rgb_to_yuv420
+    as above, everything else through ops.yuv_to_rgb(buf[:, 6:], H, W, format, ...) / ops.rgb_to_yuv(chunk, format, ..., out=buf[:, 6:])."""
     from .video import VideoRestorer
-    reader = src if isinstance(src, Y4MReader) else Y4MReader(src)
+    reader = src if isinstance(src, Y4MReader) else Y4MReader(src, formats=ALL_FORMATS)
+    fmt_in = reader.format
+    fmt_out = fmt_in if out_format is None else ops.yuv_format(out_format)[3]
+    plain420 = fmt_in == '420' and fmt_out == '420'  # the 8-bit 4:2:0 kernels of csrc/yuv.hip on both sides
     if int(read_frames) < 1:
         raise ValueError(f'read_frames must be at least 1, got {read_frames}')
     for name in (matrix_in, matrix_out):
@@ -188,7 +220,7 @@ def restore_y4m(net, src, dst, *, matrix_in=None, matrix_out=None, chroma='bilin
     Ho, Wo = vr.scale * H, vr.scale * W
     matrix_in = matrix_in or default_matrix(H, W)
     matrix_out = matrix_out or default_matrix(Ho, Wo)
-    writer = Y4MWriter(dst, Wo, Ho, reader.fps, reader.aspect, reader.range)
+    writer = Y4MWriter(dst, Wo, Ho, reader.fps, reader.aspect, reader.range, fmt_out)
     row = len(FRAME) + writer.framesize
     marks = torch.tensor(list(FRAME), dtype=torch.uint8).to(device)
 
@@ -197,7 +229,11 @@ def restore_y4m(net, src, dst, *, matrix_in=None, matrix_out=None, chroma='bilin
             host = reader.read(read_frames)
             if host.shape[0] == 0:
                 return
-            yield ops.yuv420_to_rgb(host.to(device, non_blocking=True)[:, len(FRAME):], H, W, matrix_in, reader.range, chroma)
+            yuv = host.to(device, non_blocking=True)[:, len(FRAME):]
+            if plain420:
+                yield ops.yuv420_to_rgb(yuv, H, W, matrix_in, reader.range, chroma)
+            else:
+                yield ops.yuv_to_rgb(yuv, H, W, fmt_in, matrix_in, reader.range, chroma)
 
     pending = None  # (pinned buffer, event after its copy) of the chunk before this one
 
@@ -212,7 +248,10 @@ def restore_y4m(net, src, dst, *, matrix_in=None, matrix_out=None, chroma='bilin
         buf[:, :len(FRAME)] = marks
         if on_chunk is not None:
             on_chunk(out)
-        ops.rgb_to_yuv420(out, matrix_out, reader.range, out=buf[:, len(FRAME):])
+        if plain420:
+            ops.rgb_to_yuv420(out, matrix_out, reader.range, out=buf[:, len(FRAME):])
+        else:
+            ops.rgb_to_yuv(out, fmt_out, matrix_out, reader.range, out=buf[:, len(FRAME):])
         host = _host_buffer(tuple(buf.shape))
         host.copy_(buf, non_blocking=True)
         done = None

@@ -711,6 +711,23 @@ int edvr_rgb_to_yuv420_f32(const float *rgb, uint8_t *yuv, int n, int H, int W, 
                            edvr_stream_t stream);
 int edvr_rgb_to_yuv420_u8(const uint8_t *rgb, uint8_t *yuv, int n, int H, int W, int64_t yuv_stride, const float *coef, edvr_stream_t stream);
 
+/* Planar Y'CbCr of any Y4M format <-> float32 RGB (csrc/yuv_formats.hip; definition: DESIGN 4.14).  A format is a chroma subsampling
+ * (sub_x, sub_y) - (1, 1) 4:2:0, (1, 0) 4:2:2, (0, 0) 4:4:4 - and a bit depth 8 ... 16.  A frame of (H, W) is the dense planes Y (H, W),
+ * Cb, Cr (Hc, Wc) = ((H + sub_y) >> sub_y, (W + sub_x) >> sub_x); a sample is one byte at depth 8, otherwise one little-endian 16-bit
+ * word (bits above the depth are NOT masked by the decode).  A batch is n frames yuv_stride >= framesize BYTES apart; with 16-bit samples
+ * the base address and yuv_stride are even.  coef: as above, the offsets (yoff, coff, coff) and the matrix scaled for the depth by the
+ * caller (ops.yuv_coeffs(matrix, range, depth)).  The arithmetic is that of the 8-bit 4:2:0 pair, operation by operation; the chroma
+ * filter of the decode runs along a subsampled axis only, the chroma sample of the encode is the mean of its 2 x 2 block (4:2:0), of its
+ * pair of columns (4:2:2: (p[2l] + p[2l + 1]) * 0.5f) or p itself (4:4:4); every sample is clamped to [0, 2^depth - 1] and rounded half
+ * to even.  rgb: float32 (n, 3, H, W), dense images rgb_img_stride floats apart.  Bytes between the frames of an output batch are not
+ * written.  16-byte accesses on a side whose base and strides are 16-byte aligned where W % 16 == 0, scalar ones otherwise; same values.
+ * EDVR_ERR_ARG: null pointers, n, H or W < 1, depth outside 8 ... 16, a subsampling other than the three, yuv_stride < framesize or
+ * rgb_img_stride < 3 H W with n > 1, an odd base or stride with 16-bit samples, H W > 2^29.  No allocation, no wait. */
+int edvr_yuv_to_rgb_f32(const uint8_t *yuv, float *rgb, int n, int H, int W, int sub_x, int sub_y, int depth, int64_t yuv_stride,
+                        int64_t rgb_img_stride, const float *coef, int bilinear, edvr_stream_t stream);
+int edvr_rgb_to_yuv_f32(const float *rgb, uint8_t *yuv, int n, int H, int W, int sub_x, int sub_y, int depth, int64_t rgb_img_stride,
+                        int64_t yuv_stride, const float *coef, edvr_stream_t stream);
+
 /* Frame-to-frame change for scene-cut detection (csrc/shots.hip; definition: DESIGN 4.13).  The bytes R, G, B of a pixel are the input's
  * own (_u8: x (n, H, W, 3)) or its tensor2img bytes (_f32: x (n, 3, H, W); clamp to [0, 1], x 255, round half to even, NaN -> 0); in
  * integers Y8 = ((66 R + 129 G + 25 B + 128) >> 8) + 16, and

@@ -10,7 +10,13 @@
       ending in a synchronise, against VideoRestorer.restore on resident float32 frames - the parent's path - alternated, three runs each, so
       that the spread of the resident arm is known before the difference is read.
 
+  (d) with --formats, INSTEAD of (a) - (c): ops.yuv_to_rgb (bilinear chroma) and ops.rgb_to_yuv (csrc/yuv_formats.hip) for '420p10', '422p10',
+      '444p10' and, through the same kernels, '420', on 8 frames of 720 x 1280 and one of 2160 x 3840 in a dense 16-byte-aligned batch, timed as
+      (a); beside them, in the same process and at the same shapes, ops.yuv420_to_rgb / ops.rgb_to_yuv420 - the 8-bit 4:2:0 kernels of
+      csrc/yuv.hip, which this leg leaves as they were: the comparison arm.  Written to profiles/yuv/bench_yuv_formats.json.
+
     python scripts/bench_yuv.py [--out profiles/yuv/bench_yuv.json] [--skip-video]
+    python scripts/bench_yuv.py --formats [--out profiles/yuv/bench_yuv_formats.json]
 """
 import argparse
 import io
@@ -122,6 +128,46 @@ def kernel_rows(args, dev):
     return rows
 
 
+FORMAT_CASES = [('8x720x1280', 8, (720, 1280)), ('1x2160x3840', 1, (2160, 3840))]
+FORMATS = ['420p10', '422p10', '444p10', '420']
+
+
+def format_rows(args, dev):
+    """Leg (d): one row per shape and format through csrc/yuv_formats.hip, and one per shape through the 8-bit 4:2:0 kernels of csrc/yuv.hip."""
+    from edvr_amd import ops
+    rows = []
+
+    def measure(row, arms, nbytes):
+        for arm, fn in arms.items():
+            first, second = timed(fn, args.warmup, args.iters), timed(fn, 5, args.iters)  # twice: the first ran on a colder device
+            med = min(first[0], second[0])
+            row[arm + '_us'] = round(med, 2)
+            row[arm + '_us_runs'] = [round(first[0], 2), round(second[0], 2)]
+            row[arm + '_us_min_max'] = [round(min(first[1], second[1]), 2), round(max(first[2], second[2]), 2)]
+            row[arm + '_hbm_fraction'] = round(nbytes / (med * 1e-6) / (HBM_TBS * 1e12), 4)
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+
+    for name, n, (H, W) in FORMAT_CASES:
+        gen = torch.Generator().manual_seed(0)
+        rgb = torch.rand((n, 3, H, W), generator=gen).to(dev)
+        frames8 = ops.rgb_to_yuv420(rgb, 'bt709', 'limited')
+        fs8 = ops.yuv420_frame_size(H, W)
+        measure(dict(case=name, frames=n, size=[H, W], kernels='yuv.hip', format='420', bytes_moved=n * (fs8 + 12 * H * W)),
+                {'decode': lambda: ops.yuv420_to_rgb(frames8, H, W, 'bt709', 'limited'),
+                 'encode': lambda: ops.rgb_to_yuv420(rgb, 'bt709', 'limited', out=frames8)}, n * (fs8 + 12 * H * W))
+        for fmt in FORMATS:
+            fs = ops.yuv_frame_size(H, W, fmt)
+            frames = ops.rgb_to_yuv(rgb, fmt, 'bt709', 'limited')
+            if fmt == '420':
+                assert torch.equal(frames, frames8) and torch.equal(ops.yuv_to_rgb(frames, H, W, fmt, 'bt709', 'limited'),
+                                                                    ops.yuv420_to_rgb(frames8, H, W, 'bt709', 'limited'))
+            measure(dict(case=name, frames=n, size=[H, W], kernels='yuv_formats.hip', format=fmt, bytes_moved=n * (fs + 12 * H * W)),
+                    {'decode': lambda: ops.yuv_to_rgb(frames, H, W, fmt, 'bt709', 'limited'),
+                     'encode': lambda: ops.rgb_to_yuv(rgb, fmt, 'bt709', 'limited', out=frames)}, n * (fs + 12 * H * W))
+    return rows
+
+
 def video_row(args, dev):
     """restore_y4m against VideoRestorer.restore on resident frames: 100 frames of 180 x 320, EDVR-L, chunk 10."""
     from edvr_amd import EDVR, VideoRestorer, ops
@@ -171,21 +217,29 @@ def video_row(args, dev):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument('--out', default=os.path.join(os.path.dirname(os.path.abspath(__file__)), '..', 'profiles', 'yuv', 'bench_yuv.json'))
+    ap.add_argument('--out', default=None, help='default: profiles/yuv/bench_yuv.json, with --formats profiles/yuv/bench_yuv_formats.json')
+    ap.add_argument('--formats', action='store_true', help='leg (d) alone: the format-aware kernels beside the 8-bit 4:2:0 kernels')
     ap.add_argument('--warmup', type=int, default=20)
     ap.add_argument('--iters', type=int, default=200)
     ap.add_argument('--video-frames', type=int, default=100)
     ap.add_argument('--skip-video', action='store_true', help='kernels only')
     ap.add_argument('--head', default=None, help='commit to record where the tree is not a git checkout (default: git rev-parse HEAD)')
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(os.path.dirname(os.path.abspath(__file__)), '..', 'profiles', 'yuv',
+                                'bench_yuv_formats.json' if args.formats else 'bench_yuv.json')
     assert args.iters >= 20, 'the median of at least 20 calls'
     assert torch.cuda.is_available(), 'bench_yuv needs the GPU: there is no CPU path to time'
     from edvr_amd import _lib
     from edvr_amd.build import source_hash
     dev = torch.device('cuda:0')
     record = dict(bench='bench_yuv', lib=_lib.lib().edvr_version().decode(), source_hash=source_hash(), git_head=args.head or git_head(),
-                  device=torch.cuda.get_device_name(0), hbm_tbs=HBM_TBS, warmup=args.warmup, iters=args.iters, kernels=kernel_rows(args, dev))
-    if not args.skip_video:
+                  device=torch.cuda.get_device_name(0), hbm_tbs=HBM_TBS, warmup=args.warmup, iters=args.iters)
+    if args.formats:
+        record['bench'], record['formats'] = 'bench_yuv_formats', format_rows(args, dev)
+    else:
+        record['kernels'] = kernel_rows(args, dev)
+    if not args.skip_video and not args.formats:
         record['restore_y4m'] = video_row(args, dev)
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, 'w') as f:

@@ -1,11 +1,19 @@
-"""Restore a video that has no ground truth: YUV4MPEG2 (8-bit 4:2:0) in, YUV4MPEG2 out, `-` for stdin / stdout.
+"""Restore a video that has no ground truth: YUV4MPEG2 in, YUV4MPEG2 out, `-` for stdin / stdout.
 
     ffmpeg -i in.mp4 -f yuv4mpegpipe - | python scripts/restore_video.py - - --weights EDVR_L_x4_SR_REDS_official.pth | ffmpeg -i - out.mp4
     python scripts/restore_video.py in.y4m out.y4m --weights ... --pad-mode reflect --tile 256 256 --self-ensemble flip4
+    ffmpeg -i hevc10.mp4 -strict -1 -f yuv4mpegpipe - | python scripts/restore_video.py - - --weights ... | ffmpeg -i - out.mkv
+    ffmpeg -i in.mp4 -f yuv4mpegpipe - | python scripts/restore_video.py - - --weights ... --out-format 420p10 | ffmpeg -i - out.mkv
 
-edvr_amd.y4m.restore_y4m: the frames go to the device as the decoder wrote them, are converted to RGB there (edvr_amd.ops.yuv420_to_rgb),
-restored by VideoRestorer with every frame's features extracted once, converted back (ops.rgb_to_yuv420) and written as they arrive -
-bounded memory, no intermediate files, one quantisation.  The network options are those of scripts/eval_video.py, `--batch` is the
+The input is 4:2:0, 4:2:2 or 4:4:4 at 8 ... 16 bits (C420jpeg, C422p10, C444p12 ...: 10-bit phone and camera footage, 4:2:2 intermediates
+and 4:4:4 screen captures go in as they are - ffmpeg's yuv4mpegpipe muxer writes anything but 8-bit 4:2:0 only with `-strict -1`, and
+no `-pix_fmt yuv420p` in front of the pipe throws bits or chroma away).  `--out-format NAME` picks the output's format (default: the
+input's): `420p10` or `444p10` on 8-bit input quantises the network's float32 result once, to 10 bits, which keeps skies and gradients
+free of the banding that 8 bits add.
+
+edvr_amd.y4m.restore_y4m: the frames go to the device as the decoder wrote them, are converted to RGB there (edvr_amd.ops.yuv420_to_rgb;
+ops.yuv_to_rgb for every other format), restored by VideoRestorer with every frame's features extracted once, converted back
+(ops.rgb_to_yuv420 / ops.rgb_to_yuv) and written as they arrive - bounded memory, no intermediate files, one quantisation.  The network options are those of scripts/eval_video.py, `--batch` is the
 number of output frames per pass; `--matrix-in` / `--matrix-out` default to the player rule for each side's own size (BT.709 from 1280
 columns or 577 rows, BT.601 below), `--chroma` picks the chroma upsampling filter of the decode.  `--niqe PARAMS.npz` scores the result with
 the no-reference NIQE (metrics.calculate_niqe against BasicSR's niqe_pris_params.npz; lower is better) on the float32 frames before they
@@ -32,7 +40,7 @@ def restore(args, log=log):
     from edvr_amd import EDVR
     from edvr_amd.optim import load_network
     from edvr_amd import metrics, ops
-    from edvr_amd.y4m import FRAME, Y4MReader, default_matrix, restore_y4m
+    from edvr_amd.y4m import ALL_FORMATS, FRAME, Y4MReader, default_matrix, restore_y4m
     device = torch.device('cuda', int(os.environ.get('LOCAL_RANK', 0)))
     torch.cuda.set_device(device)
     net = EDVR(num_in_ch=3, num_out_ch=3, num_feat=args.num_feat, num_frame=args.num_frame, deformable_groups=8,
@@ -49,7 +57,7 @@ def restore(args, log=log):
     src = sys.stdin.buffer if args.input == '-' else open(args.input, 'rb')
     dst = sys.stdout.buffer if args.output == '-' else open(args.output, 'wb')
     try:
-        reader = Y4MReader(src)
+        reader = Y4MReader(src, formats=ALL_FORMATS)
         log(f'{args.input}: {reader.width} x {reader.height}, F{reader.fps}, C{reader.chroma}, {reader.range} range')
         niqe_path, niqe_out, niqe_in = getattr(args, 'niqe', None), [], []
         if niqe_path:
@@ -62,7 +70,8 @@ def restore(args, log=log):
                 def scored_read(k):  # the input as restore_y4m decodes it, scored at its own size
                     host = read(k)
                     if host.shape[0]:
-                        rgb = ops.yuv420_to_rgb(host.to(device, non_blocking=True)[:, len(FRAME):], H, W, matrix_in, reader.range, args.chroma)
+                        rgb = ops.yuv_to_rgb(host.to(device, non_blocking=True)[:, len(FRAME):], H, W, reader.format, matrix_in, reader.range,
+                                             args.chroma)
                         niqe_in.extend(metrics.calculate_niqe(rgb, params=params))
                     return host
 
@@ -71,7 +80,7 @@ def restore(args, log=log):
         with torch.no_grad():
             n = restore_y4m(net, reader, dst, matrix_in=args.matrix_in, matrix_out=args.matrix_out, chroma=args.chroma,
                             read_frames=args.read_frames, num_frame=args.num_frame, padding=args.padding, chunk=args.batch, stats=stats,
-                            **kwargs)
+                            out_format=getattr(args, 'out_format', None), **kwargs)
         net.check_offsets()
         torch.cuda.synchronize()
         dt = time.time() - t0
@@ -132,7 +141,7 @@ def report_niqe(args, niqe_out, niqe_in, log=log):
 
 
 def parse_args(argv=None):
-    ap = argparse.ArgumentParser(description='Restore a YUV4MPEG2 video with EDVR (8-bit 4:2:0 in and out).')
+    ap = argparse.ArgumentParser(description='Restore a YUV4MPEG2 video with EDVR (4:2:0, 4:2:2 or 4:4:4 at 8 ... 16 bits in and out).')
     ap.add_argument('input', metavar='IN', help='Y4M file, or - for stdin')
     ap.add_argument('output', metavar='OUT', help='Y4M file, or - for stdout')
     ap.add_argument('--weights', default=None)
@@ -157,6 +166,8 @@ def parse_args(argv=None):
     ap.add_argument('--matrix-in', default=None, choices=['bt601', 'bt709'], help="the input's matrix (default: by its size)")
     ap.add_argument('--matrix-out', default=None, choices=['bt601', 'bt709'], help="the output's matrix (default: by ITS size)")
     ap.add_argument('--chroma', default='bilinear', choices=['bilinear', 'nearest'], help='chroma upsampling of the decode')
+    ap.add_argument('--out-format', default=None, metavar='NAME',
+                    help="the output's format: 420 | 422 | 444 with an optional depth p9 ... p16, e.g. 420p10 (default: the input's)")
     ap.add_argument('--niqe', default=None, metavar='PARAMS.npz',
                     help="score the output (and the input, where two 96 x 96 blocks fit) with NIQE; PARAMS.npz is BasicSR's niqe_pris_params.npz")
     ap.add_argument('--niqe-json', default=None, metavar='FILE', help='with --niqe: write the per-frame and mean NIQE there')
@@ -169,6 +180,12 @@ def parse_args(argv=None):
     ap.add_argument('--cuts-json', default=None, metavar='FILE',
                     help='with --scene-cuts or --cuts: write the cuts, every frame\'s mafd and score, the threshold and min_shot there')
     args = ap.parse_args(argv)
+    if args.out_format is not None:
+        from edvr_amd.ops import yuv_format
+        try:
+            args.out_format = yuv_format(args.out_format)[3]
+        except ValueError as e:
+            ap.error(f'--out-format: {e}')
     if args.cuts is not None and args.scene_cuts is not None:
         ap.error('--cuts and --scene-cuts exclude each other')
     if args.min_shot is not None and args.scene_cuts is None:
