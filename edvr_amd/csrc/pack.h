@@ -158,7 +158,9 @@ __device__ __forceinline__ void pack_f4s_elem(const float *__restrict__ w, unsig
     G6(tmp[r][0], tmp[r][1], tmp[r][2], u);
     unsigned *blk = U + 16 + (blk0 + 2 * r) * (6 * 256) + ln * 4 + (c & 3);
 #pragma unroll
-    for (int cc = 0; cc < 6; ++cc) blk[cc * 256] = split_f16x2(u[cc], s_u);
+    // a zero element - all of the padding - is the dword 0, as in the other split layouts: G of zeros has -0 entries, which would split
+    // into (+0, -0) = 0x80000000
+    for (int cc = 0; cc < 6; ++cc) blk[cc * 256] = u[cc] != 0.f ? split_f16x2(u[cc], s_u) : 0u;
   }
 }
 

@@ -35,8 +35,10 @@ __device__ __forceinline__ int job_of_block(const PackJob *__restrict__ jobs, in
 
 // max |w| of every job that has a split-operand layout, into header slot 2 + parity of its buffer (atomics on the bit pattern).  The
 // packing kernel of the same call reads that slot and zeroes the OTHER one, which the next call (parity flipped) accumulates into:
-// no memset launch; a buffer that skips calls may find an old maximum in its slot - still a bound of the weights' magnitude only
-// if it is >= the current one, which atomicMax guarantees.
+// no memset launch in the steady state.  A buffer that skips calls may come back on the parity of its own last call, to a slot nobody
+// zeroed: atomicMax would keep that call's maximum - still a bound, but one that costs the scale its precision once the weights have
+// shrunk, and an infinite one (a weight that was inf then) scales every finite weight to zero.  So the caller zeroes slots [2], [3] of a
+// buffer that did not take part in the call directly before (ops.prepack_conv_weights).
 __global__ __launch_bounds__(256) void weights_amax_multi_kernel(const PackJob *__restrict__ jobs, int n_jobs, int parity) {
   const PackJob jb = jobs[job_of_block(jobs, n_jobs)];
   if (!jb.wpk_f4s || jb.ks != 3) return;

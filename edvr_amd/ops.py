@@ -89,7 +89,7 @@ def workspace(nbytes, device, tag=None):
 
 
 # ------------------------------------------------------------------------------------------------ weights
-_PACKED = {}  # id(parameter) -> (weakref, {transpose_flip: (version, packed, data_ptr)})
+_PACKED = {}  # id(parameter) -> (weakref, {(transpose_flip, layout): (version, packed, data_ptr[, _PACK_CALLS of the multi launch that filled it])})
 
 
 def pack_conv_weight(weight, transpose_flip=False, f4=False, f4s=False, ci_range=None, ds=False):
@@ -199,6 +199,7 @@ def prepack_conv_weights(weights, meta=None):
     work queued on another stream that still reads a packed layout must be synchronised with by the caller (single-stream
     assumption of the training loop; GraphedEDVR pins its layouts instead)."""
     import numpy as np
+    global _PACK_CALLS
     L = _lib.lib()
     jobs, sig, filled = [], [], []
     meta = list(meta) if meta is not None else None
@@ -228,6 +229,11 @@ def prepack_conv_weights(weights, meta=None):
                     n, dt = (L.edvr_conv2d_packed_weight_f4_elems(co, ci) if f4 else L.edvr_conv2d_packed_weight_elems(co, ci, k)), torch.float32
                 if hit is not None and hit[1].numel() == n and hit[1].dtype == dt and hit[1].device == w.device and _sole_owner(hit):
                     buf = hit[1]
+                    if f4 == 2 and len(hit) > 3 and hit[3] != _PACK_CALLS:
+                        # it sat out the last call(s): nobody zeroed the max |w| slot this call accumulates into, and after an odd number
+                        # of them that is the slot of its own last call - an old, larger maximum would cost precision, an infinite one
+                        # would scale every weight to zero.  (One tiny launch, only on this rare path.)
+                        buf[2:4].zero_()
                 else:
                     buf = torch.empty(n, dtype=dt, device=w.device)
                     if f4 == 2:
@@ -260,12 +266,11 @@ def prepack_conv_weights(weights, meta=None):
         if len(_PACK_TABLES) > 8:
             _PACK_TABLES.clear()
         _PACK_TABLES[key] = tab
-    global _PACK_CALLS
     _PACK_CALLS += 1
     parity = _PACK_CALLS if any(j[8] for j in jobs) else -1
     _lib.check(L.edvr_conv2d_pack_weights_multi(_ptr(tab[0]), len(jobs), tab[1], parity, _stream()), 'edvr_conv2d_pack_weights_multi')
     for ent, k2, ver, buf, ptr in filled:
-        ent[1][k2] = (ver, buf, ptr)
+        ent[1][k2] = (ver, buf, ptr, _PACK_CALLS)  # (the call it took part in: the header slots of a split layout alternate per call)
     return len(jobs)
 
 

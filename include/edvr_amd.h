@@ -211,7 +211,9 @@ int edvr_amax_f32(const float *x, float *amax, int n, int64_t per_img, int64_t i
  * its FIRST use here), transpose_flip as above; job j owns the workgroups [first_block, first_block +
  * n_blocks) of the launch (ascending, contiguous from 0; any n_blocks >= 1 - 256 elements per workgroup and pass), total_blocks =
  * their sum.  Results are bit-identical to the per-tensor functions.  split_parity: -1 when no job has a wpk_f4s; else a counter the
- * caller increments per call (its low bit selects which header slot collects max |w| this time: one extra launch, no memset). */
+ * caller increments per call (its low bit selects which header slot collects max |w| this time: one extra launch, no memset -
+ * each call zeroes the other slot for the next one, so a buffer that was NOT part of the call directly before needs its header
+ * dwords 2 and 3 zeroed by the caller). */
 size_t edvr_pack_job_bytes(void);
 int edvr_conv2d_pack_weights_multi(const void *jobs, int n_jobs, int total_blocks, int split_parity, edvr_stream_t stream);
 int edvr_conv2d_f32(const edvr_conv2d_desc *d, edvr_stream_t stream);

@@ -114,28 +114,57 @@ def test_transpose_flip_pack_is_data_gradient(gpu):
 
 
 def test_multi_tensor_packing_is_bit_identical(gpu):
+    for f4s_training in (True, False):
+        _multi_tensor_packing_is_bit_identical(gpu, f4s_training)
+
+
+def _multi_tensor_packing_is_bit_identical(gpu, f4s_training):
     """ops.prepack_conv_weights (one edvr_conv2d_pack_weights_multi launch for a whole network's weights, the training path)
     against the per-tensor packing functions: every layout, both orientations, 1x1 / 3x3, channel counts that need padding -
-    and the cache bookkeeping (nothing to do on a second call, only the touched weight after an in-place update)."""
+    and the cache bookkeeping (nothing to do on a second call, only the touched weight after an in-place update).  Of the two
+    F(4x4) layouts the launch fills the one the setting asks for - the split one (cache slot 2) under set_f4s(training=True), the
+    fp32 one (slot True) otherwise - so both settings run, and the buffers are read from the cache itself."""
     from edvr_amd import ops
     g = torch.Generator().manual_seed(77)
     shapes = [(128, 128, 3), (64, 3, 3), (3, 64, 3), (216, 128, 3), (70, 20, 3), (64, 640, 1), (48, 96, 1), (128, 256, 3)]
     ws = [torch.nn.Parameter((torch.randn(co, ci, k, k, generator=g) * 0.1).to(gpu)) for co, ci, k in shapes]
+    f4_kind = 2 if f4s_training else True
     want = {}
     for i, w in enumerate(ws):
         for flip in (False, True):
             want[(i, flip, False)] = ops.pack_conv_weight(w, transpose_flip=flip).clone()
-            f4 = ops.f4_weight(w, w.shape[2], transpose_flip=flip)
-            if f4 is not None:
-                want[(i, flip, True)] = f4.clone()
-    ops.invalidate_packed_weights()
-    n_jobs = ops.prepack_conv_weights(ws)
-    assert n_jobs == 2 * len(ws)
-    for (i, flip, f4), ref in want.items():
-        got = ops.pack_conv_weight(ws[i], transpose_flip=flip, f4=f4)  # a cache hit now: the buffer the multi launch filled
-        assert torch.equal(got, ref), (shapes[i], flip, f4)
-    assert ops.prepack_conv_weights(ws) == 0
-    with torch.no_grad():
-        ws[3].mul_(2.0)  # in-place update: the version moves, as after an optimizer step
-    assert ops.prepack_conv_weights(ws) == 2
-    assert torch.equal(ops.pack_conv_weight(ws[3], f4=True), 2.0 * want[(3, False, True)])
+            if ops.f4_weight(w, w.shape[2], transpose_flip=flip) is not None:
+                want[(i, flip, f4_kind)] = ops.pack_conv_weight(w, transpose_flip=flip, f4=not f4s_training, f4s=f4s_training).clone()
+    assert sum(1 for k in want if k[2] is not False) == 6
+    f4_of_3 = ops.pack_conv_weight(ws[3], f4=True).clone()
+
+    def filled(i, flip, kind):
+        # the buffer the multi launch filled, from the cache: pack_conv_weight would pack a missing layout itself, with the per-tensor
+        # packer, and the comparison would be of that packer with itself
+        return ops._PACKED[id(ws[i])][1][(flip, kind)][1]
+
+    def same(got, ref, kind):
+        if kind == 2:  # dwords 2..15 of the split layout's header are the multi launch's own (max |w| of the call, by parity)
+            return got.dtype == ref.dtype and torch.equal(got[:2], ref[:2]) and torch.equal(got[16:], ref[16:])
+        return got.dtype == ref.dtype and torch.equal(got, ref)
+
+    prev = ops.set_f4s(training=f4s_training)
+    try:
+        ops.invalidate_packed_weights()
+        n_jobs = ops.prepack_conv_weights(ws)
+        assert n_jobs == 2 * len(ws)
+        assert {(i, flip, kind) for i, w in enumerate(ws) for (flip, kind) in ops._PACKED[id(w)][1]} == set(want)
+        for (i, flip, kind), ref in want.items():
+            assert same(filled(i, flip, kind), ref, kind), (shapes[i], flip, kind)
+        assert ops.prepack_conv_weights(ws) == 0
+        with torch.no_grad():
+            ws[3].mul_(2.0)  # in-place update: the version moves, as after an optimizer step
+        assert ops.prepack_conv_weights(ws) == 2
+        assert torch.equal(ops.pack_conv_weight(ws[3], f4=True), 2.0 * f4_of_3)  # (a cache hit only with the split form off)
+        got, ref = filled(3, False, f4_kind), want[(3, False, f4_kind)]
+        if f4s_training:  # twice the weights: half the scale, the same dwords
+            assert got[0].item() == ref[0].item() - (1 << 23) and got[1].item() == ref[1].item() + (1 << 23) and torch.equal(got[16:], ref[16:])
+        else:
+            assert torch.equal(got, 2.0 * ref)
+    finally:
+        ops.set_f4s(training=prev[1])
