@@ -1876,14 +1876,45 @@ def lq_crops_from_windows(windows, table, scale, degradation, table_host=None):
     return out
 
 
-# ------------------------------------------------------------------------------------------------ Y'CbCr 4:2:0 <-> RGB (csrc/yuv.hip)
+# ------------------------------------------------------------------------------------------------ planar Y'CbCr <-> RGB (csrc/yuv.hip)
 YUV_MATRICES = {'bt601': (0.299, 0.114), 'bt709': (0.2126, 0.0722)}              # (Kr, Kb)
 YUV_RANGES = {'limited': (219.0, 224.0, 16.0), 'full': (255.0, 255.0, 0.0)}     # luma scale, chroma scale, luma offset (chroma offset 128)
+YUV_SUBSAMPLINGS = {'420': (1, 1), '422': (1, 0), '444': (0, 0)}                    # (sx, sy): log2 of the chroma decimation per axis
+_YUV_ALIASES = {'420jpeg': '420', '420mpeg2': '420', '420paldv': '420'}
+
+
+def yuv_format(name):
+    """A Y4M format name -> (sx, sy, depth, canonical): '420' | '422' | '444' (chroma planes ((H + sy) >> sy, (W + sx) >> sx)) with an
+    optional suffix p9 ... p16 for the bit depth (none: 8 bits; p8 is not a Y4M tag).  '420jpeg', '420mpeg2' and '420paldv' are
+    aliases of '420'.  canonical: '420', '422p10', '444p16' ...  ValueError for anything else (DESIGN 4.14)."""
+    if not isinstance(name, str):
+        raise ValueError(f'a format is a name such as 420, 422p10 or 444p16, got {name!r}')
+    base, sep, bits = _YUV_ALIASES.get(name, name).partition('p')
+    depth = 8
+    if sep:
+        if not (bits.isascii() and bits.isdigit()) or bits != str(int(bits)) or not 9 <= int(bits) <= 16:
+            raise ValueError(f'format {name!r}: the depth suffix is p9 ... p16')
+        depth = int(bits)
+    if base not in YUV_SUBSAMPLINGS:
+        raise ValueError(f'format {name!r}: the subsampling is one of {sorted(YUV_SUBSAMPLINGS)} (mono, 4:1:1, 4:4:0 and alpha are not supported)')
+    sx, sy = YUV_SUBSAMPLINGS[base]
+    return sx, sy, depth, base + (f'p{depth}' if depth > 8 else '')
+
+
+def yuv_frame_size(H, W, fmt='420'):
+    """BYTES of one frame of (H, W) in format `fmt`: the luma plane and two chroma planes of ((H + sy) >> sy, (W + sx) >> sx), one
+    byte per sample at 8 bits and two above."""
+    sx, sy, depth, _ = yuv_format(fmt)
+    return _yuv_frame_bytes(H, W, sx, sy, depth)
+
+
+def _yuv_frame_bytes(H, W, sx, sy, depth):
+    return (H * W + 2 * ((H + sy) >> sy) * ((W + sx) >> sx)) * (2 if depth > 8 else 1)
 
 
 def yuv420_frame_size(H, W):
     """Bytes of one I420 frame of (H, W): the luma plane and two chroma planes of (ceil(H / 2), ceil(W / 2))."""
-    return H * W + 2 * ((H + 1) // 2) * ((W + 1) // 2)
+    return yuv_frame_size(H, W, '420')
 
 
 def yuv_coeffs(matrix='bt601', range='limited', depth=8):
@@ -1917,139 +1948,14 @@ def _yuv_coef_arg(mat, off):
     return (ctypes.c_float * 12)(*[v for row in mat for v in row], *off)
 
 
-def _yuv_batch(yuv, H, W, what):
+def _yuv_batch(yuv, H, W, fmt, what):
+    """Checks a (n, >= framesize) byte batch of frames, fmt = yuv_format(name) -> (n, framesize, bytes between frames)."""
     if yuv.dim() != 2:
         raise ValueError(f'{what} is a 2-D uint8 batch (n, >= framesize), got {tuple(yuv.shape)}')
     if H < 1 or W < 1:
         raise ValueError(f'a frame has at least one row and column, got {H} x {W}')
-    fs = yuv420_frame_size(H, W)
-    if yuv.shape[1] < fs:
-        raise ValueError(f'{what}: rows of {yuv.shape[1]} bytes are shorter than the {fs} bytes of a {H} x {W} I420 frame')
-    if yuv.stride(1) != 1:
-        raise ValueError(f'{what}: the bytes of a frame must be contiguous (stride(1) == 1), got stride {yuv.stride(1)}')
-    n = yuv.shape[0]
-    if n < 1:
-        raise ValueError(f'{what}: no frames')
-    if n > 1 and yuv.stride(0) < fs:
-        raise ValueError(f'{what}: frames {yuv.stride(0)} bytes apart overlap')
-    return n, fs, (yuv.stride(0) if n > 1 else fs)
-
-
-def yuv420_to_rgb(yuv, H, W, matrix='bt601', range='limited', chroma='bilinear', out_dtype=torch.float32):
-    """8-bit I420 frames -> RGB in ONE launch.  yuv: uint8 (n, >= framesize) on the GPU with stride(1) == 1 and ANY row stride and base
-    offset - each row starts with the H W luma bytes, then the (ceil(H / 2), ceil(W / 2)) Cb and Cr planes, i.e. the payload of a Y4M
-    frame (`buf[:, 6:]` of a Y4MReader buffer works as it is).  matrix 'bt601' | 'bt709', range 'limited' | 'full' (`yuv_coeffs`), chroma
-    'bilinear' (centre-sited 1/4 - 3/4 filter, vertical then horizontal, indices clamped) | 'nearest'.  Returns float32 (n, 3, H, W) in
-    [0, 1] or uint8 (n, H, W, 3); the definition, operation by operation, is DESIGN 4.11.  ValueError for bad names and layouts."""
-    if chroma not in ('bilinear', 'nearest'):
-        raise ValueError(f"chroma must be 'bilinear' or 'nearest', got {chroma!r}")
-    if out_dtype not in (torch.float32, torch.uint8):
-        raise ValueError(f'out_dtype must be torch.float32 or torch.uint8, got {out_dtype}')
-    _, mi, off = yuv_coeffs(matrix, range)
-    require_gpu(yuv, dtypes=(torch.uint8,))
-    H, W = int(H), int(W)
-    n, fs, stride = _yuv_batch(yuv, H, W, 'yuv')
-    u8out = out_dtype == torch.uint8
-    out = torch.empty((n, H, W, 3) if u8out else (n, 3, H, W), dtype=out_dtype, device=yuv.device)
-    coef, bil = _yuv_coef_arg(mi, off), int(chroma == 'bilinear')
-    nbytes = float(n) * (fs + 3 * H * W * (1 if u8out else 4))
-    if u8out:
-        _run('yuv420_to_rgb', lambda: _lib.check(_lib.lib().edvr_yuv420_to_rgb_u8(_ptr(yuv), _ptr(out), n, H, W, stride, coef, bil, _stream()),
-                                                 'edvr_yuv420_to_rgb_u8'), 0, nbytes)
-    else:
-        _run('yuv420_to_rgb', lambda: _lib.check(_lib.lib().edvr_yuv420_to_rgb_f32(_ptr(yuv), _ptr(out), n, H, W, stride, 3 * H * W, coef, bil, _stream()),
-                                                 'edvr_yuv420_to_rgb_f32'), 0, nbytes)
-    return out
-
-
-def _byte_span(t):
-    """[first, last) byte addresses a tensor's elements lie in."""
-    if t.numel() == 0:
-        return t.data_ptr(), t.data_ptr()
-    last = sum((s - 1) * st for s, st in zip(t.shape, t.stride()))
-    return t.data_ptr(), t.data_ptr() + (last + 1) * t.element_size()
-
-
-def rgb_to_yuv420(rgb, matrix='bt601', range='limited', out=None):
-    """RGB frames -> 8-bit I420 in ONE launch: rgb float32 (n, 3, H, W) (clamped to [0, 1], x 255, NOT rounded before the matrix: the
-    only quantisation is the one to YUV bytes; dense images, a slice of a longer video works) or uint8 (n, H, W, 3).  Returns uint8
-    (n, framesize), framesize = yuv420_frame_size(H, W): luma, then Cb and Cr, each the mean of its 2 x 2 block (an odd edge replicates).
-    out: a uint8 (n, >= framesize) batch to write into instead, stride(1) == 1, any row stride and base offset (`buf[:, 6:]` of a Y4M
-    write buffer); bytes past a frame's end are left alone and `out` is returned.  ValueError for bad names, layouts and an `out` that
-    overlaps the input."""
-    m, _, off = yuv_coeffs(matrix, range)
-    if not rgb.is_cuda:
-        raise NotImplementedError('edvr_amd ops run on the GPU only (HIP/gfx950); got a CPU tensor')
-    u8 = rgb.dtype == torch.uint8
-    if u8:
-        if rgb.dim() != 4 or rgb.shape[-1] != 3:
-            raise ValueError(f'uint8 frames are (n, H, W, 3), got {tuple(rgb.shape)}')
-        rgb = rgb.contiguous()
-        n, H, W, _ = rgb.shape
-    else:
-        require_gpu(rgb)
-        if rgb.dim() != 4 or rgb.shape[1] != 3:
-            raise ValueError(f'float32 frames are (n, 3, H, W), got {tuple(rgb.shape)}')
-        rgb = _as_planes(rgb)
-        n, _, H, W = rgb.shape
-    if out is None:
-        out = torch.empty((n, yuv420_frame_size(H, W)), dtype=torch.uint8, device=rgb.device)
-    else:
-        require_gpu(out, dtypes=(torch.uint8,))
-        if out.dim() == 2 and out.shape[0] != n:
-            raise ValueError(f'out holds {out.shape[0]} frames, the input {n}')
-    n, fs, stride = _yuv_batch(out, H, W, 'out')
-    (a0, a1), (b0, b1) = _byte_span(rgb), _byte_span(out)
-    if a0 < b1 and b0 < a1:
-        raise ValueError('out overlaps the input')
-    coef = _yuv_coef_arg(m, off)
-    nbytes = float(n) * (fs + 3 * H * W * (1 if u8 else 4))
-    if u8:
-        _run('rgb_to_yuv420', lambda: _lib.check(_lib.lib().edvr_rgb_to_yuv420_u8(_ptr(rgb), _ptr(out), n, H, W, stride, coef, _stream()),
-                                                 'edvr_rgb_to_yuv420_u8'), 0, nbytes)
-    else:
-        _run('rgb_to_yuv420', lambda: _lib.check(_lib.lib().edvr_rgb_to_yuv420_f32(_ptr(rgb), _ptr(out), n, H, W, _img_stride(rgb), stride, coef, _stream()),
-                                                 'edvr_rgb_to_yuv420_f32'), 0, nbytes)
-    return out
-
-
-# ------------------------------------------------------------------------------------------------ every Y4M format (csrc/yuv_formats.hip)
-YUV_SUBSAMPLINGS = {'420': (1, 1), '422': (1, 0), '444': (0, 0)}                    # (sx, sy): log2 of the chroma decimation per axis
-_YUV_ALIASES = {'420jpeg': '420', '420mpeg2': '420', '420paldv': '420'}
-
-
-def yuv_format(name):
-    """A Y4M format name -> (sx, sy, depth, canonical): '420' | '422' | '444' (chroma planes ((H + sy) >> sy, (W + sx) >> sx)) with an
-    optional suffix p9 ... p16 for the bit depth (none: 8 bits; p8 is not a Y4M tag).  '420jpeg', '420mpeg2' and '420paldv' are
-    aliases of '420'.  canonical: '420', '422p10', '444p16' ...  ValueError for anything else (DESIGN 4.14)."""
-    if not isinstance(name, str):
-        raise ValueError(f'a format is a name such as 420, 422p10 or 444p16, got {name!r}')
-    base, sep, bits = _YUV_ALIASES.get(name, name).partition('p')
-    depth = 8
-    if sep:
-        if not (bits.isascii() and bits.isdigit()) or bits != str(int(bits)) or not 9 <= int(bits) <= 16:
-            raise ValueError(f'format {name!r}: the depth suffix is p9 ... p16')
-        depth = int(bits)
-    if base not in YUV_SUBSAMPLINGS:
-        raise ValueError(f'format {name!r}: the subsampling is one of {sorted(YUV_SUBSAMPLINGS)} (mono, 4:1:1, 4:4:0 and alpha are not supported)')
-    sx, sy = YUV_SUBSAMPLINGS[base]
-    return sx, sy, depth, base + (f'p{depth}' if depth > 8 else '')
-
-
-def yuv_frame_size(H, W, fmt='420'):
-    """BYTES of one frame of (H, W) in format `fmt`: the luma plane and two chroma planes of ((H + sy) >> sy, (W + sx) >> sx), one
-    byte per sample at 8 bits and two above."""
-    sx, sy, depth, _ = yuv_format(fmt)
-    return (H * W + 2 * ((H + sy) >> sy) * ((W + sx) >> sx)) * (2 if depth > 8 else 1)
-
-
-def _yuv_fmt_batch(yuv, H, W, fmt, what):
-    if yuv.dim() != 2:
-        raise ValueError(f'{what} is a 2-D uint8 batch (n, >= framesize), got {tuple(yuv.shape)}')
-    if H < 1 or W < 1:
-        raise ValueError(f'a frame has at least one row and column, got {H} x {W}')
-    sx, sy, depth, canonical = yuv_format(fmt)
-    fs = yuv_frame_size(H, W, canonical)
+    sx, sy, depth, canonical = fmt
+    fs = _yuv_frame_bytes(H, W, sx, sy, depth)
     if yuv.shape[1] < fs:
         raise ValueError(f'{what}: rows of {yuv.shape[1]} bytes are shorter than the {fs} bytes of a {H} x {W} {canonical} frame')
     if yuv.stride(1) != 1:
@@ -2062,7 +1968,42 @@ def _yuv_fmt_batch(yuv, H, W, fmt, what):
     if depth > 8 and (yuv.data_ptr() % 2 or (n > 1 and yuv.stride(0) % 2)):
         raise ValueError(f'{what}: the 16-bit samples of {canonical} need an even base address and an even row stride, got address '
                          f'{yuv.data_ptr():#x}, stride {yuv.stride(0)}')
-    return n, fs, (yuv.stride(0) if n > 1 else fs), (sx, sy, depth)
+    return n, fs, (yuv.stride(0) if n > 1 else fs)
+
+
+_YUV420 = (1, 1, 8, '420')  # yuv_format('420')
+
+
+def _yuv_decode(op, yuv, H, W, fmt, matrix, range, chroma, out_dtype):
+    """Both decodes, fmt = yuv_format(name); uint8 RGB (n, H, W, 3) exists for 8-bit 4:2:0 alone, through edvr_yuv420_to_rgb_u8."""
+    if chroma not in ('bilinear', 'nearest'):
+        raise ValueError(f"chroma must be 'bilinear' or 'nearest', got {chroma!r}")
+    sx, sy, depth, _ = fmt
+    _, mi, off = yuv_coeffs(matrix, range, depth)
+    require_gpu(yuv, dtypes=(torch.uint8,))
+    H, W = int(H), int(W)
+    n, fs, stride = _yuv_batch(yuv, H, W, fmt, 'yuv')
+    u8 = out_dtype == torch.uint8
+    out = torch.empty((n, H, W, 3) if u8 else (n, 3, H, W), dtype=out_dtype, device=yuv.device)
+    coef, bil = _yuv_coef_arg(mi, off), int(chroma == 'bilinear')
+    if u8:
+        call = lambda: _lib.check(_lib.lib().edvr_yuv420_to_rgb_u8(_ptr(yuv), _ptr(out), n, H, W, stride, coef, bil, _stream()), 'edvr_yuv420_to_rgb_u8')
+    else:
+        call = lambda: _lib.check(_lib.lib().edvr_yuv_to_rgb_f32(_ptr(yuv), _ptr(out), n, H, W, sx, sy, depth, stride, 3 * H * W, coef, bil, _stream()),
+                                  'edvr_yuv_to_rgb_f32')
+    _run(op, call, 0, float(n) * (fs + 3 * H * W * (1 if u8 else 4)))
+    return out
+
+
+def yuv420_to_rgb(yuv, H, W, matrix='bt601', range='limited', chroma='bilinear', out_dtype=torch.float32):
+    """8-bit I420 frames -> RGB in ONE launch.  yuv: uint8 (n, >= framesize) on the GPU with stride(1) == 1 and ANY row stride and base
+    offset - each row starts with the H W luma bytes, then the (ceil(H / 2), ceil(W / 2)) Cb and Cr planes, i.e. the payload of a Y4M
+    frame (`buf[:, 6:]` of a Y4MReader buffer works as it is).  matrix 'bt601' | 'bt709', range 'limited' | 'full' (`yuv_coeffs`), chroma
+    'bilinear' (centre-sited 1/4 - 3/4 filter, vertical then horizontal, indices clamped) | 'nearest'.  Returns float32 (n, 3, H, W) in
+    [0, 1] or uint8 (n, H, W, 3); the definition, operation by operation, is DESIGN 4.11.  ValueError for bad names and layouts."""
+    if out_dtype not in (torch.float32, torch.uint8):
+        raise ValueError(f'out_dtype must be torch.float32 or torch.uint8, got {out_dtype}')
+    return _yuv_decode('yuv420_to_rgb', yuv, H, W, _YUV420, matrix, range, chroma, out_dtype)
 
 
 def yuv_to_rgb(yuv, H, W, fmt='420', matrix='bt601', range='limited', chroma='bilinear'):
@@ -2072,18 +2013,63 @@ def yuv_to_rgb(yuv, H, W, fmt='420', matrix='bt601', range='limited', chroma='bi
     the depth are NOT masked, and the base address and row stride are even.  matrix, range: `yuv_coeffs` at the format's depth; chroma:
     'bilinear' (the centre-sited 1/4 - 3/4 filter along each subsampled axis, vertical then horizontal, indices clamped) | 'nearest'.
     The definition is DESIGN 4.14; at '420' it is that of yuv420_to_rgb, bit for bit.  ValueError for bad names and layouts."""
-    if chroma not in ('bilinear', 'nearest'):
-        raise ValueError(f"chroma must be 'bilinear' or 'nearest', got {chroma!r}")
-    depth = yuv_format(fmt)[2]
-    _, mi, off = yuv_coeffs(matrix, range, depth)
-    require_gpu(yuv, dtypes=(torch.uint8,))
-    H, W = int(H), int(W)
-    n, fs, stride, (sx, sy, depth) = _yuv_fmt_batch(yuv, H, W, fmt, 'yuv')
-    out = torch.empty((n, 3, H, W), dtype=torch.float32, device=yuv.device)
-    coef, bil = _yuv_coef_arg(mi, off), int(chroma == 'bilinear')
-    _run('yuv_to_rgb', lambda: _lib.check(_lib.lib().edvr_yuv_to_rgb_f32(_ptr(yuv), _ptr(out), n, H, W, sx, sy, depth, stride, 3 * H * W, coef, bil,
-                                                                         _stream()), 'edvr_yuv_to_rgb_f32'), 0, float(n) * (fs + 12 * H * W))
+    return _yuv_decode('yuv_to_rgb', yuv, H, W, yuv_format(fmt), matrix, range, chroma, torch.float32)
+
+
+def _byte_span(t):
+    """[first, last) byte addresses a tensor's elements lie in."""
+    if t.numel() == 0:
+        return t.data_ptr(), t.data_ptr()
+    last = sum((s - 1) * st for s, st in zip(t.shape, t.stride()))
+    return t.data_ptr(), t.data_ptr() + (last + 1) * t.element_size()
+
+
+def _yuv_encode(op, rgb, fmt, matrix, range, out, u8_too):
+    """Both encodes, fmt = yuv_format(name); uint8 RGB (n, H, W, 3) is read for 8-bit 4:2:0 alone (`u8_too`), through edvr_rgb_to_yuv420_u8."""
+    sx, sy, depth, _ = fmt
+    m, _, off = yuv_coeffs(matrix, range, depth)
+    if not rgb.is_cuda:
+        raise NotImplementedError('edvr_amd ops run on the GPU only (HIP/gfx950); got a CPU tensor')
+    u8 = u8_too and rgb.dtype == torch.uint8
+    if u8:
+        if rgb.dim() != 4 or rgb.shape[-1] != 3:
+            raise ValueError(f'uint8 frames are (n, H, W, 3), got {tuple(rgb.shape)}')
+        rgb = rgb.contiguous()
+        n, H, W, _ = rgb.shape
+    else:
+        require_gpu(rgb)
+        if rgb.dim() != 4 or rgb.shape[1] != 3:
+            raise ValueError(f'float32 frames are (n, 3, H, W), got {tuple(rgb.shape)}')
+        rgb = _as_planes(rgb)
+        n, _, H, W = rgb.shape
+    if out is None:
+        out = torch.empty((n, _yuv_frame_bytes(H, W, sx, sy, depth)), dtype=torch.uint8, device=rgb.device)
+    else:
+        require_gpu(out, dtypes=(torch.uint8,))
+        if out.dim() == 2 and out.shape[0] != n:
+            raise ValueError(f'out holds {out.shape[0]} frames, the input {n}')
+    n, fs, stride = _yuv_batch(out, H, W, fmt, 'out')
+    (a0, a1), (b0, b1) = _byte_span(rgb), _byte_span(out)
+    if a0 < b1 and b0 < a1:
+        raise ValueError('out overlaps the input')
+    coef = _yuv_coef_arg(m, off)
+    if u8:
+        call = lambda: _lib.check(_lib.lib().edvr_rgb_to_yuv420_u8(_ptr(rgb), _ptr(out), n, H, W, stride, coef, _stream()), 'edvr_rgb_to_yuv420_u8')
+    else:
+        call = lambda: _lib.check(_lib.lib().edvr_rgb_to_yuv_f32(_ptr(rgb), _ptr(out), n, H, W, sx, sy, depth, _img_stride(rgb), stride, coef, _stream()),
+                                  'edvr_rgb_to_yuv_f32')
+    _run(op, call, 0, float(n) * (fs + 3 * H * W * (1 if u8 else 4)))
     return out
+
+
+def rgb_to_yuv420(rgb, matrix='bt601', range='limited', out=None):
+    """RGB frames -> 8-bit I420 in ONE launch: rgb float32 (n, 3, H, W) (clamped to [0, 1], x 255, NOT rounded before the matrix: the
+    only quantisation is the one to YUV bytes; dense images, a slice of a longer video works) or uint8 (n, H, W, 3).  Returns uint8
+    (n, framesize), framesize = yuv420_frame_size(H, W): luma, then Cb and Cr, each the mean of its 2 x 2 block (an odd edge replicates).
+    out: a uint8 (n, >= framesize) batch to write into instead, stride(1) == 1, any row stride and base offset (`buf[:, 6:]` of a Y4M
+    write buffer); bytes past a frame's end are left alone and `out` is returned.  ValueError for bad names, layouts and an `out` that
+    overlaps the input."""
+    return _yuv_encode('rgb_to_yuv420', rgb, _YUV420, matrix, range, out, True)
 
 
 def rgb_to_yuv(rgb, fmt='420', matrix='bt601', range='limited', out=None):
@@ -2095,27 +2081,7 @@ def rgb_to_yuv(rgb, fmt='420', matrix='bt601', range='limited', out=None):
     offset (even ones above 8 bits; `buf[:, 6:]` of a Y4M write buffer); bytes past a frame's end are left alone and `out` is returned.
     uint8 RGB stays with rgb_to_yuv420.  The definition is DESIGN 4.14.  ValueError for bad names, layouts and an `out` that overlaps
     the input."""
-    depth = yuv_format(fmt)[2]
-    m, _, off = yuv_coeffs(matrix, range, depth)
-    require_gpu(rgb)
-    if rgb.dim() != 4 or rgb.shape[1] != 3:
-        raise ValueError(f'float32 frames are (n, 3, H, W), got {tuple(rgb.shape)}')
-    rgb = _as_planes(rgb)
-    n, _, H, W = rgb.shape
-    if out is None:
-        out = torch.empty((n, yuv_frame_size(H, W, fmt)), dtype=torch.uint8, device=rgb.device)
-    else:
-        require_gpu(out, dtypes=(torch.uint8,))
-        if out.dim() == 2 and out.shape[0] != n:
-            raise ValueError(f'out holds {out.shape[0]} frames, the input {n}')
-    n, fs, stride, (sx, sy, depth) = _yuv_fmt_batch(out, H, W, fmt, 'out')
-    (a0, a1), (b0, b1) = _byte_span(rgb), _byte_span(out)
-    if a0 < b1 and b0 < a1:
-        raise ValueError('out overlaps the input')
-    coef = _yuv_coef_arg(m, off)
-    _run('rgb_to_yuv', lambda: _lib.check(_lib.lib().edvr_rgb_to_yuv_f32(_ptr(rgb), _ptr(out), n, H, W, sx, sy, depth, _img_stride(rgb), stride, coef,
-                                                                         _stream()), 'edvr_rgb_to_yuv_f32'), 0, float(n) * (fs + 12 * H * W))
-    return out
+    return _yuv_encode('rgb_to_yuv', rgb, yuv_format(fmt), matrix, range, out, False)
 
 
 # ------------------------------------------------------------------------------------------------ scene cuts

@@ -206,7 +206,7 @@ def restore_y4m(net, src, dst, *, matrix_in=None, matrix_out=None, chroma='bilin
     reader = src if isinstance(src, Y4MReader) else Y4MReader(src, formats=ALL_FORMATS)
     fmt_in = reader.format
     fmt_out = fmt_in if out_format is None else ops.yuv_format(out_format)[3]
-    plain420 = fmt_in == '420' and fmt_out == '420'  # the 8-bit 4:2:0 kernels of csrc/yuv.hip on both sides
+    plain420 = fmt_in == '420' and fmt_out == '420'  # the 8-bit 4:2:0 operators (uint8 samples, 4:2:0 instances of csrc/yuv.hip) on both sides
     if int(read_frames) < 1:
         raise ValueError(f'read_frames must be at least 1, got {read_frames}')
     for name in (matrix_in, matrix_out):

@@ -690,21 +690,28 @@ int edvr_imresize_bicubic_u8_windows(const uint8_t *src, const int32_t *table, c
 int edvr_bd_downsample_u8_windows(const uint8_t *src, const int32_t *table, const int32_t *table_host, uint8_t *dst, int n, int p, int wh, int ww,
                                   int pitch, int scale, edvr_stream_t stream);
 
-/* 8-bit Y'CbCr 4:2:0 <-> RGB (csrc/yuv.hip; definition: DESIGN 4.11).  An I420 frame of (H, W) is H W luma bytes, then Hc Wc bytes of Cb,
- * then of Cr, Hc = ceil(H / 2), Wc = ceil(W / 2), every plane dense - the payload of a YUV4MPEG2 frame; a batch is n frames yuv_stride >=
- * framesize bytes apart at ANY base address and stride (a Y4M read buffer: framesize + 6 apart, 6 past its start).  Odd H and W are legal.
- * coef: 12 HOST floats read before the call returns - a 3 x 3 matrix row-major, then the offsets (yoff, 128, 128): for the decode the
- * INVERSE of the forward matrix M, for the encode M itself (RGB in 0 ... 255 -> Y, Cb, Cr), computed in float64 by the caller and rounded.
- * All arithmetic float32, every product and sum rounded on its own in the order of DESIGN 4.11 (no contraction).
- * yuv420_to_rgb: chroma upsampled by replication (bilinear == 0) or by the centre-sited 1/4 - 3/4 filter, vertical then horizontal,
- * indices clamped to the plane; v = Mi (Y - yoff, Cb - 128, Cr - 128); _f32: rgb (n, 3, H, W), dense images rgb_img_stride floats apart,
- * clamp(v, 0, 255) / 255.0f; _u8: rgb (n, H, W, 3) dense bytes, clamp and round half to even.
- * rgb_to_yuv420: _f32 reads x = clamp(f, 0, 1) * 255.0f (NaN -> 0), _u8 the byte; p = M x + off; Y = round(clamp(p_0)), a chroma sample
- * the mean of p over its 2 x 2 block (row and column indices clamped to the frame: an odd edge replicates), clamped and rounded.  Bytes
- * between the frames of the output batch are not written.
+/* Planar Y'CbCr of any Y4M format <-> RGB (csrc/yuv.hip, one kernel family; definition: DESIGN 4.11, depths and subsamplings: 4.14).
+ * A format is a chroma subsampling (sub_x, sub_y) - (1, 1) 4:2:0, (1, 0) 4:2:2, (0, 0) 4:4:4 - and a bit depth 8 ... 16.  A frame of
+ * (H, W) is the dense planes Y (H, W), Cb, Cr (Hc, Wc) = ((H + sub_y) >> sub_y, (W + sub_x) >> sub_x) - the payload of a YUV4MPEG2
+ * frame; a sample is one byte at depth 8, otherwise one little-endian 16-bit word (bits above the depth are NOT masked by the decode).
+ * A batch is n frames yuv_stride >= framesize BYTES apart at ANY base address and stride (a Y4M read buffer: framesize + 6 apart, 6 past
+ * its start); with 16-bit samples the base address and yuv_stride are even.  Odd H and W are legal.
+ * coef: 12 HOST floats read before the call returns - a 3 x 3 matrix row-major, then the offsets (yoff, coff, coff): for the decode the
+ * INVERSE of the forward matrix M, for the encode M itself (RGB in 0 ... 255 -> Y, Cb, Cr), computed in float64 and scaled for the depth
+ * by the caller (ops.yuv_coeffs(matrix, range, depth)) and rounded.  All arithmetic float32, every product and sum rounded on its own
+ * in the order of DESIGN 4.11 (no contraction).
+ * yuv_to_rgb: chroma upsampled along the subsampled axes by replication (bilinear == 0) or by the centre-sited 1/4 - 3/4 filter, vertical
+ * then horizontal, indices clamped to the plane; v = Mi (Y - yoff, Cb - coff, Cr - coff); _f32: rgb (n, 3, H, W), dense images
+ * rgb_img_stride floats apart, clamp(v, 0, 255) / 255.0f; _u8: rgb (n, H, W, 3) dense bytes, clamp and round half to even.
+ * rgb_to_yuv: _f32 reads x = clamp(f, 0, 1) * 255.0f (NaN -> 0), _u8 the byte; p = M x + off; a chroma sample is the mean of p over its
+ * 2 x 2 block (4:2:0), over its pair of columns (4:2:2: (p[2l] + p[2l + 1]) * 0.5f) or p itself (4:4:4), row and column indices clamped
+ * to the frame (an odd edge replicates); every sample is clamped to [0, 2^depth - 1] and rounded half to even.  Bytes between the frames
+ * of the output batch are not written.
+ * The yuv420 four are the same functions at (sub_x, sub_y, depth) = (1, 1, 8) - an I420 frame: H W luma bytes, then Hc Wc bytes of Cb,
+ * then of Cr, Hc = ceil(H / 2), Wc = ceil(W / 2); uint8 RGB exists for this format alone.
  * 16-byte accesses on a side whose base and strides are 16-byte aligned where W % 16 == 0, scalar ones otherwise; same values either way.
- * EDVR_ERR_ARG: null pointers, n, H or W < 1, yuv_stride < framesize or rgb_img_stride < 3 H W with n > 1, H W > 2^29.  No allocation,
- * no wait. */
+ * EDVR_ERR_ARG: null pointers, n, H or W < 1, depth outside 8 ... 16, a subsampling other than the three, yuv_stride < framesize or
+ * rgb_img_stride < 3 H W with n > 1, an odd base or stride with 16-bit samples, H W > 2^29.  No allocation, no wait. */
 int edvr_yuv420_to_rgb_f32(const uint8_t *yuv, float *rgb, int n, int H, int W, int64_t yuv_stride, int64_t rgb_img_stride, const float *coef,
                            int bilinear, edvr_stream_t stream);
 int edvr_yuv420_to_rgb_u8(const uint8_t *yuv, uint8_t *rgb, int n, int H, int W, int64_t yuv_stride, const float *coef, int bilinear,
@@ -712,19 +719,6 @@ int edvr_yuv420_to_rgb_u8(const uint8_t *yuv, uint8_t *rgb, int n, int H, int W,
 int edvr_rgb_to_yuv420_f32(const float *rgb, uint8_t *yuv, int n, int H, int W, int64_t rgb_img_stride, int64_t yuv_stride, const float *coef,
                            edvr_stream_t stream);
 int edvr_rgb_to_yuv420_u8(const uint8_t *rgb, uint8_t *yuv, int n, int H, int W, int64_t yuv_stride, const float *coef, edvr_stream_t stream);
-
-/* Planar Y'CbCr of any Y4M format <-> float32 RGB (csrc/yuv_formats.hip; definition: DESIGN 4.14).  A format is a chroma subsampling
- * (sub_x, sub_y) - (1, 1) 4:2:0, (1, 0) 4:2:2, (0, 0) 4:4:4 - and a bit depth 8 ... 16.  A frame of (H, W) is the dense planes Y (H, W),
- * Cb, Cr (Hc, Wc) = ((H + sub_y) >> sub_y, (W + sub_x) >> sub_x); a sample is one byte at depth 8, otherwise one little-endian 16-bit
- * word (bits above the depth are NOT masked by the decode).  A batch is n frames yuv_stride >= framesize BYTES apart; with 16-bit samples
- * the base address and yuv_stride are even.  coef: as above, the offsets (yoff, coff, coff) and the matrix scaled for the depth by the
- * caller (ops.yuv_coeffs(matrix, range, depth)).  The arithmetic is that of the 8-bit 4:2:0 pair, operation by operation; the chroma
- * filter of the decode runs along a subsampled axis only, the chroma sample of the encode is the mean of its 2 x 2 block (4:2:0), of its
- * pair of columns (4:2:2: (p[2l] + p[2l + 1]) * 0.5f) or p itself (4:4:4); every sample is clamped to [0, 2^depth - 1] and rounded half
- * to even.  rgb: float32 (n, 3, H, W), dense images rgb_img_stride floats apart.  Bytes between the frames of an output batch are not
- * written.  16-byte accesses on a side whose base and strides are 16-byte aligned where W % 16 == 0, scalar ones otherwise; same values.
- * EDVR_ERR_ARG: null pointers, n, H or W < 1, depth outside 8 ... 16, a subsampling other than the three, yuv_stride < framesize or
- * rgb_img_stride < 3 H W with n > 1, an odd base or stride with 16-bit samples, H W > 2^29.  No allocation, no wait. */
 int edvr_yuv_to_rgb_f32(const uint8_t *yuv, float *rgb, int n, int H, int W, int sub_x, int sub_y, int depth, int64_t yuv_stride,
                         int64_t rgb_img_stride, const float *coef, int bilinear, edvr_stream_t stream);
 int edvr_rgb_to_yuv_f32(const float *rgb, uint8_t *yuv, int n, int H, int W, int sub_x, int sub_y, int depth, int64_t rgb_img_stride,

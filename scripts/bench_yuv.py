@@ -1,22 +1,26 @@
-"""Times the Y'CbCr 4:2:0 <-> RGB kernels (csrc/yuv.hip) and the Y4M path built on them.
+"""Times the Y'CbCr <-> RGB kernels (csrc/yuv.hip) and the Y4M path built on them.
 
-  (a) ops.yuv420_to_rgb (float32 output, bilinear chroma) and ops.rgb_to_yuv420 (float32 input) on 8 frames of 180 x 320 and 720 x 1280 and
-      one of 2160 x 3840, each on a dense 16-byte-aligned batch and inside a Y4M buffer (stride framesize + 6, 6 bytes in: scalar accesses
-      on the YUV side): device events around one call (launch included) after warm-up, the median, the bytes actually moved (frame bytes +
-      float32 RGB bytes, each once) and the share of the 6.29 TB/s measured HBM rate they amount to;
+  (a) ops.yuv420_to_rgb (bilinear chroma) and ops.rgb_to_yuv420, float32 RGB and (the *_u8_* arms) uint8 RGB, on 8 frames of 180 x 320 and
+      720 x 1280 and one of 2160 x 3840, each on a dense 16-byte-aligned batch and inside a Y4M buffer (stride framesize + 6, 6 bytes in:
+      scalar accesses on the YUV side): device events around one call (launch included) after warm-up, the median, the bytes actually moved
+      (frame bytes + RGB bytes, each once) and the share of the 6.29 TB/s measured HBM rate they amount to;
   (b) a stock-torch composition of the same definition on the device (slicing, repeat_interleave-free index arithmetic, separate mul /
       add, clamp, round) as a TIMING arm only;
   (c) restore_y4m on an in-memory Y4M of 100 frames of 180 x 320 (EDVR-L as trained, T = 5, chunk 10) in frames/s, host clock around the call
       ending in a synchronise, against VideoRestorer.restore on resident float32 frames - the parent's path - alternated, three runs each, so
       that the spread of the resident arm is known before the difference is read.
 
-  (d) with --formats, INSTEAD of (a) - (c): ops.yuv_to_rgb (bilinear chroma) and ops.rgb_to_yuv (csrc/yuv_formats.hip) for '420p10', '422p10',
-      '444p10' and, through the same kernels, '420', on 8 frames of 720 x 1280 and one of 2160 x 3840 in a dense 16-byte-aligned batch, timed as
-      (a); beside them, in the same process and at the same shapes, ops.yuv420_to_rgb / ops.rgb_to_yuv420 - the 8-bit 4:2:0 kernels of
-      csrc/yuv.hip, which this leg leaves as they were: the comparison arm.  Written to profiles/yuv/bench_yuv_formats.json.
+  (d) with --formats, INSTEAD of (a) - (c): ops.yuv_to_rgb (bilinear chroma) and ops.rgb_to_yuv for '420p10', '422p10', '444p10' and '420'
+      on 8 frames of 720 x 1280 and one of 2160 x 3840 in a dense 16-byte-aligned batch, timed as (a); beside them, in the same process and
+      at the same shapes, ops.yuv420_to_rgb / ops.rgb_to_yuv420, which reach the same kernels as the '420' row through the 8-bit 4:2:0
+      entry points.  Printed, and written where --out names a file: profiles/yuv/bench_yuv_formats.json is the record of the commit that
+      still had a kernel file per operator pair and is not overwritten by default.
+
+Only public ops calls that every revision with both operator pairs has, so the same file times an older tree for a comparison.
 
     python scripts/bench_yuv.py [--out profiles/yuv/bench_yuv.json] [--skip-video]
-    python scripts/bench_yuv.py --formats [--out profiles/yuv/bench_yuv_formats.json]
+    python scripts/bench_yuv.py --formats [--out FILE]
+    python scripts/bench_yuv.py ... --tree DIR     the package of another checkout (built), for scripts/bench_yuv_compare.py
 """
 import argparse
 import io
@@ -29,7 +33,7 @@ import time
 
 import torch
 
-sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..'))
+HERE = os.path.dirname(os.path.abspath(__file__))
 
 HBM_TBS = 6.29
 CASES = [('8x180x320', 8, (180, 320)), ('8x720x1280', 8, (720, 1280)), ('1x2160x3840', 1, (2160, 3840))]
@@ -84,9 +88,9 @@ def stock_encode(rgb, m, off):
     return torch.cat(planes, 1)
 
 
-def git_head():
+def git_head(tree):
     try:
-        return subprocess.check_output(['git', 'rev-parse', 'HEAD'], cwd=os.path.dirname(os.path.abspath(__file__)), stderr=subprocess.DEVNULL).decode().strip()
+        return subprocess.check_output(['git', 'rev-parse', 'HEAD'], cwd=tree, stderr=subprocess.DEVNULL).decode().strip()
     except (OSError, subprocess.CalledProcessError):
         return None
 
@@ -102,25 +106,34 @@ def kernel_rows(args, dev):
         y4m = torch.zeros((n, fs + 6), dtype=torch.uint8, device=dev)
         y4m[:, 6:] = frames
         rgb = ops.yuv420_to_rgb(frames, H, W, 'bt709', 'limited')
+        rgb8 = ops.yuv420_to_rgb(frames, H, W, 'bt709', 'limited', 'bilinear', torch.uint8)
         assert torch.equal(rgb, ops.yuv420_to_rgb(y4m[:, 6:], H, W, 'bt709', 'limited'))
+        assert torch.equal(rgb8, ops.yuv420_to_rgb(y4m[:, 6:], H, W, 'bt709', 'limited', 'bilinear', torch.uint8))
+        assert torch.equal(ops.rgb_to_yuv420(rgb8, 'bt709', 'limited'), ops.rgb_to_yuv420(rgb8, 'bt709', 'limited', out=y4m[:, 6:]))
         assert torch.equal(ops.rgb_to_yuv420(rgb, 'bt709', 'limited'), ops.rgb_to_yuv420(rgb, 'bt709', 'limited', out=y4m[:, 6:]))
         parity_dec = (rgb - stock_decode(frames, H, W, mi, off)).abs().max().item()
         parity_enc = (ops.rgb_to_yuv420(rgb, 'bt709', 'limited').int() - stock_encode(rgb, m, off).int()).abs().max().item()
-        nbytes = n * (fs + 12 * H * W)
+        nbytes, nbytes_u8 = n * (fs + 12 * H * W), n * (fs + 3 * H * W)
         arms = {
             'decode_dense': lambda: ops.yuv420_to_rgb(frames, H, W, 'bt709', 'limited'),
             'decode_y4m': lambda: ops.yuv420_to_rgb(y4m[:, 6:], H, W, 'bt709', 'limited'),
             'encode_dense': lambda: ops.rgb_to_yuv420(rgb, 'bt709', 'limited', out=frames),
             'encode_y4m': lambda: ops.rgb_to_yuv420(rgb, 'bt709', 'limited', out=y4m[:, 6:]),
+            'decode_u8_dense': lambda: ops.yuv420_to_rgb(frames, H, W, 'bt709', 'limited', 'bilinear', torch.uint8),
+            'decode_u8_y4m': lambda: ops.yuv420_to_rgb(y4m[:, 6:], H, W, 'bt709', 'limited', 'bilinear', torch.uint8),
+            'encode_u8_dense': lambda: ops.rgb_to_yuv420(rgb8, 'bt709', 'limited', out=frames),
+            'encode_u8_y4m': lambda: ops.rgb_to_yuv420(rgb8, 'bt709', 'limited', out=y4m[:, 6:]),
         }
-        row = dict(case=name, frames=n, size=[H, W], bytes_moved=nbytes, stock_decode_max_abs_diff=parity_dec, stock_encode_max_abs_diff=parity_enc)
+        row = dict(case=name, frames=n, size=[H, W], bytes_moved=nbytes, bytes_moved_u8=nbytes_u8, stock_decode_max_abs_diff=parity_dec,
+                   stock_encode_max_abs_diff=parity_enc)
         for arm, fn in arms.items():
+            moved = nbytes_u8 if '_u8_' in arm else nbytes
             first, second = timed(fn, args.warmup, args.iters), timed(fn, 5, args.iters)  # twice: the first ran on a colder device
             med = min(first[0], second[0])
             row[arm + '_us'] = round(med, 2)
             row[arm + '_us_runs'] = [round(first[0], 2), round(second[0], 2)]
             row[arm + '_us_min_max'] = [round(min(first[1], second[1]), 2), round(max(first[2], second[2]), 2)]
-            row[arm + '_hbm_fraction'] = round(nbytes / (med * 1e-6) / (HBM_TBS * 1e12), 4)
+            row[arm + '_hbm_fraction'] = round(moved / (med * 1e-6) / (HBM_TBS * 1e12), 4)
         row['stock_decode_us'] = round(timed(lambda: stock_decode(frames, H, W, mi, off), 5, max(20, args.iters // 4))[0], 2)
         row['stock_encode_us'] = round(timed(lambda: stock_encode(rgb, m, off), 5, max(20, args.iters // 4))[0], 2)
         rows.append(row)
@@ -133,7 +146,8 @@ FORMATS = ['420p10', '422p10', '444p10', '420']
 
 
 def format_rows(args, dev):
-    """Leg (d): one row per shape and format through csrc/yuv_formats.hip, and one per shape through the 8-bit 4:2:0 kernels of csrc/yuv.hip."""
+    """Leg (d): one row per shape and format through ops.yuv_to_rgb / ops.rgb_to_yuv, and one per shape through ops.yuv420_to_rgb /
+    ops.rgb_to_yuv420."""
     from edvr_amd import ops
     rows = []
 
@@ -153,7 +167,7 @@ def format_rows(args, dev):
         rgb = torch.rand((n, 3, H, W), generator=gen).to(dev)
         frames8 = ops.rgb_to_yuv420(rgb, 'bt709', 'limited')
         fs8 = ops.yuv420_frame_size(H, W)
-        measure(dict(case=name, frames=n, size=[H, W], kernels='yuv.hip', format='420', bytes_moved=n * (fs8 + 12 * H * W)),
+        measure(dict(case=name, frames=n, size=[H, W], ops='yuv420_to_rgb / rgb_to_yuv420', format='420', bytes_moved=n * (fs8 + 12 * H * W)),
                 {'decode': lambda: ops.yuv420_to_rgb(frames8, H, W, 'bt709', 'limited'),
                  'encode': lambda: ops.rgb_to_yuv420(rgb, 'bt709', 'limited', out=frames8)}, n * (fs8 + 12 * H * W))
         for fmt in FORMATS:
@@ -162,7 +176,7 @@ def format_rows(args, dev):
             if fmt == '420':
                 assert torch.equal(frames, frames8) and torch.equal(ops.yuv_to_rgb(frames, H, W, fmt, 'bt709', 'limited'),
                                                                     ops.yuv420_to_rgb(frames8, H, W, 'bt709', 'limited'))
-            measure(dict(case=name, frames=n, size=[H, W], kernels='yuv_formats.hip', format=fmt, bytes_moved=n * (fs + 12 * H * W)),
+            measure(dict(case=name, frames=n, size=[H, W], ops='yuv_to_rgb / rgb_to_yuv', format=fmt, bytes_moved=n * (fs + 12 * H * W)),
                     {'decode': lambda: ops.yuv_to_rgb(frames, H, W, fmt, 'bt709', 'limited'),
                      'encode': lambda: ops.rgb_to_yuv(rgb, fmt, 'bt709', 'limited', out=frames)}, n * (fs + 12 * H * W))
     return rows
@@ -217,23 +231,24 @@ def video_row(args, dev):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument('--out', default=None, help='default: profiles/yuv/bench_yuv.json, with --formats profiles/yuv/bench_yuv_formats.json')
-    ap.add_argument('--formats', action='store_true', help='leg (d) alone: the format-aware kernels beside the 8-bit 4:2:0 kernels')
+    ap.add_argument('--out', default=None, help='default: profiles/yuv/bench_yuv.json; with --formats none, the rows are only printed')
+    ap.add_argument('--tree', default=os.path.join(HERE, '..'), help='the checkout whose edvr_amd package is timed (default: this one)')
+    ap.add_argument('--formats', action='store_true', help='leg (d) alone: the operators that take a format beside the 8-bit 4:2:0 operators')
     ap.add_argument('--warmup', type=int, default=20)
     ap.add_argument('--iters', type=int, default=200)
     ap.add_argument('--video-frames', type=int, default=100)
     ap.add_argument('--skip-video', action='store_true', help='kernels only')
     ap.add_argument('--head', default=None, help='commit to record where the tree is not a git checkout (default: git rev-parse HEAD)')
     args = ap.parse_args()
-    if args.out is None:
-        args.out = os.path.join(os.path.dirname(os.path.abspath(__file__)), '..', 'profiles', 'yuv',
-                                'bench_yuv_formats.json' if args.formats else 'bench_yuv.json')
+    if args.out is None and not args.formats:
+        args.out = os.path.join(HERE, '..', 'profiles', 'yuv', 'bench_yuv.json')
+    sys.path.insert(0, os.path.abspath(args.tree))
     assert args.iters >= 20, 'the median of at least 20 calls'
     assert torch.cuda.is_available(), 'bench_yuv needs the GPU: there is no CPU path to time'
     from edvr_amd import _lib
     from edvr_amd.build import source_hash
     dev = torch.device('cuda:0')
-    record = dict(bench='bench_yuv', lib=_lib.lib().edvr_version().decode(), source_hash=source_hash(), git_head=args.head or git_head(),
+    record = dict(bench='bench_yuv', lib=_lib.lib().edvr_version().decode(), source_hash=source_hash(), git_head=args.head or git_head(os.path.abspath(args.tree)),
                   device=torch.cuda.get_device_name(0), hbm_tbs=HBM_TBS, warmup=args.warmup, iters=args.iters)
     if args.formats:
         record['bench'], record['formats'] = 'bench_yuv_formats', format_rows(args, dev)
@@ -241,10 +256,11 @@ def main():
         record['kernels'] = kernel_rows(args, dev)
     if not args.skip_video and not args.formats:
         record['restore_y4m'] = video_row(args, dev)
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, 'w') as f:
-        json.dump(record, f, indent=1)
-    print(f'wrote {args.out}')
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, 'w') as f:
+            json.dump(record, f, indent=1)
+        print(f'wrote {args.out}')
 
 
 if __name__ == '__main__':

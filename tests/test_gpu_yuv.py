@@ -1,4 +1,4 @@
-"""GPU: csrc/yuv.hip (ops.yuv420_to_rgb / ops.rgb_to_yuv420) bit for bit against the definition evaluated on the host (tests/util_yuv.py),
+"""GPU: the 8-bit 4:2:0 instances of csrc/yuv.hip (ops.yuv420_to_rgb / ops.rgb_to_yuv420, float32 and uint8 RGB) bit for bit against the definition evaluated on the host (tests/util_yuv.py),
 over sizes, layouts and both access-width paths; the golden fixture of the reference through the kernels; and edvr_amd.y4m.restore_y4m
 against the composition done by hand."""
 import ctypes
@@ -126,11 +126,20 @@ def test_layouts_and_access_widths_agree(H, W):
     assert torch.equal(off.cpu(), want_dec[('bilinear', torch.float32)]) and float(flat[0]) == 0.0 and float(flat[-1]) == 0.0
     flat8 = torch.zeros(n * 3 * H * W + 16, dtype=torch.uint8, device='cuda')
     off8 = flat8[1:1 + n * 3 * H * W].view(n, H, W, 3)
-    _lib.check(_lib.lib().edvr_yuv420_to_rgb_u8(ctypes.c_void_p(dev.data_ptr()), ctypes.c_void_p(off8.data_ptr()), n, H, W, fs, coef, 0, stream),
-               'edvr_yuv420_to_rgb_u8')
-    assert torch.equal(off8.cpu(), want_dec[('nearest', torch.uint8)]) and int(flat8[0]) == 0 and int(flat8[-15:].sum()) == 0
+    for c in ('bilinear', 'nearest'):
+        flat8.zero_()
+        _lib.check(_lib.lib().edvr_yuv420_to_rgb_u8(ctypes.c_void_p(dev.data_ptr()), ctypes.c_void_p(off8.data_ptr()), n, H, W, fs, coef,
+                                                    int(c == 'bilinear'), stream), 'edvr_yuv420_to_rgb_u8')
+        assert torch.equal(off8.cpu(), want_dec[(c, torch.uint8)]) and int(flat8[0]) == 0 and int(flat8[-15:].sum()) == 0, c
     off8.copy_(rgb8.cuda())
     assert torch.equal(ops.rgb_to_yuv420(off8, 'bt709', 'limited').cpu(), want_enc[torch.uint8])
+    # the float32 8-bit 4:2:0 encode of the C ABI, which the operators no longer pass through
+    m, _, _ = ops.yuv_coeffs('bt709', 'limited')
+    coef = (ctypes.c_float * 12)(*[v for row in m for v in row], *o3)
+    src, enc = rgbf.cuda(), torch.zeros(n, fs, dtype=torch.uint8, device='cuda')
+    _lib.check(_lib.lib().edvr_rgb_to_yuv420_f32(ctypes.c_void_p(src.data_ptr()), ctypes.c_void_p(enc.data_ptr()), n, H, W, 3 * H * W, fs, coef,
+                                                 stream), 'edvr_rgb_to_yuv420_f32')
+    assert torch.equal(enc.cpu(), want_enc[torch.float32])
 
 
 def test_golden_fixture_through_the_kernels():

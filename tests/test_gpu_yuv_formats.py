@@ -1,4 +1,4 @@
-"""GPU: csrc/yuv_formats.hip (ops.yuv_to_rgb / ops.rgb_to_yuv) bit for bit against the definition evaluated on the host
+"""GPU: every format of csrc/yuv.hip (ops.yuv_to_rgb / ops.rgb_to_yuv) bit for bit against the definition evaluated on the host
 (tests/util_yuv_formats.py) over formats, depths, sizes, layouts and both access widths of either side; against the 8-bit
 4:2:0 operators at '420'; and edvr_amd.y4m.restore_y4m on 10-bit, 4:2:2 and 4:4:4 streams against the composition done by hand."""
 import ctypes

@@ -1,5 +1,5 @@
 """The definition of ops.yuv420_to_rgb / ops.rgb_to_yuv420 in torch float32 on the CPU, one tensor operation per rounding:
-what the kernels of csrc/yuv.hip are compared against bit for bit, and what the golden fixture ties to the reference's rgb2ycbcr /
+what the 8-bit 4:2:0 instances of csrc/yuv.hip are compared against bit for bit, and what the golden fixture ties to the reference's rgb2ycbcr /
 ycbcr2rgb.  Written from the definition, not from the kernels: the only shared piece is the order of operations the definition fixes."""
 import os
 

@@ -1,5 +1,5 @@
 """The definition of ops.yuv_to_rgb / ops.rgb_to_yuv in torch float32 on the CPU, one tensor operation per rounding: what
-the kernels of csrc/yuv_formats.hip are compared against bit for bit.  Written from the definition, not from the kernels, in the manner
+the kernels of csrc/yuv.hip are compared against bit for bit.  Written from the definition, not from the kernels, in the manner
 of tests/util_yuv.py (whose 8-bit 4:2:0 definition this one must reproduce at '420')."""
 import torch
 
