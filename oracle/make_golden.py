@@ -251,6 +251,81 @@ def ssim_case():
         sys.modules['cv2'] = saved
 
 
+def metrics_edges_case():
+    """PSNR and SSIM of the reference's own calculate_psnr / calculate_ssim on the reference's own tensor2img (basicsr/utils/img_util.py:36-98,
+    so the rounding of exact halves is the reference's, not a restatement's) of the edge contents of tests/util_metrics.py: `ties`, `wide`,
+    `inf` and `const` at 27 x 42 and at 40 x 44 with crop_border 7 (GOLDEN_CASES), three channels, both test_y_channel values.  cv2 is
+    absent: getGaussianKernel / filter2D as in ssim_case, cvtColor(RGB2BGR) = the channels reversed; torchvision's make_grid (4-D input
+    only) is never reached.  The file keeps `ties` as the bytes k of float32((k + 0.5) / 255) and `const` as one value per tensor."""
+    import sys
+    import types
+    import importlib.util
+    import numpy as np
+    from scipy import ndimage
+    import util_metrics as UM
+    cv2 = types.ModuleType('cv2')
+    cv2.COLOR_RGB2BGR = 4
+
+    def gk(ksize, sigma):
+        x = np.arange(ksize, dtype=np.float64) - (ksize - 1) * 0.5
+        k = np.exp(-0.5 / (sigma * sigma) * x * x)
+        return (k / k.sum()).reshape(-1, 1)
+    cv2.getGaussianKernel = gk
+    cv2.filter2D = lambda img, ddepth, kernel: ndimage.correlate(img, kernel, mode='mirror')
+    cv2.cvtColor = lambda img, code: np.ascontiguousarray(img[:, :, ::-1])
+    names = ('cv2', 'torchvision', 'torchvision.utils', 'basicsr', 'basicsr.utils', 'basicsr.metrics', 'basicsr.utils.img_util',
+             'basicsr.utils.matlab_functions', 'basicsr.metrics.metric_util', 'basicsr.metrics.psnr_ssim')
+    saved = {k: sys.modules.get(k) for k in names}
+    sys.modules['cv2'] = cv2
+    tv, tvu = types.ModuleType('torchvision'), types.ModuleType('torchvision.utils')
+    tvu.make_grid = None
+    sys.modules['torchvision'], sys.modules['torchvision.utils'] = tv, tvu
+    for pkg in ('basicsr', 'basicsr.utils', 'basicsr.metrics'):
+        m = types.ModuleType(pkg)
+        m.__path__ = []
+        sys.modules[pkg] = m
+
+    def load(name, rel):
+        spec = importlib.util.spec_from_file_location(name, os.path.join('/root/reference', rel))
+        mod = importlib.util.module_from_spec(spec)
+        sys.modules[name] = mod
+        spec.loader.exec_module(mod)
+        return mod
+    try:
+        tensor2img = load('basicsr.utils.img_util', 'basicsr/utils/img_util.py').tensor2img
+        load('basicsr.utils.matlab_functions', 'basicsr/utils/matlab_functions.py')
+        load('basicsr.metrics.metric_util', 'basicsr/metrics/metric_util.py')
+        ps = load('basicsr.metrics.psnr_ssim', 'basicsr/metrics/psnr_ssim.py')
+        cases = []
+        for kind, h, w, crop in UM.GOLDEN_CASES:
+            pred, gt = UM.make_pair(kind, 1, 3, h, w)
+            a, b = tensor2img(pred[0].clone()), tensor2img(gt[0].clone())  # (h, w, 3) uint8, BGR; tensor2img clamps a float32 argument in place
+            assert a.dtype == np.uint8 and a.shape == (h, w, 3)
+            case = dict(kind=kind, h=h, w=w, crop_border=crop,
+                        psnr={ych: float(ps.calculate_psnr(a, b, crop, 'HWC', ych)) for ych in (False, True)},
+                        ssim={ych: float(ps.calculate_ssim(a, b, crop, 'HWC', ych)) for ych in (False, True)})
+            if kind == 'ties':  # (k + 0.5) / 255 -> k, exactly
+                k = [torch.from_numpy(np.floor(t.numpy().astype(np.float64) * 255).astype(np.uint8)) for t in (pred, gt)]
+                assert all(torch.equal(torch.from_numpy(UM.ties_from_k(v.numpy())), t) for v, t in zip(k, (pred, gt)))
+                case.update(pred_k=k[0], gt_k=k[1])
+            elif kind == 'const':
+                assert all(bool((t == t.flatten()[0]).all()) for t in (pred, gt))
+                case.update(pred=pred.flatten()[:1].clone().reshape(1, 1, 1, 1), gt=gt.flatten()[:1].clone().reshape(1, 1, 1, 1))
+            else:
+                case.update(pred=pred, gt=gt)
+            cases.append(case)
+        torch.save(dict(cases=cases), os.path.join(OUT, 'metrics_edges.pt'))
+        for case, (kind, h, w, crop) in zip(UM.load_golden(os.path.join(OUT, 'metrics_edges.pt')), UM.GOLDEN_CASES):  # the file gives the inputs back
+            pred, gt = UM.make_pair(kind, 1, 3, h, w)
+            assert torch.equal(case['pred'], pred) and torch.equal(case['gt'], gt), (kind, h, w)
+    finally:
+        for k, m in saved.items():
+            if m is None:
+                sys.modules.pop(k, None)
+            else:
+                sys.modules[k] = m
+
+
 def frame_indices_case():
     """generate_frame_indices of the reference (basicsr/data/data_util.py:35-88), executed from its source text (the module
     itself imports cv2 / lmdb helpers): every centre index of sequences of 7, 10 and 100 frames, 5- and 7-frame windows."""
@@ -619,6 +694,7 @@ def main():
     lr_sched_case()
     psnr_case()
     ssim_case()
+    metrics_edges_case()
     frame_indices_case()
     data_case()
     vimeo_train_case()
