@@ -8,7 +8,7 @@
 // base address and the stride are even (checked on the host: the kernels read and write words).
 // RGB is planar float32 (n, 3, H, W) in [0, 1] for every format or, for 8-bit 4:2:0 alone, interleaved uint8 (n, H, W, 3).
 //
-// Definition (depths and subsamplings: 4.14).  M (3 x 3, RGB in 0 ... 255 -> Y, Cb, Cr without offsets), its inverse Mi and
+// Definition (depths and subsamplings: 4.14; chroma siting: 4.15).  M (3 x 3, RGB in 0 ... 255 -> Y, Cb, Cr without offsets), its inverse Mi and
 // the offsets (yoff, coff, coff) are computed by the caller in float64 for the depth, rounded to float32 and arrive as kernel arguments -
 // no tables.  The kernels see these 12 floats and, in the encode, the largest sample 2^d - 1; nothing else depends on d, so the depth is a
 // RUN-TIME argument and only the sample type (byte | word) is a template parameter.  Every product and every sum below is one float32
@@ -22,10 +22,22 @@
 //           p_k = ((M[k][0] r + M[k][1] g) + M[k][2] b) + off_k;  Y = rint(clamp(p_0, 0, 2^d - 1));
 //           chroma 4:2:0 (k, l) = ((p[2k][2l] + p[2k][2l + 1]) + (p[2k + 1][2l] + p[2k + 1][2l + 1])) * 0.25f, 4:2:2 (p[2l] + p[2l + 1]) * 0.5f,
 //           4:4:4 p; row and column indices clamped to the frame (an odd edge replicates); clamped to [0, 2^d - 1], rounded half to even.
+//   siting  per SUBSAMPLED axis, centre (everything above: chroma sample k lies between luma samples 2k and 2k + 1) or co-sited (on luma
+//           sample 2k): 'left' = co-sited columns (H.264 / HEVC / AV1 4:2:0, every 4:2:2), 'topleft' = co-sited columns and rows (BT.2020).
+//           decode, co-sited axis: even 2k: c[k], odd 2k + 1: 0.5 c[k] + 0.5 c[k + 1] - the two-tap form above with other weights, so the
+//           four weights per axis are RUN-TIME arguments (wv, wh) and every siting runs the same decode instances; centre through them
+//           is the same float32 value (the weights are the same constants).
+//           encode, co-sited axis: [1 2 1] / 4 around luma sample 2k.  Horizontal first, un-normalised: co-sited h[r][l] = (p[r][2l - 1] +
+//           p[r][2l + 1]) + (p[r][2l] + p[r][2l]) (scale 4), centre h[r][l] = p[r][2l] + p[r][2l + 1] (scale 2); then vertical over h:
+//           co-sited (h[2k - 1] + h[2k + 1]) + (h[2k] + h[2k]) (4), centre h[2k] + h[2k + 1] (2), 4:2:2 h[r] (1); then ONE product with the
+//           reciprocal of the scales' product (a power of two), clamp, round.  Indices clamped to the frame.  Both axes centred: the
+//           expression above, bit for bit.  The co-sited axes are template parameters (CX, CY) of the subsampled encode instances.
 //
 // Kernel shape: both kernels move samples and nothing else.  One thread owns 16 columns of one row pair (sy = 1) or of one row (sy = 0),
 // so every luma sample, chroma sample and RGB sample is loaded or stored by exactly one thread (the bilinear decode re-reads the
-// neighbouring chroma rows and one sample left and right of its own through the cache: at 4:2:0, 1/4 of a sample per pixel and plane).
+// neighbouring chroma rows and one sample left and right of its own through the cache: at 4:2:0, 1/4 of a sample per pixel and plane;
+// the co-sited encode recomputes, from RGB read through the cache, Cb / Cr of the column left of its 16 (CX: one scalar pixel per row) and
+// the row above its pair (CY: that row's 16 columns, with the 16-byte loads where RV)).
 // The subsampling is a template parameter (it decides how many rows and chroma samples a thread holds in registers), as are the RGB side
 // (U8; its staging arrays exist in those instances only) and two flags that pick the access width per side, both of which need
 // W % 16 == 0 (every thread's 16 columns are whole): YV - 16-byte plane accesses (two per luma row of words; 8-byte ones for the 8 chroma
@@ -52,9 +64,12 @@ struct YuvArgs {
   float m[9];         // decode: Mi, encode: M (row-major)
   float off[3];       // (yoff, coff, coff)
   float maxv;         // 2^d - 1 (read by the instances with 16-bit samples)
+  // bilinear decode, per axis (v: rows, h: columns): even 2k = w[0] c[k - 1] + w[1] c[k], odd 2k + 1 = w[2] c[k] + w[3] c[k + 1]
+  float wv[4], wh[4];
 };
 
-// (exact in float32 for 16-bit samples and weights 1/4, 3/4 - 16 + 2 + 2 fractional bits after both passes: fused or not, the same value)
+// (exact in float32 for 16-bit samples and weights 0, 1/4, 1/2, 3/4, 1 - 16 + 2 + 2 fractional bits after both passes: fused or not, the
+// same value)
 __device__ __forceinline__ float yuv_mix(float wa, float a, float wb, float b) { return __fadd_rn(__fmul_rn(wa, a), __fmul_rn(wb, b)); }
 // a product rounded on its own: __fmul_rn is a plain `*` to the compiler, and -ffp-contract=fast would fuse it into the add that
 // consumes it; the empty asm keeps the two apart (as accumulate_weighted of ensemble.hip does)
@@ -136,7 +151,7 @@ __device__ __forceinline__ void yuv_pixels4(const YuvArgs &a, const float *ly, c
 #pragma unroll
     for (int p = 0; p < 2; ++p) {
       const float *s = p ? cr : cb;
-      if (SX && BIL) c[p] = (px & 1) ? yuv_mix(0.75f, s[l + 1], 0.25f, s[l + 2]) : yuv_mix(0.25f, s[l], 0.75f, s[l + 1]);
+      if (SX && BIL) c[p] = (px & 1) ? yuv_mix(a.wh[2], s[l + 1], a.wh[3], s[l + 2]) : yuv_mix(a.wh[0], s[l], a.wh[1], s[l + 1]);
       else c[p] = s[l + 1];
     }
     const float d0 = __fsub_rn(ly[px], a.off[0]);
@@ -178,8 +193,8 @@ __global__ __launch_bounds__(256) void yuv_to_rgb_kernel(const YuvArgs a) {
         yuv_load_chroma<T, CW, YV, BIL && SX>(plane + (int64_t)min(rg + 1, Hc - 1) * Wc, c0, Wc, dn);
 #pragma unroll
         for (int j = 0; j < CW + 2; ++j) {
-          cv[p][0][j] = yuv_mix(0.25f, up[j], 0.75f, mid[j]);
-          cv[p][1][j] = yuv_mix(0.75f, mid[j], 0.25f, dn[j]);
+          cv[p][0][j] = yuv_mix(a.wv[0], up[j], a.wv[1], mid[j]);
+          cv[p][1][j] = yuv_mix(a.wv[2], mid[j], a.wv[3], dn[j]);
         }
       } else {
 #pragma unroll
@@ -257,19 +272,29 @@ __device__ __forceinline__ void yuv_ycc4(const YuvArgs &a, float maxv, const flo
   }
 }
 
-// the chroma samples that columns 4 g ... 4 g + 3 of a row group give: the mean over the subsampled axes, p[row][(Y, Cb, Cr)][column]
-template <int SX, int SY>
-__device__ __forceinline__ void yuv_chroma4(float maxv, const float (&p)[1 + SY][3][4], int g, uint32_t (&cq)[2][16 >> SX]) {
+// the chroma samples that columns 4 g ... 4 g + 3 of a row group give: the filter over the subsampled axes (the mean, or [1 2 1] / 4 along
+// a co-sited axis), p[row][(Y, Cb, Cr)][column]; rows 0 and 1 are the group's own, row 2 (CY) the one above it; left[row] = (Cb, Cr) of
+// column 4 g - 1 (read where CX)
+template <int SX, int SY, bool CX, bool CY>
+__device__ __forceinline__ void yuv_chroma4(float maxv, const float (&p)[1 + SY + CY][3][4], const float (&left)[1 + SY + CY][2], int g,
+                                            uint32_t (&cq)[2][16 >> SX]) {
+  constexpr int NR = 1 + SY + CY;
 #pragma unroll
   for (int k = 1; k < 3; ++k) {
-    if constexpr (SX && SY) {
+    if constexpr (SX) {
+      constexpr float inv = 1.f / (float)((CX ? 4 : 2) * (SY ? (CY ? 4 : 2) : 1));
 #pragma unroll
-      for (int l = 0; l < 2; ++l)
-        cq[k - 1][2 * g + l] = yuv_sample(
-            __fmul_rn(__fadd_rn(__fadd_rn(p[0][k][2 * l], p[0][k][2 * l + 1]), __fadd_rn(p[1][k][2 * l], p[1][k][2 * l + 1])), 0.25f), maxv);
-    } else if constexpr (SX) {
+      for (int l = 0; l < 2; ++l) {
+        float h[NR];
 #pragma unroll
-      for (int l = 0; l < 2; ++l) cq[k - 1][2 * g + l] = yuv_sample(__fmul_rn(__fadd_rn(p[0][k][2 * l], p[0][k][2 * l + 1]), 0.5f), maxv);
+        for (int r = 0; r < NR; ++r) {
+          if (CX) h[r] = __fadd_rn(__fadd_rn(l ? p[r][k][1] : left[r][k - 1], p[r][k][2 * l + 1]), __fadd_rn(p[r][k][2 * l], p[r][k][2 * l]));
+          else h[r] = __fadd_rn(p[r][k][2 * l], p[r][k][2 * l + 1]);
+        }
+        float s = h[0];
+        if constexpr (SY) s = CY ? __fadd_rn(__fadd_rn(h[NR - 1], h[1]), __fadd_rn(h[0], h[0])) : __fadd_rn(h[0], h[1]);
+        cq[k - 1][2 * g + l] = yuv_sample(__fmul_rn(s, inv), maxv);
+      }
     } else {
 #pragma unroll
       for (int i = 0; i < 4; ++i) cq[k - 1][4 * g + i] = yuv_sample(p[0][k][i], maxv);
@@ -277,23 +302,49 @@ __device__ __forceinline__ void yuv_chroma4(float maxv, const float (&p)[1 + SY]
   }
 }
 
-template <int SX, int SY, typename T, bool YV, bool RV, bool U8>
+// (Cb, Cr) before quantisation of ONE pixel, from a scalar RGB load: the halo column of a co-sited horizontal axis.  The operations of
+// the kernel's own columns in their order, so that a neighbouring thread's value of the same pixel is the same float.
+template <bool U8>
+__device__ __forceinline__ void yuv_cbcr1(const YuvArgs &a, int img, int y, int x, float (&c)[2]) {
+  float v[3];
+  if constexpr (U8) {
+    const uint8_t *s = static_cast<const uint8_t *>(a.src) + (((int64_t)img * a.H + y) * a.W + x) * 3;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) v[k] = (float)s[k];
+  } else {
+    const float *s = static_cast<const float *>(a.src) + (int64_t)img * a.rgb_stride + (int64_t)y * a.W + x;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) v[k] = __fmul_rn(fminf(fmaxf(s[(int64_t)k * a.H * a.W], 0.f), 1.f), 255.f);
+  }
+#pragma unroll
+  for (int k = 1; k < 3; ++k) c[k - 1] = __fadd_rn(yuv_dot(a.m + 3 * k, v[0], v[1], v[2]), a.off[k]);
+}
+
+// CX / CY: the horizontal / vertical axis is subsampled AND co-sited ([1 2 1] / 4 instead of the mean of two).  CY adds a third row to
+// what a thread reads, the one above its pair (NR rows: R own, which also give luma, then that one); CX one pixel left of its 16 per row.
+template <int SX, int SY, typename T, bool YV, bool RV, bool U8, bool CX, bool CY>
 __global__ __launch_bounds__(256) void rgb_to_yuv_kernel(const YuvArgs a) {
-  constexpr int R = 1 + SY, CW = 16 >> SX;
+  static_assert((!CX || SX) && (!CY || SY), "only a subsampled axis has a siting");
+  constexpr int R = 1 + SY, NR = R + CY, CW = 16 >> SX;
   const int item = blockIdx.x * 256 + threadIdx.x;
   if (item >= a.total) return;
   const int cg = item % a.gw, t = item / a.gw, rg = t % a.hr, img = t / a.hr;
   const int H = a.H, W = a.W, Hc = a.Hc, Wc = a.Wc;
   const int y0 = R * rg, x0 = 16 * cg, c0 = x0 >> SX;
   const bool second = SY && y0 + 1 < H;
-  const int ys[2] = {y0, second ? y0 + 1 : y0};  // an odd last row is its own partner
+  const int ys[3] = {y0, second ? y0 + 1 : y0, max(y0 - 1, 0)};  // an odd last row is its own partner; the row above clamps at row 0
   const float maxv = sizeof(T) == 1 ? 255.f : a.maxv;  // byte samples exist at depth 8 only: a constant clamp folds into one instruction
 
-  uint32_t yq[R][16], cq[2][CW];
-  if constexpr (U8) {
-    uint32_t in[R][12];  // the 48 interleaved bytes of each row
+  uint32_t yq[NR][16], cq[2][CW];  // (yq of the row above is never stored: the compiler drops what computes it)
+  float left[NR][2];
+  if constexpr (CX) {
 #pragma unroll
-    for (int r = 0; r < R; ++r) {
+    for (int r = 0; r < NR; ++r) yuv_cbcr1<U8>(a, img, ys[r], max(x0 - 1, 0), left[r]);
+  }
+  if constexpr (U8) {
+    uint32_t in[NR][12];  // the 48 interleaved bytes of each row
+#pragma unroll
+    for (int r = 0; r < NR; ++r) {
       const uint8_t *row = static_cast<const uint8_t *>(a.src) + ((int64_t)img * H + ys[r]) * W * 3;
       if (RV) {
 #pragma unroll
@@ -315,9 +366,9 @@ __global__ __launch_bounds__(256) void rgb_to_yuv_kernel(const YuvArgs a) {
     }
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
-      float p[R][3][4];  // row, (Y, Cb, Cr), column
+      float p[NR][3][4];  // row, (Y, Cb, Cr), column
 #pragma unroll
-      for (int r = 0; r < R; ++r) {
+      for (int r = 0; r < NR; ++r) {
         float x[3][4];
 #pragma unroll
         for (int i = 0; i < 4; ++i)
@@ -328,15 +379,19 @@ __global__ __launch_bounds__(256) void rgb_to_yuv_kernel(const YuvArgs a) {
           }
         yuv_ycc4(a, maxv, x, p[r], yq[r] + 4 * g);
       }
-      yuv_chroma4<SX, SY>(maxv, p, g, cq);
+      yuv_chroma4<SX, SY, CX, CY>(maxv, p, left, g, cq);
+      if constexpr (CX) {
+#pragma unroll
+        for (int r = 0; r < NR; ++r) left[r][0] = p[r][1][3], left[r][1] = p[r][2][3];
+      }
     }
   } else {
     const float *img_src = static_cast<const float *>(a.src) + (int64_t)img * a.rgb_stride;
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
-      float p[R][3][4];
+      float p[NR][3][4];
 #pragma unroll
-      for (int r = 0; r < R; ++r) {
+      for (int r = 0; r < NR; ++r) {
         float x[3][4];
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
@@ -353,7 +408,11 @@ __global__ __launch_bounds__(256) void rgb_to_yuv_kernel(const YuvArgs a) {
         }
         yuv_ycc4(a, maxv, x, p[r], yq[r] + 4 * g);
       }
-      yuv_chroma4<SX, SY>(maxv, p, g, cq);
+      yuv_chroma4<SX, SY, CX, CY>(maxv, p, left, g, cq);
+      if constexpr (CX) {
+#pragma unroll
+        for (int r = 0; r < NR; ++r) left[r][0] = p[r][1][3], left[r][1] = p[r][2][3];
+      }
     }
   }
 
@@ -372,8 +431,11 @@ static inline bool yuv_aligned(const void *p, uintptr_t a) { return reinterpret_
 // validates, fills the geometry and the two access-width flags; coef: 12 host floats, the matrix row-major, then the offsets.
 // Byte RGB (8-bit 4:2:0 only) is dense: it has no image stride to validate.
 static int yuv_fill(YuvArgs &a, const char *what, const void *yuv, const void *rgb, bool rgb_u8, int n, int H, int W, int sub_x, int sub_y,
-                    int depth, int64_t yuv_stride, int64_t rgb_stride, const float *coef, bool &yv, bool &rv) {
+                    int depth, int64_t yuv_stride, int64_t rgb_stride, const float *coef, int siting_x, int siting_y, bool &yv, bool &rv) {
   EDVR_REQUIRE(yuv && rgb && coef && n > 0 && H > 0 && W > 0, "%s: bad arguments", what);
+  EDVR_REQUIRE((siting_x == 0 || siting_x == 1) && (siting_y == 0 || siting_y == 1),
+               "%s: a siting is 0 (centre) or 1 (co-sited) per axis, got (%d, %d)", what, siting_x, siting_y);
+  EDVR_REQUIRE(siting_y <= siting_x, "%s: co-sited rows go with co-sited columns ('topleft'); (0, 1) is no siting in use", what);
   EDVR_REQUIRE(depth >= 8 && depth <= 16, "%s: a depth of %d bits is outside 8 ... 16", what, depth);
   EDVR_REQUIRE((sub_x == 1 && sub_y == 1) || (sub_x == 1 && sub_y == 0) || (sub_x == 0 && sub_y == 0),
                "%s: chroma subsampling (%d, %d) is none of 4:2:0 (1, 1), 4:2:2 (1, 0), 4:4:4 (0, 0)", what, sub_x, sub_y);
@@ -395,6 +457,9 @@ static int yuv_fill(YuvArgs &a, const char *what, const void *yuv, const void *r
   for (int i = 0; i < 9; ++i) a.m[i] = coef[i];
   for (int i = 0; i < 3; ++i) a.off[i] = coef[9 + i];
   a.maxv = (float)((1 << depth) - 1);
+  // the decode's weights: centre (1/4, 3/4 | 3/4, 1/4), co-sited (0, 1 | 1/2, 1/2); an axis that is not subsampled never reads its four
+  static const float centre[4] = {0.25f, 0.75f, 0.75f, 0.25f}, cosited[4] = {0.f, 1.f, 0.5f, 0.5f};
+  for (int i = 0; i < 4; ++i) a.wv[i] = (siting_y ? cosited : centre)[i], a.wh[i] = (siting_x ? cosited : centre)[i];
   // W % 16 == 0: H W and Hc Wc samples are multiples of 16 and 8, so every plane row starts as aligned as its accesses are wide
   const bool whole = W % 16 == 0;
   yv = whole && yuv_aligned(yuv, 16) && (n == 1 || yuv_stride % 16 == 0);
@@ -411,13 +476,24 @@ static void yuv_decode_launch(bool yv, bool rv, const YuvArgs &a, hipStream_t st
   else hipLaunchKernelGGL((yuv_to_rgb_kernel<SX, SY, T, false, false, BIL, U8>), grid, block, 0, stream, a);
 }
 
-template <int SX, int SY, typename T, bool U8>
+template <int SX, int SY, typename T, bool U8, bool CX, bool CY>
 static void yuv_encode_launch(bool yv, bool rv, const YuvArgs &a, hipStream_t stream) {
   const dim3 grid(cdiv(a.total, 256)), block(256);
-  if (yv && rv) hipLaunchKernelGGL((rgb_to_yuv_kernel<SX, SY, T, true, true, U8>), grid, block, 0, stream, a);
-  else if (yv) hipLaunchKernelGGL((rgb_to_yuv_kernel<SX, SY, T, true, false, U8>), grid, block, 0, stream, a);
-  else if (rv) hipLaunchKernelGGL((rgb_to_yuv_kernel<SX, SY, T, false, true, U8>), grid, block, 0, stream, a);
-  else hipLaunchKernelGGL((rgb_to_yuv_kernel<SX, SY, T, false, false, U8>), grid, block, 0, stream, a);
+  if (yv && rv) hipLaunchKernelGGL((rgb_to_yuv_kernel<SX, SY, T, true, true, U8, CX, CY>), grid, block, 0, stream, a);
+  else if (yv) hipLaunchKernelGGL((rgb_to_yuv_kernel<SX, SY, T, true, false, U8, CX, CY>), grid, block, 0, stream, a);
+  else if (rv) hipLaunchKernelGGL((rgb_to_yuv_kernel<SX, SY, T, false, true, U8, CX, CY>), grid, block, 0, stream, a);
+  else hipLaunchKernelGGL((rgb_to_yuv_kernel<SX, SY, T, false, false, U8, CX, CY>), grid, block, 0, stream, a);
+}
+
+// the siting -> the instance: (centre, centre), 'left' (co-sited columns), 'topleft' (both) where the axis is subsampled; co-sited rows
+// under centred columns is a siting nobody uses and has no instance (the callers refuse it)
+template <int SX, int SY, typename T, bool U8>
+static void yuv_encode_siting(bool cx, bool cy, bool yv, bool rv, const YuvArgs &a, hipStream_t stream) {
+  if constexpr (SX) {
+    if (cx && SY && cy) return yuv_encode_launch<SX, SY, T, U8, true, SY != 0>(yv, rv, a, stream);
+    if (cx) return yuv_encode_launch<SX, SY, T, U8, true, false>(yv, rv, a, stream);
+  }
+  yuv_encode_launch<SX, SY, T, U8, false, false>(yv, rv, a, stream);
 }
 
 // (4:4:4 has nothing to filter: its one decode instance per sample type serves both values of `bilinear`)
@@ -430,10 +506,10 @@ static void yuv_decode_filter(bool bil, bool yv, bool rv, const YuvArgs &a, hipS
 // the format -> the instance.  Byte RGB is instantiated for 8-bit 4:2:0 alone, which yuv_fill has made sure of.
 template <bool U8>
 static int yuv_decode(const char *what, const uint8_t *yuv, void *rgb, int n, int H, int W, int sub_x, int sub_y, int depth, int64_t yuv_stride,
-                      int64_t rgb_stride, const float *coef, int bilinear, edvr_stream_t stream) {
+                      int64_t rgb_stride, const float *coef, int bilinear, int siting_x, int siting_y, edvr_stream_t stream) {
   YuvArgs a;
   bool yv, rv;
-  const int rc = yuv_fill(a, what, yuv, rgb, U8, n, H, W, sub_x, sub_y, depth, yuv_stride, rgb_stride, coef, yv, rv);
+  const int rc = yuv_fill(a, what, yuv, rgb, U8, n, H, W, sub_x, sub_y, depth, yuv_stride, rgb_stride, coef, siting_x, siting_y, yv, rv);
   if (rc != EDVR_OK) return rc;
   a.src = yuv, a.dst = rgb;
   const bool wide = depth > 8, bil = bilinear != 0;
@@ -452,22 +528,22 @@ static int yuv_decode(const char *what, const uint8_t *yuv, void *rgb, int n, in
 
 template <bool U8>
 static int yuv_encode(const char *what, const void *rgb, uint8_t *yuv, int n, int H, int W, int sub_x, int sub_y, int depth, int64_t rgb_stride,
-                      int64_t yuv_stride, const float *coef, edvr_stream_t stream) {
+                      int64_t yuv_stride, const float *coef, int siting_x, int siting_y, edvr_stream_t stream) {
   YuvArgs a;
   bool yv, rv;
-  const int rc = yuv_fill(a, what, yuv, rgb, U8, n, H, W, sub_x, sub_y, depth, yuv_stride, rgb_stride, coef, yv, rv);
+  const int rc = yuv_fill(a, what, yuv, rgb, U8, n, H, W, sub_x, sub_y, depth, yuv_stride, rgb_stride, coef, siting_x, siting_y, yv, rv);
   if (rc != EDVR_OK) return rc;
   a.src = rgb, a.dst = yuv;
-  const bool wide = depth > 8;
+  const bool wide = depth > 8, cx = siting_x != 0, cy = siting_y != 0;
   hipStream_t s = as_stream(stream);
   if constexpr (U8) {
-    yuv_encode_launch<1, 1, uint8_t, true>(yv, rv, a, s);
+    yuv_encode_siting<1, 1, uint8_t, true>(cx, cy, yv, rv, a, s);
   } else if (sub_y) {
-    wide ? yuv_encode_launch<1, 1, uint16_t, false>(yv, rv, a, s) : yuv_encode_launch<1, 1, uint8_t, false>(yv, rv, a, s);
+    wide ? yuv_encode_siting<1, 1, uint16_t, false>(cx, cy, yv, rv, a, s) : yuv_encode_siting<1, 1, uint8_t, false>(cx, cy, yv, rv, a, s);
   } else if (sub_x) {
-    wide ? yuv_encode_launch<1, 0, uint16_t, false>(yv, rv, a, s) : yuv_encode_launch<1, 0, uint8_t, false>(yv, rv, a, s);
+    wide ? yuv_encode_siting<1, 0, uint16_t, false>(cx, cy, yv, rv, a, s) : yuv_encode_siting<1, 0, uint8_t, false>(cx, cy, yv, rv, a, s);
   } else {
-    wide ? yuv_encode_launch<0, 0, uint16_t, false>(yv, rv, a, s) : yuv_encode_launch<0, 0, uint8_t, false>(yv, rv, a, s);
+    wide ? yuv_encode_siting<0, 0, uint16_t, false>(cx, cy, yv, rv, a, s) : yuv_encode_siting<0, 0, uint8_t, false>(cx, cy, yv, rv, a, s);
   }
   return check_launch("rgb_to_yuv_kernel");
 }
@@ -476,30 +552,55 @@ static int yuv_encode(const char *what, const void *rgb, uint8_t *yuv, int n, in
 
 extern "C" int edvr_yuv_to_rgb_f32(const uint8_t *yuv, float *rgb, int n, int H, int W, int sub_x, int sub_y, int depth, int64_t yuv_stride,
                                    int64_t rgb_img_stride, const float *coef, int bilinear, edvr_stream_t stream) {
-  return edvr::yuv_decode<false>("yuv_to_rgb", yuv, rgb, n, H, W, sub_x, sub_y, depth, yuv_stride, rgb_img_stride, coef, bilinear, stream);
+  return edvr::yuv_decode<false>("yuv_to_rgb", yuv, rgb, n, H, W, sub_x, sub_y, depth, yuv_stride, rgb_img_stride, coef, bilinear, 0, 0, stream);
 }
 
 extern "C" int edvr_rgb_to_yuv_f32(const float *rgb, uint8_t *yuv, int n, int H, int W, int sub_x, int sub_y, int depth, int64_t rgb_img_stride,
                                    int64_t yuv_stride, const float *coef, edvr_stream_t stream) {
-  return edvr::yuv_encode<false>("rgb_to_yuv", rgb, yuv, n, H, W, sub_x, sub_y, depth, rgb_img_stride, yuv_stride, coef, stream);
+  return edvr::yuv_encode<false>("rgb_to_yuv", rgb, yuv, n, H, W, sub_x, sub_y, depth, rgb_img_stride, yuv_stride, coef, 0, 0, stream);
 }
 
 extern "C" int edvr_yuv420_to_rgb_f32(const uint8_t *yuv, float *rgb, int n, int H, int W, int64_t yuv_stride, int64_t rgb_img_stride,
                                       const float *coef, int bilinear, edvr_stream_t stream) {
-  return edvr::yuv_decode<false>("yuv420_to_rgb", yuv, rgb, n, H, W, 1, 1, 8, yuv_stride, rgb_img_stride, coef, bilinear, stream);
+  return edvr::yuv_decode<false>("yuv420_to_rgb", yuv, rgb, n, H, W, 1, 1, 8, yuv_stride, rgb_img_stride, coef, bilinear, 0, 0, stream);
 }
 
 extern "C" int edvr_yuv420_to_rgb_u8(const uint8_t *yuv, uint8_t *rgb, int n, int H, int W, int64_t yuv_stride, const float *coef, int bilinear,
                                      edvr_stream_t stream) {
-  return edvr::yuv_decode<true>("yuv420_to_rgb", yuv, rgb, n, H, W, 1, 1, 8, yuv_stride, 0, coef, bilinear, stream);
+  return edvr::yuv_decode<true>("yuv420_to_rgb", yuv, rgb, n, H, W, 1, 1, 8, yuv_stride, 0, coef, bilinear, 0, 0, stream);
 }
 
 extern "C" int edvr_rgb_to_yuv420_f32(const float *rgb, uint8_t *yuv, int n, int H, int W, int64_t rgb_img_stride, int64_t yuv_stride,
                                       const float *coef, edvr_stream_t stream) {
-  return edvr::yuv_encode<false>("rgb_to_yuv420", rgb, yuv, n, H, W, 1, 1, 8, rgb_img_stride, yuv_stride, coef, stream);
+  return edvr::yuv_encode<false>("rgb_to_yuv420", rgb, yuv, n, H, W, 1, 1, 8, rgb_img_stride, yuv_stride, coef, 0, 0, stream);
 }
 
 extern "C" int edvr_rgb_to_yuv420_u8(const uint8_t *rgb, uint8_t *yuv, int n, int H, int W, int64_t yuv_stride, const float *coef,
                                      edvr_stream_t stream) {
-  return edvr::yuv_encode<true>("rgb_to_yuv420", rgb, yuv, n, H, W, 1, 1, 8, 0, yuv_stride, coef, stream);
+  return edvr::yuv_encode<true>("rgb_to_yuv420", rgb, yuv, n, H, W, 1, 1, 8, 0, yuv_stride, coef, 0, 0, stream);
+}
+
+// the same with a chroma siting per axis (0 centre, 1 co-sited): each function above is its sited form at (0, 0)
+extern "C" int edvr_yuv_to_rgb_sited_f32(const uint8_t *yuv, float *rgb, int n, int H, int W, int sub_x, int sub_y, int depth, int64_t yuv_stride,
+                                         int64_t rgb_img_stride, const float *coef, int bilinear, int siting_x, int siting_y,
+                                         edvr_stream_t stream) {
+  return edvr::yuv_decode<false>("yuv_to_rgb", yuv, rgb, n, H, W, sub_x, sub_y, depth, yuv_stride, rgb_img_stride, coef, bilinear, siting_x,
+                                 siting_y, stream);
+}
+
+extern "C" int edvr_rgb_to_yuv_sited_f32(const float *rgb, uint8_t *yuv, int n, int H, int W, int sub_x, int sub_y, int depth,
+                                         int64_t rgb_img_stride, int64_t yuv_stride, const float *coef, int siting_x, int siting_y,
+                                         edvr_stream_t stream) {
+  return edvr::yuv_encode<false>("rgb_to_yuv", rgb, yuv, n, H, W, sub_x, sub_y, depth, rgb_img_stride, yuv_stride, coef, siting_x, siting_y,
+                                 stream);
+}
+
+extern "C" int edvr_yuv420_to_rgb_sited_u8(const uint8_t *yuv, uint8_t *rgb, int n, int H, int W, int64_t yuv_stride, const float *coef,
+                                           int bilinear, int siting_x, int siting_y, edvr_stream_t stream) {
+  return edvr::yuv_decode<true>("yuv420_to_rgb", yuv, rgb, n, H, W, 1, 1, 8, yuv_stride, 0, coef, bilinear, siting_x, siting_y, stream);
+}
+
+extern "C" int edvr_rgb_to_yuv420_sited_u8(const uint8_t *rgb, uint8_t *yuv, int n, int H, int W, int64_t yuv_stride, const float *coef,
+                                           int siting_x, int siting_y, edvr_stream_t stream) {
+  return edvr::yuv_encode<true>("rgb_to_yuv420", rgb, yuv, n, H, W, 1, 1, 8, 0, yuv_stride, coef, siting_x, siting_y, stream);
 }

@@ -1877,10 +1877,22 @@ def lq_crops_from_windows(windows, table, scale, degradation, table_host=None):
 
 
 # ------------------------------------------------------------------------------------------------ planar Y'CbCr <-> RGB (csrc/yuv.hip)
-YUV_MATRICES = {'bt601': (0.299, 0.114), 'bt709': (0.2126, 0.0722)}              # (Kr, Kb)
+# (Kr, Kb).  'bt2020nc' is BT.2020 non-constant luminance under the name ffmpeg's -colorspace gives it; a bare 'bt2020', which does not
+# say which of the standard's two systems is meant, stays an unknown name
+YUV_MATRICES = {'bt601': (0.299, 0.114), 'bt709': (0.2126, 0.0722), 'bt2020nc': (0.2627, 0.0593)}
 YUV_RANGES = {'limited': (219.0, 224.0, 16.0), 'full': (255.0, 255.0, 0.0)}     # luma scale, chroma scale, luma offset (chroma offset 128)
 YUV_SUBSAMPLINGS = {'420': (1, 1), '422': (1, 0), '444': (0, 0)}                    # (sx, sy): log2 of the chroma decimation per axis
 _YUV_ALIASES = {'420jpeg': '420', '420mpeg2': '420', '420paldv': '420'}
+# chroma siting -> (horizontal, vertical): 0 centre, 1 co-sited with the even luma samples; read along subsampled axes only
+YUV_SITINGS = {'center': (0, 0), 'left': (1, 0), 'topleft': (1, 1)}
+
+
+def _yuv_siting(siting, sx, sy):
+    """A siting name -> (cx, cy) for a format of subsampling (sx, sy): an axis that is not subsampled has no siting (0)."""
+    if not isinstance(siting, str) or siting not in YUV_SITINGS:
+        raise ValueError(f'siting must be one of {sorted(YUV_SITINGS)}, got {siting!r}')
+    cx, cy = YUV_SITINGS[siting]
+    return cx & sx, cy & sy
 
 
 def yuv_format(name):
@@ -1974,11 +1986,17 @@ def _yuv_batch(yuv, H, W, fmt, what):
 _YUV420 = (1, 1, 8, '420')  # yuv_format('420')
 
 
-def _yuv_decode(op, yuv, H, W, fmt, matrix, range, chroma, out_dtype):
-    """Both decodes, fmt = yuv_format(name); uint8 RGB (n, H, W, 3) exists for 8-bit 4:2:0 alone, through edvr_yuv420_to_rgb_u8."""
+def _yuv_decode(op, yuv, H, W, fmt, matrix, range, chroma, out_dtype, siting='center'):
+    """Both decodes, fmt = yuv_format(name); uint8 RGB (n, H, W, 3) exists for 8-bit 4:2:0 alone, through edvr_yuv420_to_rgb_u8.  A siting
+    that co-sites an axis the format subsamples goes through the _sited entry points; everything else through the ones it always did."""
     if chroma not in ('bilinear', 'nearest'):
         raise ValueError(f"chroma must be 'bilinear' or 'nearest', got {chroma!r}")
     sx, sy, depth, _ = fmt
+    cx = cy = 0
+    if siting != 'center':  # (the default pays this comparison and nothing else)
+        cx, cy = _yuv_siting(siting, sx, sy)
+        if chroma == 'nearest':
+            cx = cy = 0  # replication has no siting
     _, mi, off = yuv_coeffs(matrix, range, depth)
     require_gpu(yuv, dtypes=(torch.uint8,))
     H, W = int(H), int(W)
@@ -1986,7 +2004,13 @@ def _yuv_decode(op, yuv, H, W, fmt, matrix, range, chroma, out_dtype):
     u8 = out_dtype == torch.uint8
     out = torch.empty((n, H, W, 3) if u8 else (n, 3, H, W), dtype=out_dtype, device=yuv.device)
     coef, bil = _yuv_coef_arg(mi, off), int(chroma == 'bilinear')
-    if u8:
+    if cx and u8:
+        call = lambda: _lib.check(_lib.lib().edvr_yuv420_to_rgb_sited_u8(_ptr(yuv), _ptr(out), n, H, W, stride, coef, bil, cx, cy, _stream()),
+                                  'edvr_yuv420_to_rgb_sited_u8')
+    elif cx:
+        call = lambda: _lib.check(_lib.lib().edvr_yuv_to_rgb_sited_f32(_ptr(yuv), _ptr(out), n, H, W, sx, sy, depth, stride, 3 * H * W, coef, bil, cx, cy,
+                                                                        _stream()), 'edvr_yuv_to_rgb_sited_f32')
+    elif u8:
         call = lambda: _lib.check(_lib.lib().edvr_yuv420_to_rgb_u8(_ptr(yuv), _ptr(out), n, H, W, stride, coef, bil, _stream()), 'edvr_yuv420_to_rgb_u8')
     else:
         call = lambda: _lib.check(_lib.lib().edvr_yuv_to_rgb_f32(_ptr(yuv), _ptr(out), n, H, W, sx, sy, depth, stride, 3 * H * W, coef, bil, _stream()),
@@ -1995,25 +2019,29 @@ def _yuv_decode(op, yuv, H, W, fmt, matrix, range, chroma, out_dtype):
     return out
 
 
-def yuv420_to_rgb(yuv, H, W, matrix='bt601', range='limited', chroma='bilinear', out_dtype=torch.float32):
+def yuv420_to_rgb(yuv, H, W, matrix='bt601', range='limited', chroma='bilinear', out_dtype=torch.float32, siting='center'):
     """8-bit I420 frames -> RGB in ONE launch.  yuv: uint8 (n, >= framesize) on the GPU with stride(1) == 1 and ANY row stride and base
     offset - each row starts with the H W luma bytes, then the (ceil(H / 2), ceil(W / 2)) Cb and Cr planes, i.e. the payload of a Y4M
-    frame (`buf[:, 6:]` of a Y4MReader buffer works as it is).  matrix 'bt601' | 'bt709', range 'limited' | 'full' (`yuv_coeffs`), chroma
-    'bilinear' (centre-sited 1/4 - 3/4 filter, vertical then horizontal, indices clamped) | 'nearest'.  Returns float32 (n, 3, H, W) in
-    [0, 1] or uint8 (n, H, W, 3); the definition, operation by operation, is DESIGN 4.11.  ValueError for bad names and layouts."""
+    frame (`buf[:, 6:]` of a Y4MReader buffer works as it is).  matrix: a name of YUV_MATRICES, range 'limited' | 'full' (`yuv_coeffs`), chroma
+    'bilinear' (the two-tap filter of the siting, vertical then horizontal, indices clamped) | 'nearest'.  siting (YUV_SITINGS, DESIGN
+    4.15): where the chroma samples lie - 'center' (JPEG / MPEG-1: the 1/4 - 3/4 filter), 'left' (H.264 / HEVC / AV1: co-sited with the even
+    luma columns - even columns take c[k], odd ones 0.5 c[k] + 0.5 c[k + 1]), 'topleft' (BT.2020 / UHD: rows likewise); 'nearest' ignores
+    it.  Returns float32 (n, 3, H, W) in [0, 1] or uint8 (n, H, W, 3); the definition, operation by operation, is DESIGN 4.11.  ValueError
+    for bad names and layouts."""
     if out_dtype not in (torch.float32, torch.uint8):
         raise ValueError(f'out_dtype must be torch.float32 or torch.uint8, got {out_dtype}')
-    return _yuv_decode('yuv420_to_rgb', yuv, H, W, _YUV420, matrix, range, chroma, out_dtype)
+    return _yuv_decode('yuv420_to_rgb', yuv, H, W, _YUV420, matrix, range, chroma, out_dtype, siting)
 
 
-def yuv_to_rgb(yuv, H, W, fmt='420', matrix='bt601', range='limited', chroma='bilinear'):
+def yuv_to_rgb(yuv, H, W, fmt='420', matrix='bt601', range='limited', chroma='bilinear', siting='center'):
     """Planar Y'CbCr frames of any Y4M format -> float32 RGB (n, 3, H, W) in [0, 1], in ONE launch.  fmt: `yuv_format` - 4:2:0, 4:2:2 or
     4:4:4 at 8 ... 16 bits.  yuv: uint8 (n, >= yuv_frame_size(H, W, fmt)) on the GPU with stride(1) == 1 and any row stride and base
     offset (`buf[:, 6:]` of a Y4MReader buffer works as it is); above 8 bits a sample is a little-endian 16-bit word, whose bits above
     the depth are NOT masked, and the base address and row stride are even.  matrix, range: `yuv_coeffs` at the format's depth; chroma:
-    'bilinear' (the centre-sited 1/4 - 3/4 filter along each subsampled axis, vertical then horizontal, indices clamped) | 'nearest'.
-    The definition is DESIGN 4.14; at '420' it is that of yuv420_to_rgb, bit for bit.  ValueError for bad names and layouts."""
-    return _yuv_decode('yuv_to_rgb', yuv, H, W, yuv_format(fmt), matrix, range, chroma, torch.float32)
+    'bilinear' (the two-tap filter of the siting along each subsampled axis, vertical then horizontal, indices clamped) | 'nearest'.
+    siting: as yuv420_to_rgb takes it, per SUBSAMPLED axis - 'topleft' on 4:2:2 is 'left', any siting on 4:4:4 changes nothing.
+    The definition is DESIGN 4.14 (siting: 4.15); at '420' it is that of yuv420_to_rgb, bit for bit.  ValueError for bad names and layouts."""
+    return _yuv_decode('yuv_to_rgb', yuv, H, W, yuv_format(fmt), matrix, range, chroma, torch.float32, siting)
 
 
 def _byte_span(t):
@@ -2024,9 +2052,13 @@ def _byte_span(t):
     return t.data_ptr(), t.data_ptr() + (last + 1) * t.element_size()
 
 
-def _yuv_encode(op, rgb, fmt, matrix, range, out, u8_too):
-    """Both encodes, fmt = yuv_format(name); uint8 RGB (n, H, W, 3) is read for 8-bit 4:2:0 alone (`u8_too`), through edvr_rgb_to_yuv420_u8."""
+def _yuv_encode(op, rgb, fmt, matrix, range, out, u8_too, siting='center'):
+    """Both encodes, fmt = yuv_format(name); uint8 RGB (n, H, W, 3) is read for 8-bit 4:2:0 alone (`u8_too`), through edvr_rgb_to_yuv420_u8.
+    A siting that co-sites an axis the format subsamples goes through the _sited entry points."""
     sx, sy, depth, _ = fmt
+    cx = cy = 0
+    if siting != 'center':
+        cx, cy = _yuv_siting(siting, sx, sy)
     m, _, off = yuv_coeffs(matrix, range, depth)
     if not rgb.is_cuda:
         raise NotImplementedError('edvr_amd ops run on the GPU only (HIP/gfx950); got a CPU tensor')
@@ -2053,7 +2085,13 @@ def _yuv_encode(op, rgb, fmt, matrix, range, out, u8_too):
     if a0 < b1 and b0 < a1:
         raise ValueError('out overlaps the input')
     coef = _yuv_coef_arg(m, off)
-    if u8:
+    if cx and u8:
+        call = lambda: _lib.check(_lib.lib().edvr_rgb_to_yuv420_sited_u8(_ptr(rgb), _ptr(out), n, H, W, stride, coef, cx, cy, _stream()),
+                                  'edvr_rgb_to_yuv420_sited_u8')
+    elif cx:
+        call = lambda: _lib.check(_lib.lib().edvr_rgb_to_yuv_sited_f32(_ptr(rgb), _ptr(out), n, H, W, sx, sy, depth, _img_stride(rgb), stride, coef, cx, cy,
+                                                                        _stream()), 'edvr_rgb_to_yuv_sited_f32')
+    elif u8:
         call = lambda: _lib.check(_lib.lib().edvr_rgb_to_yuv420_u8(_ptr(rgb), _ptr(out), n, H, W, stride, coef, _stream()), 'edvr_rgb_to_yuv420_u8')
     else:
         call = lambda: _lib.check(_lib.lib().edvr_rgb_to_yuv_f32(_ptr(rgb), _ptr(out), n, H, W, sx, sy, depth, _img_stride(rgb), stride, coef, _stream()),
@@ -2062,26 +2100,28 @@ def _yuv_encode(op, rgb, fmt, matrix, range, out, u8_too):
     return out
 
 
-def rgb_to_yuv420(rgb, matrix='bt601', range='limited', out=None):
+def rgb_to_yuv420(rgb, matrix='bt601', range='limited', out=None, siting='center'):
     """RGB frames -> 8-bit I420 in ONE launch: rgb float32 (n, 3, H, W) (clamped to [0, 1], x 255, NOT rounded before the matrix: the
     only quantisation is the one to YUV bytes; dense images, a slice of a longer video works) or uint8 (n, H, W, 3).  Returns uint8
     (n, framesize), framesize = yuv420_frame_size(H, W): luma, then Cb and Cr, each the mean of its 2 x 2 block (an odd edge replicates).
     out: a uint8 (n, >= framesize) batch to write into instead, stride(1) == 1, any row stride and base offset (`buf[:, 6:]` of a Y4M
-    write buffer); bytes past a frame's end are left alone and `out` is returned.  ValueError for bad names, layouts and an `out` that
-    overlaps the input."""
-    return _yuv_encode('rgb_to_yuv420', rgb, _YUV420, matrix, range, out, True)
+    write buffer); bytes past a frame's end are left alone and `out` is returned.  siting (YUV_SITINGS): where the chroma
+    samples are to lie - 'center' (the mean above), 'left' ([1 2 1] / 4 over the columns around the even one, the mean of the two rows),
+    'topleft' ([1 2 1] / 4 along both axes, around the even row and column); indices clamped to the frame.  ValueError for bad names,
+    layouts and an `out` that overlaps the input."""
+    return _yuv_encode('rgb_to_yuv420', rgb, _YUV420, matrix, range, out, True, siting)
 
 
-def rgb_to_yuv(rgb, fmt='420', matrix='bt601', range='limited', out=None):
+def rgb_to_yuv(rgb, fmt='420', matrix='bt601', range='limited', out=None, siting='center'):
     """float32 RGB (n, 3, H, W) -> planar Y'CbCr frames of any Y4M format in ONE launch (clamped to [0, 1], x 255, NOT rounded before
     the matrix: the only quantisation is the one to samples of the format's depth; dense images, a slice of a longer video works).
     Returns uint8 (n, yuv_frame_size(H, W, fmt)): luma, then Cb and Cr - the mean of a 2 x 2 block (4:2:0) or of a pair of columns
     (4:2:2), an odd edge replicating, or the sample itself (4:4:4) - clamped to [0, 2^depth - 1] and rounded half to even, a byte or a
     little-endian 16-bit word each.  out: a uint8 (n, >= framesize) batch to write into instead, stride(1) == 1, any row stride and base
     offset (even ones above 8 bits; `buf[:, 6:]` of a Y4M write buffer); bytes past a frame's end are left alone and `out` is returned.
-    uint8 RGB stays with rgb_to_yuv420.  The definition is DESIGN 4.14.  ValueError for bad names, layouts and an `out` that overlaps
-    the input."""
-    return _yuv_encode('rgb_to_yuv', rgb, yuv_format(fmt), matrix, range, out, False)
+    uint8 RGB stays with rgb_to_yuv420.  siting: as rgb_to_yuv420 takes it, per SUBSAMPLED axis ('topleft' on 4:2:2 is 'left', 4:4:4 has
+    none).  The definition is DESIGN 4.14 (siting: 4.15).  ValueError for bad names, layouts and an `out` that overlaps the input."""
+    return _yuv_encode('rgb_to_yuv', rgb, yuv_format(fmt), matrix, range, out, False, siting)
 
 
 # ------------------------------------------------------------------------------------------------ scene cuts

@@ -19,6 +19,9 @@ from . import ops
 MAGIC = b'YUV4MPEG2'
 FRAME = b'FRAME\n'
 CHROMA_420 = ('420jpeg', '420mpeg2', '420paldv', '420')
+# the chroma siting (ops.YUV_SITINGS) the three 8-bit 4:2:0 tags stand for, as muxers pair them with chroma locations; no other tag says
+SITING_OF_TAG = {'420jpeg': 'center', '420mpeg2': 'left', '420paldv': 'topleft'}
+TAG_OF_SITING = {v: k for k, v in SITING_OF_TAG.items()}
 # every format ops.yuv_to_rgb / ops.rgb_to_yuv convert, by its canonical name: '420', '420p9' ... '420p16', '422' ..., '444' ... '444p16'
 ALL_FORMATS = tuple(base + (f'p{d}' if d > 8 else '') for base in ('420', '422', '444') for d in range(8, 17))
 
@@ -43,16 +46,20 @@ class Y4MReader:
     formats: None - 8-bit 4:2:0 only, the format ops.yuv420_to_rgb reads - or a collection of format names (`ops.yuv_format`), such as
     ALL_FORMATS: 4:2:0, 4:2:2 and 4:4:4 at 8 ... 16 bits, which ops.yuv_to_rgb reads.
 
-    Accepted: C420jpeg, C420mpeg2, C420paldv, C420 and no C tag - ALL treated as centre-sited chroma (the 'bilinear' filter of
-    ops.yuv420_to_rgb; the left-sited filter of mpeg2 / the co-sited rows of paldv are not implemented, the difference is a quarter-sample
-    chroma shift); with `formats`, also those of C422, C444 and C420p9 ... C444p16 that it names; Ip, I? and no I tag;
+    Accepted: C420jpeg, C420mpeg2, C420paldv, C420 and no C tag - the same planes, whose tag names the chroma siting (`siting` below;
+    the reader only reports it, `restore_y4m(siting_in='auto')` and the siting argument of the ops use it); with `formats`, also those of
+    C422, C444 and C420p9 ... C444p16 that it names; Ip, I? and no I tag;
     XCOLORRANGE=FULL | LIMITED (no tag: limited).  ValueError: a bad magic, a missing or non-positive W / H, interlaced video (It, Ib,
     Im), a format that `formats` does not name (without it: C422, C444 and every high-bit-depth format), Cmono / C411 / C440 / C444alpha
     and depths outside 8 ... 16 always, a frame line that is not `FRAME`, and a truncated frame (the message names the frame index).
 
     width, height, fps ('30000:1001' as written, or None), aspect (likewise), range ('limited' | 'full'), chroma (the tag's value or
     None), format (the canonical name: '420', '422p10' ...), depth, subsampling ((sx, sy): log2 of the chroma decimation per axis),
-    framesize (bytes, by the format); `frames_read` counts what read() returned so far."""
+    framesize (bytes, by the format); `frames_read` counts what read() returned so far.
+    siting: what the tag says about where the chroma samples lie (ops.YUV_SITINGS) - 'center' for C420jpeg, 'left' for
+    C420mpeg2, 'topleft' for C420paldv, None where the tag says nothing: C420, no tag, every C422 / C444 and every p9 ... p16 tag.
+    (C420paldv is read as top-left co-sited chroma, which is how muxers use the tag for that chroma location; true PAL-DV siting, with Cb
+    and Cr on alternate lines, is not implemented.)"""
 
     def __init__(self, stream, formats=None):
         self.stream = stream
@@ -97,6 +104,7 @@ class Y4MReader:
             if self.format not in accepted:
                 raise ValueError(f'C{self.chroma} is not among the accepted formats ({", ".join(sorted(accepted))})')
         self.subsampling = (sx, sy)
+        self.siting = SITING_OF_TAG.get(self.chroma)
         self.framesize = ops.yuv_frame_size(self.height, self.width, self.format)
         self.frames_read = 0
 
@@ -148,19 +156,24 @@ class Y4MWriter:
     """Writes progressive YUV4MPEG2: the header on construction (`Ip`, `C420jpeg` for format '420' and `C<canonical name>` for any
     other of `ops.yuv_format`, F / A as given - strings such as '30000:1001', omitted when None - and XCOLORRANGE=FULL for range
     'full'), then `write(buf)` for every uint8 host buffer (k, 6 + framesize) whose rows already begin with `FRAME\\n` - the bytes go
-    out as they are, in one write."""
+    out as they are, in one write.  siting (ops.YUV_SITINGS): for 8-bit 4:2:0 the tag is `C420jpeg` ('center', the default),
+    `C420mpeg2` ('left') or `C420paldv` ('topleft'); the tags of every other format cannot carry a siting - it is checked and otherwise
+    ignored, and whoever encodes such a stream says it there (ffmpeg: `-chroma_sample_location left` / `topleft` on the output side)."""
 
-    def __init__(self, stream, W, H, fps=None, aspect=None, range='limited', format='420'):
+    def __init__(self, stream, W, H, fps=None, aspect=None, range='limited', format='420', siting='center'):
         if range not in ops.YUV_RANGES:
             raise ValueError(f'range must be one of {sorted(ops.YUV_RANGES)}, got {range!r}')
+        if siting not in TAG_OF_SITING:
+            raise ValueError(f'siting must be one of {sorted(TAG_OF_SITING)}, got {siting!r}')
         if int(W) < 1 or int(H) < 1:
             raise ValueError(f'a frame has at least one row and column, got {H} x {W}')
         self.stream, self.width, self.height, self.range = stream, int(W), int(H), range
         self.format = ops.yuv_format(format)[3]
+        self.siting = siting
         self.framesize = ops.yuv_frame_size(self.height, self.width, self.format)
         self.frames_written = 0
         head = [MAGIC.decode(), f'W{self.width}', f'H{self.height}'] + ([f'F{fps}'] if fps else []) + ['Ip'] + ([f'A{aspect}'] if aspect else [])
-        head += ['C420jpeg' if self.format == '420' else 'C' + self.format] + (['XCOLORRANGE=FULL'] if range == 'full' else [])
+        head += ['C' + TAG_OF_SITING[siting] if self.format == '420' else 'C' + self.format] + (['XCOLORRANGE=FULL'] if range == 'full' else [])
         stream.write((' '.join(head) + '\n').encode('ascii'))
 
     def write(self, buf):
@@ -176,8 +189,18 @@ class Y4MWriter:
         self.frames_written += buf.shape[0]
 
 
+def resolve_siting(siting, reader):
+    """A siting argument -> a name of ops.YUV_SITINGS: 'auto' is what the reader's tag says (`Y4MReader.siting`) or, where the tag is
+    silent, 'left' - the default chroma location of H.264, HEVC and AV1 4:2:0 and the siting of every 4:2:2."""
+    if siting == 'auto':
+        return reader.siting or 'left'
+    if siting not in ops.YUV_SITINGS:
+        raise ValueError(f"siting must be 'auto' or one of {sorted(ops.YUV_SITINGS)}, got {siting!r}")
+    return siting
+
+
 def restore_y4m(net, src, dst, *, matrix_in=None, matrix_out=None, chroma='bilinear', read_frames=8, on_chunk=None, stats=None, out_format=None,
-                **restorer_kwargs):
+                siting_in='center', siting_out=None, **restorer_kwargs):
     """Restore a Y4M stream with `net` (an EDVR in eval mode, on the GPU) into a Y4M stream; returns the number of frames.  Call it under
     torch.no_grad().
 
@@ -186,7 +209,7 @@ def restore_y4m(net, src, dst, *, matrix_in=None, matrix_out=None, chroma='bilin
             -> ops.rgb_to_yuv420(chunk, out=buf[:, 6:]) -> one copy into pinned memory -> dst (a binary stream)
 
     The frames never exist as RGB bytes and the network's float32 result is quantised once, to YUV bytes.  matrix_in / matrix_out:
-    'bt601' | 'bt709'; None follows `default_matrix` for that side's OWN frame size - a 180 x 320 input is read as BT.601 and its 720 x 1280
+    a name of ops.YUV_MATRICES ('bt601' | 'bt709' | 'bt2020nc'); None follows `default_matrix` for that side's OWN frame size - a 180 x 320 input is read as BT.601 and its 720 x 1280
     result written as BT.709, because that is how it will be played.  The range (XCOLORRANGE) is copied from the input, F and A likewise;
     the output is s W x s H, s = 4 (1 for an hr_in network).  chroma: the upsampling filter of the decode.  restorer_kwargs: chunk,
     pad_mode, tile, tile_overlap, tile_blend, self_ensemble, time_reverse, ... as VideoRestorer takes them - sizes that are no multiple
@@ -201,7 +224,12 @@ def restore_y4m(net, src, dst, *, matrix_in=None, matrix_out=None, chroma='bilin
     Formats: a raw stream is opened with ALL_FORMATS - 4:2:0, 4:2:2 and 4:4:4 at 8 ... 16 bits.  out_format: None writes the
     input's format, a name of `ops.yuv_format` that one: `out_format='420p10'` (or '444p10') on 8-bit input quantises the network's
     float32 result once, to 10 bits, instead of banding it at 8.  8-bit 4:2:0 in and out goes through ops.yuv420_to_rgb / rgb_to_yuv420
-    as above, everything else through ops.yuv_to_rgb(buf[:, 6:], H, W, format, ...) / ops.rgb_to_yuv(chunk, format, ..., out=buf[:, 6:])."""
+    as above, everything else through ops.yuv_to_rgb(buf[:, 6:], H, W, format, ...) / ops.rgb_to_yuv(chunk, format, ..., out=buf[:, 6:]).
+    Chroma siting: siting_in - 'center' (the default: what this function always did), 'left', 'topleft', or 'auto': the
+    reader's tag (`Y4MReader.siting`) and 'left' where the tag is silent, which is right for nearly all H.264 / HEVC / AV1 footage -
+    decoding left-sited chroma as centred shifts the colour by half an input pixel, two output pixels.  siting_out: the siting the output
+    is encoded for and, for 8-bit 4:2:0, tagged with (Y4MWriter); None - the resolved input siting.  The transfer function is never
+    touched.  With both sitings 'center' the calls are the ones made before the argument existed."""
     from .video import VideoRestorer
     reader = src if isinstance(src, Y4MReader) else Y4MReader(src, formats=ALL_FORMATS)
     fmt_in = reader.format
@@ -214,13 +242,18 @@ def restore_y4m(net, src, dst, *, matrix_in=None, matrix_out=None, chroma='bilin
             raise ValueError(f'matrix must be one of {sorted(ops.YUV_MATRICES)}, got {name!r}')
     if chroma not in ('bilinear', 'nearest'):
         raise ValueError(f"chroma must be 'bilinear' or 'nearest', got {chroma!r}")
+    siting_in = resolve_siting(siting_in, reader)
+    siting_out = siting_in if siting_out is None else resolve_siting(siting_out, reader)
+    # (no keyword at 'center': the calls of every caller and stand-in that predates the argument)
+    kw_in = {} if siting_in == 'center' else {'siting': siting_in}
+    kw_out = {} if siting_out == 'center' else {'siting': siting_out}
     vr = VideoRestorer(net, out_dtype=torch.float32, **restorer_kwargs)
     device = next(net.parameters()).device
     H, W = reader.height, reader.width
     Ho, Wo = vr.scale * H, vr.scale * W
     matrix_in = matrix_in or default_matrix(H, W)
     matrix_out = matrix_out or default_matrix(Ho, Wo)
-    writer = Y4MWriter(dst, Wo, Ho, reader.fps, reader.aspect, reader.range, fmt_out)
+    writer = Y4MWriter(dst, Wo, Ho, reader.fps, reader.aspect, reader.range, fmt_out, siting_out)
     row = len(FRAME) + writer.framesize
     marks = torch.tensor(list(FRAME), dtype=torch.uint8).to(device)
 
@@ -231,9 +264,9 @@ def restore_y4m(net, src, dst, *, matrix_in=None, matrix_out=None, chroma='bilin
                 return
             yuv = host.to(device, non_blocking=True)[:, len(FRAME):]
             if plain420:
-                yield ops.yuv420_to_rgb(yuv, H, W, matrix_in, reader.range, chroma)
+                yield ops.yuv420_to_rgb(yuv, H, W, matrix_in, reader.range, chroma, **kw_in)
             else:
-                yield ops.yuv_to_rgb(yuv, H, W, fmt_in, matrix_in, reader.range, chroma)
+                yield ops.yuv_to_rgb(yuv, H, W, fmt_in, matrix_in, reader.range, chroma, **kw_in)
 
     pending = None  # (pinned buffer, event after its copy) of the chunk before this one
 
@@ -249,9 +282,9 @@ def restore_y4m(net, src, dst, *, matrix_in=None, matrix_out=None, chroma='bilin
         if on_chunk is not None:
             on_chunk(out)
         if plain420:
-            ops.rgb_to_yuv420(out, matrix_out, reader.range, out=buf[:, len(FRAME):])
+            ops.rgb_to_yuv420(out, matrix_out, reader.range, out=buf[:, len(FRAME):], **kw_out)
         else:
-            ops.rgb_to_yuv(out, fmt_out, matrix_out, reader.range, out=buf[:, len(FRAME):])
+            ops.rgb_to_yuv(out, fmt_out, matrix_out, reader.range, out=buf[:, len(FRAME):], **kw_out)
         host = _host_buffer(tuple(buf.shape))
         host.copy_(buf, non_blocking=True)
         done = None

@@ -724,6 +724,24 @@ int edvr_yuv_to_rgb_f32(const uint8_t *yuv, float *rgb, int n, int H, int W, int
 int edvr_rgb_to_yuv_f32(const float *rgb, uint8_t *yuv, int n, int H, int W, int sub_x, int sub_y, int depth, int64_t rgb_img_stride,
                         int64_t yuv_stride, const float *coef, edvr_stream_t stream);
 
+/* The same conversions with a chroma siting per axis (definition: DESIGN 4.15): siting_x / siting_y = 0 centre (chroma sample k lies
+ * between luma samples 2k and 2k + 1: JPEG / MPEG-1, and what the functions above compute - each of them is its _sited form at (0, 0)) or
+ * 1 co-sited (sample k lies ON luma sample 2k).  (1, 0) is 'left' - H.264 / HEVC / AV1 4:2:0 by default, every 4:2:2; (1, 1) is 'topleft' -
+ * BT.2020 / UHD.  An axis that is not subsampled ignores its value, and so does a decode with bilinear == 0.
+ * Decode, co-sited axis: even 2k takes c[k], odd 2k + 1 takes 0.5 c[k] + 0.5 c[k + 1] (vertical, then horizontal, indices clamped).
+ * Encode, co-sited axis: [1 2 1] / 4 around luma sample 2k over the values p before quantisation - horizontally (p[2l - 1] + p[2l + 1]) +
+ * (p[2l] + p[2l]) (a centred axis: p[2l] + p[2l + 1]), then the same over those sums vertically, then one product with the reciprocal of
+ * the weights' sum; indices clamped to the frame.  The horizontal halo column and the row above a row pair are recomputed from RGB.
+ * EDVR_ERR_ARG as above, and for a siting other than 0 / 1 or (0, 1) (co-sited rows under centred columns: no standard's siting). */
+int edvr_yuv_to_rgb_sited_f32(const uint8_t *yuv, float *rgb, int n, int H, int W, int sub_x, int sub_y, int depth, int64_t yuv_stride,
+                              int64_t rgb_img_stride, const float *coef, int bilinear, int siting_x, int siting_y, edvr_stream_t stream);
+int edvr_rgb_to_yuv_sited_f32(const float *rgb, uint8_t *yuv, int n, int H, int W, int sub_x, int sub_y, int depth, int64_t rgb_img_stride,
+                              int64_t yuv_stride, const float *coef, int siting_x, int siting_y, edvr_stream_t stream);
+int edvr_yuv420_to_rgb_sited_u8(const uint8_t *yuv, uint8_t *rgb, int n, int H, int W, int64_t yuv_stride, const float *coef, int bilinear,
+                                int siting_x, int siting_y, edvr_stream_t stream);
+int edvr_rgb_to_yuv420_sited_u8(const uint8_t *rgb, uint8_t *yuv, int n, int H, int W, int64_t yuv_stride, const float *coef, int siting_x,
+                                int siting_y, edvr_stream_t stream);
+
 /* Frame-to-frame change for scene-cut detection (csrc/shots.hip; definition: DESIGN 4.13).  The bytes R, G, B of a pixel are the input's
  * own (_u8: x (n, H, W, 3)) or its tensor2img bytes (_f32: x (n, 3, H, W); clamp to [0, 1], x 255, round half to even, NaN -> 0); in
  * integers Y8 = ((66 R + 129 G + 25 B + 128) >> 8) + 16, and

@@ -16,10 +16,16 @@
       entry points.  Printed, and written where --out names a file: profiles/yuv/bench_yuv_formats.json is the record of the commit that
       still had a kernel file per operator pair and is not overwritten by default.
 
-Only public ops calls that every revision with both operator pairs has, so the same file times an older tree for a comparison.
+  (e) with --siting, INSTEAD of (a) - (d): ops.yuv_to_rgb (bilinear chroma) and ops.rgb_to_yuv under every chroma siting ('center',
+      'left', 'topleft') for '420', '420p10' and '422p10' at the shapes of (d), timed as (a), each siting's time beside
+      'center' of the same process.  Written to profiles/yuv/bench_yuv_siting.json by default.
+
+Legs (a) - (d): only public ops calls that every revision with both operator pairs has, so the same file times an older tree for a
+comparison.
 
     python scripts/bench_yuv.py [--out profiles/yuv/bench_yuv.json] [--skip-video]
     python scripts/bench_yuv.py --formats [--out FILE]
+    python scripts/bench_yuv.py --siting [--out profiles/yuv/bench_yuv_siting.json]
     python scripts/bench_yuv.py ... --tree DIR     the package of another checkout (built), for scripts/bench_yuv_compare.py
 """
 import argparse
@@ -182,6 +188,39 @@ def format_rows(args, dev):
     return rows
 
 
+SITING_FORMATS = ['420', '420p10', '422p10']
+SITINGS = ['center', 'left', 'topleft']
+
+
+def siting_rows(args, dev):
+    """Leg (e): one row per shape, format and siting through ops.yuv_to_rgb / ops.rgb_to_yuv; `*_over_center` is the ratio to the
+    'center' row of the same shape and format ('topleft' on 4:2:2 is 'left': the same launch, timed again)."""
+    from edvr_amd import ops
+    rows = []
+    for name, n, (H, W) in FORMAT_CASES:
+        rgb = torch.rand((n, 3, H, W), generator=torch.Generator().manual_seed(0)).to(dev)
+        for fmt in SITING_FORMATS:
+            fs = ops.yuv_frame_size(H, W, fmt)
+            nbytes = n * (fs + 12 * H * W)
+            frames = ops.rgb_to_yuv(rgb, fmt, 'bt709', 'limited')
+            base = {}
+            for siting in SITINGS:
+                row = dict(case=name, frames=n, size=[H, W], format=fmt, siting=siting, bytes_moved=nbytes)
+                arms = {'decode': lambda: ops.yuv_to_rgb(frames, H, W, fmt, 'bt709', 'limited', 'bilinear', siting),
+                        'encode': lambda: ops.rgb_to_yuv(rgb, fmt, 'bt709', 'limited', out=frames, siting=siting)}
+                for arm, fn in arms.items():
+                    first, second = timed(fn, args.warmup, args.iters), timed(fn, 5, args.iters)  # twice: the first ran on a colder device
+                    med = min(first[0], second[0])
+                    row[arm + '_us'] = round(med, 2)
+                    row[arm + '_us_runs'] = [round(first[0], 2), round(second[0], 2)]
+                    row[arm + '_hbm_fraction'] = round(nbytes / (med * 1e-6) / (HBM_TBS * 1e12), 4)
+                    base.setdefault(arm, med)
+                    row[arm + '_over_center'] = round(med / base[arm], 4)
+                rows.append(row)
+                print(json.dumps(row), flush=True)
+    return rows
+
+
 def video_row(args, dev):
     """restore_y4m against VideoRestorer.restore on resident frames: 100 frames of 180 x 320, EDVR-L, chunk 10."""
     from edvr_amd import EDVR, VideoRestorer, ops
@@ -234,6 +273,7 @@ def main():
     ap.add_argument('--out', default=None, help='default: profiles/yuv/bench_yuv.json; with --formats none, the rows are only printed')
     ap.add_argument('--tree', default=os.path.join(HERE, '..'), help='the checkout whose edvr_amd package is timed (default: this one)')
     ap.add_argument('--formats', action='store_true', help='leg (d) alone: the operators that take a format beside the 8-bit 4:2:0 operators')
+    ap.add_argument('--siting', action='store_true', help='leg (e) alone: decode and encode under every chroma siting')
     ap.add_argument('--warmup', type=int, default=20)
     ap.add_argument('--iters', type=int, default=200)
     ap.add_argument('--video-frames', type=int, default=100)
@@ -241,7 +281,7 @@ def main():
     ap.add_argument('--head', default=None, help='commit to record where the tree is not a git checkout (default: git rev-parse HEAD)')
     args = ap.parse_args()
     if args.out is None and not args.formats:
-        args.out = os.path.join(HERE, '..', 'profiles', 'yuv', 'bench_yuv.json')
+        args.out = os.path.join(HERE, '..', 'profiles', 'yuv', 'bench_yuv_siting.json' if args.siting else 'bench_yuv.json')
     sys.path.insert(0, os.path.abspath(args.tree))
     assert args.iters >= 20, 'the median of at least 20 calls'
     assert torch.cuda.is_available(), 'bench_yuv needs the GPU: there is no CPU path to time'
@@ -250,11 +290,13 @@ def main():
     dev = torch.device('cuda:0')
     record = dict(bench='bench_yuv', lib=_lib.lib().edvr_version().decode(), source_hash=source_hash(), git_head=args.head or git_head(os.path.abspath(args.tree)),
                   device=torch.cuda.get_device_name(0), hbm_tbs=HBM_TBS, warmup=args.warmup, iters=args.iters)
-    if args.formats:
+    if args.siting:
+        record['bench'], record['sitings'] = 'bench_yuv_siting', siting_rows(args, dev)
+    elif args.formats:
         record['bench'], record['formats'] = 'bench_yuv_formats', format_rows(args, dev)
     else:
         record['kernels'] = kernel_rows(args, dev)
-    if not args.skip_video and not args.formats:
+    if not args.skip_video and not args.formats and not args.siting:
         record['restore_y4m'] = video_row(args, dev)
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)

@@ -15,7 +15,13 @@ edvr_amd.y4m.restore_y4m: the frames go to the device as the decoder wrote them,
 ops.yuv_to_rgb for every other format), restored by VideoRestorer with every frame's features extracted once, converted back
 (ops.rgb_to_yuv420 / ops.rgb_to_yuv) and written as they arrive - bounded memory, no intermediate files, one quantisation.  The network options are those of scripts/eval_video.py, `--batch` is the
 number of output frames per pass; `--matrix-in` / `--matrix-out` default to the player rule for each side's own size (BT.709 from 1280
-columns or 577 rows, BT.601 below), `--chroma` picks the chroma upsampling filter of the decode.  `--niqe PARAMS.npz` scores the result with
+columns or 577 rows, BT.601 below; `bt2020nc` - BT.2020 non-constant luminance, what 10-bit UHD / HDR footage is - is given by name), `--chroma`
+picks the chroma upsampling filter of the decode.  `--siting` says where the input's chroma samples lie: `center` (the default: JPEG / MPEG-1),
+`left` (H.264, HEVC and AV1 4:2:0, every 4:2:2), `topleft` (BT.2020 / UHD) or `auto` - the stream's tag (C420jpeg / C420mpeg2 / C420paldv) and
+`left` where the tag is silent.  `--siting auto` is right for nearly all decoded video: read with the wrong siting, the colour lands half an
+input pixel - two output pixels - beside the luma.  `--siting-out` is the siting the output is encoded for (default: the input's); 8-bit 4:2:0
+output carries it in its tag, for every other format tell the encoder (ffmpeg: `-chroma_sample_location left` on the output side).  The
+transfer function (gamma, PQ, HLG) is never touched: the network sees R'G'B' as coded.  `--niqe PARAMS.npz` scores the result with
 the no-reference NIQE (metrics.calculate_niqe against BasicSR's niqe_pris_params.npz; lower is better) on the float32 frames before they
 are converted back, and the decoded input at its own size beside it where at least two 96 x 96 blocks fit; `--niqe-json FILE` writes
 both lists.  `--scene-cuts [THR]` finds hard cuts (VideoRestorer's cuts='auto': ffmpeg's scene score on the 0 ... 255 scale, default 10) and
@@ -40,7 +46,7 @@ def restore(args, log=log):
     from edvr_amd import EDVR
     from edvr_amd.optim import load_network
     from edvr_amd import metrics, ops
-    from edvr_amd.y4m import ALL_FORMATS, FRAME, Y4MReader, default_matrix, restore_y4m
+    from edvr_amd.y4m import ALL_FORMATS, FRAME, Y4MReader, default_matrix, resolve_siting, restore_y4m
     device = torch.device('cuda', int(os.environ.get('LOCAL_RANK', 0)))
     torch.cuda.set_device(device)
     net = EDVR(num_in_ch=3, num_out_ch=3, num_feat=args.num_feat, num_frame=args.num_frame, deformable_groups=8,
@@ -59,6 +65,11 @@ def restore(args, log=log):
     try:
         reader = Y4MReader(src, formats=ALL_FORMATS)
         log(f'{args.input}: {reader.width} x {reader.height}, F{reader.fps}, C{reader.chroma}, {reader.range} range')
+        siting_in = resolve_siting(getattr(args, 'siting', 'center'), reader)
+        siting_out = getattr(args, 'siting_out', None)
+        if (siting_in, siting_out) != ('center', None):
+            kwargs.update(siting_in=siting_in, siting_out=siting_out)
+            log(f'{args.input}: chroma siting {siting_in} in, {resolve_siting(siting_out or siting_in, reader)} out')
         niqe_path, niqe_out, niqe_in = getattr(args, 'niqe', None), [], []
         if niqe_path:
             params = metrics.load_niqe_params(niqe_path)
@@ -71,7 +82,7 @@ def restore(args, log=log):
                     host = read(k)
                     if host.shape[0]:
                         rgb = ops.yuv_to_rgb(host.to(device, non_blocking=True)[:, len(FRAME):], H, W, reader.format, matrix_in, reader.range,
-                                             args.chroma)
+                                             args.chroma, siting_in)
                         niqe_in.extend(metrics.calculate_niqe(rgb, params=params))
                     return host
 
@@ -163,9 +174,13 @@ def parse_args(argv=None):
     ap.add_argument('--self-ensemble', default=None, choices=['flip4', 'd4'],
                     help='restore under the 4 flips / the 8 symmetries of the square and average (n x the time)')
     ap.add_argument('--time-reverse', action='store_true', help='also restore the video in reversed frame order and average (x2)')
-    ap.add_argument('--matrix-in', default=None, choices=['bt601', 'bt709'], help="the input's matrix (default: by its size)")
-    ap.add_argument('--matrix-out', default=None, choices=['bt601', 'bt709'], help="the output's matrix (default: by ITS size)")
+    ap.add_argument('--matrix-in', default=None, choices=['bt601', 'bt709', 'bt2020nc'], help="the input's matrix (default: by its size)")
+    ap.add_argument('--matrix-out', default=None, choices=['bt601', 'bt709', 'bt2020nc'], help="the output's matrix (default: by ITS size)")
     ap.add_argument('--chroma', default='bilinear', choices=['bilinear', 'nearest'], help='chroma upsampling of the decode')
+    ap.add_argument('--siting', default='center', choices=['center', 'left', 'topleft', 'auto'],
+                    help="where the input's chroma samples lie; auto: by the stream's tag, left where it is silent (recommended for decoded video)")
+    ap.add_argument('--siting-out', default=None, choices=['center', 'left', 'topleft', 'auto'],
+                    help="the siting the output is encoded for (default: the input's)")
     ap.add_argument('--out-format', default=None, metavar='NAME',
                     help="the output's format: 420 | 422 | 444 with an optional depth p9 ... p16, e.g. 420p10 (default: the input's)")
     ap.add_argument('--niqe', default=None, metavar='PARAMS.npz',
