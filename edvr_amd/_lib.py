@@ -108,6 +108,7 @@ PROTOTYPES = {
     'edvr_rgb_to_yuv420_sited_u8': (i32, [vp, vp, i32, i32, i32, i64, vp, i32, i32, vp]),
     'edvr_frame_sad_rgb_u8': (i32, [vp, vp, vp, i32, i32, i32, i64, vp]),
     'edvr_frame_sad_rgb_f32': (i32, [vp, vp, vp, i32, i32, i32, i64, vp]),
+    'edvr_jpeg_roundtrip_u8': (i32, [vp, vp, vp, i32, i32, i32, i32, i64, i64, i32, vp]),
     'edvr_adam_chunk_bytes': (sz, []),
     'edvr_adam_multi_f32': (i32, [vp, i32, ctypes.c_float, ctypes.c_float, ctypes.c_float, vp]),
     'edvr_dcnv1_fwd_ws_bytes': (sz, [i32] * 12),
@@ -153,6 +154,7 @@ CONV_AUTO, CONV_DIRECT, CONV_WINOGRAD, CONV_WINOGRAD_F4, CONV_WINOGRAD_F4S = 0, 
  CONV_KERNEL_DIRECT_SPLIT, CONV_KERNEL_DIRECT) = range(8)  # EDVR_CONV_KERNEL_*: what edvr_conv2d_kernel returns
 DTYPE_F32, DTYPE_F64, DTYPE_F16 = 0, 1, 2  # EDVR_DTYPE_*
 DCN_HALO_TAPWIN = 16  # EDVR_DCN_HALO_TAPWIN
+JPEG_SUBSAMPLINGS = {'420': 420, '444': 444}  # EDVR_JPEG_*
 
 _lib = None
 

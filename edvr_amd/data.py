@@ -101,13 +101,15 @@ def reds_keys(meta_info_file, val_partition):
 
 class ClipPlan:
     """Every random decision of one training sample: which frames, where to crop, how to augment."""
-    __slots__ = ('key', 'clip', 'center', 'frames', 'top', 'left', 'flags')
+    __slots__ = ('key', 'clip', 'center', 'frames', 'top', 'left', 'flags', 'jpeg_quality')
 
-    def __init__(self, key, clip, center, frames, top, left, flags):
+    def __init__(self, key, clip, center, frames, top, left, flags, jpeg_quality=0):
         self.key, self.clip, self.center, self.frames, self.top, self.left, self.flags = key, clip, center, frames, top, left, flags
+        self.jpeg_quality = jpeg_quality  # of the LQ crops' JPEG round trip (lq_jpeg), all frames of the clip alike; 0 = none
 
     def __repr__(self):
-        return f'ClipPlan({self.key}: frames {self.frames} of {self.clip}, crop ({self.top}, {self.left}), aug {self.flags})'
+        jpeg = f', jpeg {self.jpeg_quality}' if self.jpeg_quality else ''
+        return f'ClipPlan({self.key}: frames {self.frames} of {self.clip}, crop ({self.top}, {self.left}), aug {self.flags}{jpeg})'
 
 
 def _make_client(opt, client, with_lq):
@@ -126,12 +128,57 @@ def _make_client(opt, client, with_lq):
     raise ValueError(f'io_backend {backend} is not supported (disk, lmdb)')
 
 
+def training_lq_jpeg(opt):
+    """The `lq_jpeg` key of a TRAINING option block: None without it, else (lo, hi, subsampling, prob) of
+    {'quality': q | [lo, hi], 'subsampling': '420' | '444', 'prob': 0 .. 1}: the LQ crops of a clip go through ops.jpeg_roundtrip at a
+    quality drawn from lo .. hi with probability prob.  ValueError for a quality outside 1 .. 100, lo > hi, an unknown
+    subsampling or key and a prob outside [0, 1]."""
+    from .ops import JPEG_SUBSAMPLINGS, jpeg_quality
+    if opt.get('lq_jpeg') is None:
+        return None
+    spec = dict(opt['lq_jpeg'])
+    unknown = set(spec) - {'quality', 'subsampling', 'prob'}
+    if unknown or 'quality' not in spec:
+        raise ValueError(f"lq_jpeg takes 'quality' and optionally 'subsampling' and 'prob', got {sorted(spec)}")
+    quality = spec['quality']
+    if isinstance(quality, (list, tuple)):
+        if len(quality) != 2:
+            raise ValueError(f'lq_jpeg: quality is an int or [lo, hi], got {quality!r}')
+        lo, hi = (jpeg_quality(q, 'lq_jpeg: quality') for q in quality)
+    else:
+        lo = hi = jpeg_quality(quality, 'lq_jpeg: quality')
+    if lo > hi:
+        raise ValueError(f'lq_jpeg: quality range [{lo}, {hi}] is empty')
+    subsampling = spec.get('subsampling', '420')
+    if subsampling not in JPEG_SUBSAMPLINGS:
+        raise ValueError(f'lq_jpeg: subsampling must be one of {JPEG_SUBSAMPLINGS}, got {subsampling!r}')
+    prob = spec.get('prob', 1.0)
+    if isinstance(prob, bool) or not isinstance(prob, (int, float)) or not 0 <= prob <= 1:
+        raise ValueError(f'lq_jpeg: prob must be a number in [0, 1], got {prob!r}')
+    return lo, hi, subsampling, float(prob)
+
+
+def _draw_jpeg_quality(lq_jpeg, rng):
+    """The planners' last draws, made only where the option block has `lq_jpeg`: [r.random() < prob where prob < 1], then
+    r.randint(lo, hi) - on a stream r forked from the state `rng` is in after the reference's draws.  `rng` itself is not advanced, so
+    every other decision of the epoch - this plan's and all later ones' - is what it is without the key, and a loader with the key
+    yields the batches of the loader without it, compressed."""
+    if lq_jpeg is None:
+        return 0
+    lo, hi, _, prob = lq_jpeg
+    r = random.Random(repr(rng.getstate()))
+    if prob < 1 and not r.random() < prob:
+        return 0
+    return r.randint(lo, hi)
+
+
 class REDSClipPlanner:
     """The decisions of REDSDataset.__getitem__ (reds_dataset.py:106-234), separated from the pixels.  `opt` has the reference's
     keys (dataroot_gt, dataroot_lq, meta_info_file, val_partition, io_backend, num_frame, gt_size, interval_list, random_reverse,
     use_flip, use_rot, scale).  plan(index, rng) draws from `rng` (a random.Random or the `random` module) exactly the values the
     reference draws, in its order: interval, [new centre frames while the window leaves 0..99], [reverse], crop top, crop left,
-    [hflip], [vflip], [rot90]."""
+    [hflip], [vflip], [rot90] - and after them, with an `lq_jpeg` key only (training_lq_jpeg), the clip's JPEG quality, from a fork of
+    the stream (_draw_jpeg_quality) that leaves `rng` where the reference's draws left it."""
 
     def __init__(self, opt, client=None):
         if opt.get('dataroot_flow') is not None:
@@ -144,6 +191,7 @@ class REDSClipPlanner:
         self.keys = reds_keys(opt['meta_info_file'], opt['val_partition'])
         self.interval_list, self.random_reverse = opt['interval_list'], opt['random_reverse']
         self.lq_from_gt = training_lq_from_gt(opt)  # None: an LQ tree
+        self.lq_jpeg = training_lq_jpeg(opt)  # None: no JPEG round trip of the LQ crops
         self.client = _make_client(opt, client, self.lq_from_gt is None)
         self._shape = {}  # clip -> ((h_lq, w_lq), (h_gt, w_gt)): all frames of a REDS clip have one size
         # the one place the two sources of LQ part: where the sizes come from and what load() stages
@@ -190,7 +238,7 @@ class REDSClipPlanner:
             flags |= AUG_VFLIP
         if self.opt['use_rot'] and rng.random() < 0.5:
             flags |= AUG_ROT90
-        return ClipPlan(key, clip, center, frames, top, left, flags)
+        return ClipPlan(key, clip, center, frames, top, left, flags, _draw_jpeg_quality(self.lq_jpeg, rng))
 
     def _load_gt_windows(self, plan, lq_out=None, gt_out=None):
         """load() without an LQ tree: lq is the pair (windows (t, e, pitch) uint8, table (t, 8) int32) of the decoded GT frames for
@@ -217,7 +265,8 @@ class Vimeo90KClipPlanner:
     7-frame sequences `<root>/<clip>/<seq>/im1.png .. im7.png`, keys from the meta file (`00001/0001 7 (256,448,3)`), GT = im4,
     the centred window of `num_frame` frames, and the reference's draws in its order: [reverse], crop top, crop left, [hflip],
     [vflip], [rot90].  The reference reverses its neighbour list IN PLACE (:82-83), so the orientation persists from one sample to
-    the next: plan() keeps that state too (one planner = one dataset object)."""
+    the next: plan() keeps that state too (one planner = one dataset object).  With an `lq_jpeg` key the clip's JPEG quality is drawn last,
+    as REDSClipPlanner draws it."""
 
     def __init__(self, opt, client=None):
         self.opt = opt
@@ -229,6 +278,7 @@ class Vimeo90KClipPlanner:
         self.neighbor_list = [i + (9 - self.num_frame) // 2 for i in range(self.num_frame)]
         self.random_reverse = opt['random_reverse']
         self.lq_from_gt = training_lq_from_gt(opt)  # None: an LQ tree
+        self.lq_jpeg = training_lq_jpeg(opt)  # None: no JPEG round trip of the LQ crops
         self.client = _make_client(opt, client, self.lq_from_gt is None)
         # the one place the two sources of LQ part: where the sizes come from and what load() stages
         if self.lq_from_gt is None:
@@ -267,7 +317,7 @@ class Vimeo90KClipPlanner:
             flags |= AUG_VFLIP
         if self.opt['use_rot'] and rng.random() < 0.5:
             flags |= AUG_ROT90
-        return ClipPlan(key, key, 4, frames, top, left, flags)
+        return ClipPlan(key, key, 4, frames, top, left, flags, _draw_jpeg_quality(self.lq_jpeg, rng))
 
     def _load_gt_windows(self, plan, lq_out=None, gt_out=None):
         return self.windows.load(plan, [f'im{f}' for f in plan.frames], 'im4', lq_out, gt_out)
@@ -393,20 +443,32 @@ def imresize(img, scale, antialiasing=True):
     return ops.imresize(img, scale, antialiasing)
 
 
-def lq_from_gt(gt, scale, quantize=None, degradation='bi'):
+def lq_from_gt(gt, scale, quantize=None, degradation='bi', jpeg_quality=None, jpeg_subsampling='420'):
     """The x`scale` LQ frames of GT frames (t, 3, H, W) float32 on the device, H and W multiples of `scale`.  degradation 'bi': imresize
     by 1 / scale, rounded to 8 bits when `quantize` (the default; what a stored PNG dataset contains) - generate_bicubic_img.m without
     the files.  'bd': duf_downsample, NOT rounded unless `quantize` is given as True - VideoTestDUFDataset feeds the float result to the
-    network."""
+    network.  jpeg_quality 1 .. 100: the 8-bit LQ frames go through a baseline JPEG round trip (ops.jpeg_roundtrip, DESIGN 4.16;
+    jpeg_subsampling '420' or '444') before they become float - compression artifacts on top of the downsampling; it works on bytes, so
+    it implies `quantize` and is a ValueError with quantize=False."""
     from . import ops
     if degradation not in DEGRADATIONS:
         raise ValueError(f'degradation must be one of {DEGRADATIONS}, got {degradation!r}')
+    if jpeg_quality is not None:
+        jpeg_quality = ops.jpeg_quality(jpeg_quality, 'jpeg_quality')
+        if jpeg_subsampling not in ops.JPEG_SUBSAMPLINGS:
+            raise ValueError(f'jpeg_subsampling must be one of {ops.JPEG_SUBSAMPLINGS}, got {jpeg_subsampling!r}')
+        if quantize is not None and not quantize:
+            raise ValueError('jpeg_quality compresses the 8-bit LQ frames: it cannot go with quantize=False')
+        quantize = True
     if quantize is None:
         quantize = degradation == 'bi'
     down = (lambda **kw: ops.imresize(gt, 1 / scale, **kw)) if degradation == 'bi' else (lambda **kw: ops.bd_downsample(gt, scale, **kw))
     if not quantize:
         return down()
-    return ops.frames_u8_to_f32(down(out_dtype=torch.uint8)[None])[0]
+    lq = down(out_dtype=torch.uint8)
+    if jpeg_quality is not None:
+        lq = ops.jpeg_roundtrip(lq, jpeg_quality, jpeg_subsampling)
+    return ops.frames_u8_to_f32(lq[None])[0]
 
 
 # ------------------------------------------------------------------------------------------------ BD downsampling (csrc/bd.hip)
@@ -626,7 +688,9 @@ class VideoTestClips:
 
     Without an LQ folder: dataroot_lq None and lq_from_gt = {'scale': 4, 'quantize': True} derive the LQ frames from the decoded GT on
     the device (lq_from_gt above; GT mod-cropped to a multiple of the scale first, as read_img_seq(require_mod_crop=True) does);
-    lq_from_gt = {'scale': 4, 'degradation': 'bd'} makes them with duf_downsample instead (not quantised unless 'quantize' says so)."""
+    lq_from_gt = {'scale': 4, 'degradation': 'bd'} makes them with duf_downsample instead (not quantised unless 'quantize' says so);
+    'jpeg_quality': q (and 'jpeg_subsampling': '420' | '444') adds the JPEG round trip of lq_from_gt above, which implies 'quantize'
+    and is a ValueError with 'quantize': False."""
 
     def __init__(self, opt, device='cuda'):
         import glob
@@ -641,8 +705,19 @@ class VideoTestClips:
             degradation = self.lq_from_gt.get('degradation', 'bi')
             if degradation not in DEGRADATIONS:
                 raise ValueError(f'lq_from_gt: degradation must be one of {DEGRADATIONS}, got {degradation!r}')
-            self.lq_from_gt = {'scale': int(self.lq_from_gt['scale']), 'quantize': bool(self.lq_from_gt.get('quantize', degradation == 'bi')),
+            jpeg = {k: self.lq_from_gt[k] for k in ('jpeg_quality', 'jpeg_subsampling') if self.lq_from_gt.get(k) is not None}
+            if jpeg.get('jpeg_quality') is None:
+                jpeg = {}
+            self.lq_from_gt = {'scale': int(self.lq_from_gt['scale']), 'quantize': bool(self.lq_from_gt.get('quantize', degradation == 'bi' or bool(jpeg))),
                                'degradation': degradation}
+            if jpeg:
+                from .ops import JPEG_SUBSAMPLINGS, jpeg_quality
+                jpeg['jpeg_quality'] = jpeg_quality(jpeg['jpeg_quality'], 'lq_from_gt: jpeg_quality')
+                if jpeg.setdefault('jpeg_subsampling', '420') not in JPEG_SUBSAMPLINGS:
+                    raise ValueError(f"lq_from_gt: jpeg_subsampling must be one of {JPEG_SUBSAMPLINGS}, got {jpeg['jpeg_subsampling']!r}")
+                if not self.lq_from_gt['quantize']:
+                    raise ValueError("lq_from_gt: jpeg_quality compresses the 8-bit LQ frames: it cannot go with 'quantize': False")
+            self._lq_jpeg = jpeg
             if degradation == 'bd':
                 if self.lq_from_gt['scale'] not in BD_SCALES:
                     raise ValueError(f"lq_from_gt: scale {self.lq_from_gt['scale']} is not one of {BD_SCALES} (degradation 'bd')")
@@ -705,7 +780,7 @@ class VideoTestClips:
         scale, quantize = self.lq_from_gt['scale'], self.lq_from_gt['quantize']
         gt = read_img_seq(paths_gt, self.device, require_mod_crop=True, scale=scale)
         src = gt if list(paths_lq) == list(paths_gt) else read_img_seq(paths_lq, self.device, require_mod_crop=True, scale=scale)
-        return lq_from_gt(src, scale, quantize, self.lq_from_gt['degradation']), gt
+        return lq_from_gt(src, scale, quantize, self.lq_from_gt['degradation'], **self._lq_jpeg), gt
 
     def __getitem__(self, index):
         folder = self.data_info['folder'][index]
@@ -788,7 +863,11 @@ class REDSDeviceLoader:
     next() -> {'lq': (b, t, 3, p, p), 'gt': (b, 3, P, P) float32 device tensors, 'key': [str]} or None at the end of the epoch
     (CUDAPrefetcher.next, prefetch_dataloader.py:118-122); reset() starts the next epoch.  A planner thread makes the random
     decisions serially from epoch_rng(seed + rank, epoch) (deterministic whatever the thread count and prefetch depth), `num_threads` workers decode into pinned staging
-    slots, the copy + conversion of batch k+1 run on a side stream while batch k trains."""
+    slots, the copy + conversion of batch k+1 run on a side stream while batch k trains.
+
+    opt['lq_jpeg'] = {'quality': q | [lo, hi], 'subsampling': '420', 'prob': 1.0} (training_lq_jpeg; either source of LQ): the LQ crop
+    bytes of the batch go through ONE ops.jpeg_roundtrip launch at each clip's planned quality before the conversion to float - GT is
+    untouched, and the 8 x 8 block grid starts at the crop's corner."""
 
     def __init__(self, opt, batch_size, device='cuda', rank=0, world_size=1, ratio=1, seed=0, num_threads=8, depth=3, drop_last=True,
                  client=None):
@@ -815,6 +894,8 @@ class REDSDeviceLoader:
                               for s, tab in zip(lq_slots, self._tables)]
             self._lq_upload = self._upload_gt_windows
         self.slots = [(lq, torch.empty((batch_size, 1, P, P, 3), dtype=torch.uint8).pin_memory()) for lq in lq_slots]
+        # lq_jpeg: one quality per LQ frame, in a pinned table per slot (copied on the loader's stream before the slot is handed back)
+        self._jpeg_tables = [torch.zeros(batch_size * t, dtype=torch.int32).pin_memory() for _ in lq_slots] if self.planner.lq_jpeg else None
         self.stream = torch.cuda.Stream(self.device)
         self.epoch = 0
         self._start()
@@ -886,6 +967,11 @@ class REDSDeviceLoader:
         flags = bytes(p.flags for p in plans)
         with torch.cuda.stream(self.stream):
             lq_d, gt_d = self._lq_upload(slot, n), gt[:n].to(self.device, non_blocking=True)
+            if self._jpeg_tables is not None:  # compression comes before flip / rotation: the block grid is anchored at the crop's corner
+                t, p = self.planner.num_frame, self.planner.lq_size
+                table = self._jpeg_tables[slot][:n * t]
+                table.view(n, t).copy_(torch.tensor([pl.jpeg_quality for pl in plans], dtype=torch.int32)[:, None])
+                lq_d = ops.jpeg_roundtrip(lq_d.view(n * t, p, p, 3), table.to(self.device, non_blocking=True), self.planner.lq_jpeg[2]).view(n, t, p, p, 3)
             copied = torch.cuda.Event()
             copied.record(self.stream)
             out = {'lq': ops.frames_u8_to_f32(lq_d, flags), 'gt': ops.frames_u8_to_f32(gt_d, flags)[:, 0], 'key': [p.key for p in plans]}

@@ -2162,3 +2162,73 @@ def frame_sad(frames, prev=None, out=None):
     nbytes = float(n + (prev is not None)) * 3 * H * W * frames.element_size() + 8.0 * n  # each frame once
     _run('frame_sad', lambda: _lib.check(getattr(_lib.lib(), name)(_ptr(frames), _ptr(prev), _ptr(out), n, H, W, stride, _stream()), name), 0, nbytes)
     return out
+
+
+# ------------------------------------------------------------------------------------------------ JPEG round trip (csrc/jpeg.hip)
+JPEG_SUBSAMPLINGS = tuple(_lib.JPEG_SUBSAMPLINGS)
+
+
+def jpeg_quality(quality, what='quality', allow_zero=False):
+    """One host-side JPEG quality as an int: 1 .. 100 (0 = no compression where `allow_zero`); ValueError otherwise."""
+    import operator
+    try:
+        q = operator.index(quality) if not isinstance(quality, bool) else None
+    except TypeError:
+        q = None
+    if q is None:
+        raise ValueError(f'{what} must be an int in 1 .. 100, got {quality!r}')
+    if not (1 <= q <= 100 or (allow_zero and q == 0)):
+        raise ValueError(f'{what} {q} is outside 1 .. 100')
+    return q
+
+
+def jpeg_roundtrip(frames, quality, subsampling='420', out=None):
+    """What a baseline JPEG encoder followed by a decoder makes of a batch of frames, in ONE launch: libjpeg's integer
+    pipeline - colour conversion, edge padding to the MCU, 2 x 2 chroma mean ('420'), 13-bit DCT, Annex K tables scaled by the quality
+    and back - byte for byte what PIL's Image.save(format='JPEG', quality=q, subsampling=2 | 0) and Image.open(...).convert('RGB')
+    return.  Entropy coding is lossless and is not performed.  frames: uint8 (n, H, W, 3) RGB on the GPU, 1 <= n <= 65535, each image
+    dense, the images any distance apart (a slice of a longer batch works as it is) -> uint8 (n, H, W, 3).  quality: an int 1 .. 100 for
+    every image, a sequence of n ints, or an int32 (n,) device tensor (which the kernel clamps to 0 .. 100); an entry 0 copies that
+    image through unchanged.  subsampling: '420' (16 x 16 MCUs) or '444' (8 x 8).  out: a uint8 (n, H, W, 3) tensor of dense images to
+    write into, which must not overlap `frames` (a workgroup reads pixels of its neighbours' tiles).  ValueError for bad qualities,
+    names, layouts and an overlapping `out`; CPU tensors raise NotImplementedError: there is no fallback."""
+    for t in (frames, out, quality if torch.is_tensor(quality) else None):
+        if t is not None and not t.is_cuda:
+            raise NotImplementedError('edvr_amd ops run on the GPU only (HIP/gfx950); got a CPU tensor')
+    if subsampling not in _lib.JPEG_SUBSAMPLINGS:
+        raise ValueError(f'subsampling must be one of {JPEG_SUBSAMPLINGS}, got {subsampling!r}')
+    if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[-1] != 3:
+        raise ValueError(f'frames are uint8 (n, H, W, 3), got {frames.dtype} {tuple(frames.shape)}')
+    n, H, W, _ = frames.shape
+    if not 0 < n <= 65535 or H < 1 or W < 1:
+        raise ValueError(f'jpeg_roundtrip takes 1..65535 non-empty frames per call, got {tuple(frames.shape)}')
+
+    def dense(t):
+        return t[0].is_contiguous() and (n == 1 or t.stride(0) >= 3 * H * W)
+    if not dense(frames):
+        frames = frames.contiguous()
+    table, q_all = None, 0
+    if torch.is_tensor(quality):
+        if quality.dtype != torch.int32 or tuple(quality.shape) != (n,):
+            raise ValueError(f'a quality table is an int32 ({n},) device tensor, got {quality.dtype} {tuple(quality.shape)}')
+        table = quality.contiguous()
+    elif isinstance(quality, (list, tuple)):
+        if len(quality) != n:
+            raise ValueError(f'{len(quality)} qualities for {n} frames')
+        table = torch.tensor([jpeg_quality(q, allow_zero=True) for q in quality], dtype=torch.int32).to(frames.device, non_blocking=True)
+    else:
+        q_all = jpeg_quality(quality, allow_zero=True)
+    if out is None:
+        out = torch.empty((n, H, W, 3), dtype=torch.uint8, device=frames.device)
+    else:
+        if out.dtype != torch.uint8 or tuple(out.shape) != (n, H, W, 3) or not dense(out):
+            raise ValueError(f'out is a uint8 {(n, H, W, 3)} tensor of dense images, got {out.dtype} {tuple(out.shape)}')
+        (a0, a1), (b0, b1) = _byte_span(frames), _byte_span(out)
+        if a0 < b1 and b0 < a1:
+            raise ValueError('out overlaps the input')
+    stride = lambda t: t.stride(0) if n > 1 else 3 * H * W
+    nbytes = 6.0 * n * H * W + (4.0 * n if table is not None else 0.0)  # each pixel read and written once, plus the table
+    _run('jpeg_roundtrip', lambda: _lib.check(_lib.lib().edvr_jpeg_roundtrip_u8(_ptr(frames), _ptr(out), _ptr(table), q_all, n, H, W, stride(frames),
+                                                                                 stride(out), _lib.JPEG_SUBSAMPLINGS[subsampling], _stream()),
+                                              'edvr_jpeg_roundtrip_u8'), 0, nbytes)
+    return out

@@ -755,6 +755,22 @@ int edvr_rgb_to_yuv420_sited_u8(const uint8_t *rgb, uint8_t *yuv, int n, int H, 
 int edvr_frame_sad_rgb_u8(const uint8_t *x, const uint8_t *prev, uint64_t *sad, int n, int H, int W, int64_t img_stride, edvr_stream_t stream);
 int edvr_frame_sad_rgb_f32(const float *x, const float *prev, uint64_t *sad, int n, int H, int W, int64_t img_stride, edvr_stream_t stream);
 
+/* Baseline JPEG round trip (csrc/jpeg.hip; definition: DESIGN 4.16): dst = what a baseline JPEG encoder at `quality` followed by a decoder
+ * returns for src - libjpeg's integer pipeline (colour conversion, edge padding to the MCU, 2 x 2 chroma mean with alternating bias, 13-bit
+ * Loeffler DCT, Annex K tables scaled by the quality, inverse DCT, triangle-filter chroma upsampling), byte for byte; entropy coding is
+ * lossless and is not performed.  src, dst: n dense (H, W, 3) RGB byte images src_image_stride / dst_image_stride BYTES apart at any base
+ * address (0 = dense; a slice of a longer batch works); the two must not overlap (a workgroup reads pixels of its neighbours' tiles).
+ * quality: a DEVICE table of n int32, each clamped to 0 ... 100 by the kernel, or NULL: quality_all, 0 ... 100, for every image.  A
+ * quality of 0 copies that image through unchanged.  subsampling: EDVR_JPEG_420 (16 x 16 MCUs) or EDVR_JPEG_444 (8 x 8).
+ * ONE kernel launch, grid (64 x 64 pixel tiles, n); dword accesses on a side whose base and stride are multiples of 4 where W % 4 == 0,
+ * bytes otherwise; same values either way.  EDVR_ERR_ARG: null src / dst, n outside 1 ... 65535, H or W < 1, H W > 2^29, a subsampling
+ * other than the two, quality_all outside 0 ... 100 with a NULL table, an image stride shorter than 3 H W with n > 1.  No allocation, no
+ * wait, capturable in a graph. */
+#define EDVR_JPEG_444 444
+#define EDVR_JPEG_420 420
+int edvr_jpeg_roundtrip_u8(const uint8_t *src, uint8_t *dst, const int32_t *quality, int quality_all, int n, int H, int W,
+                           int64_t src_image_stride, int64_t dst_image_stride, int subsampling, edvr_stream_t stream);
+
 /* Multi-tensor Adam step <- torch.optim.Adam.step() as the reference builds it (basicsr/models/edvr_model.py:21-53, parameter
  * groups with dcn_lr_mul; stepped in sr_model.py:112).  `chunk_table` is a DEVICE array of n_chunks records of
  * edvr_adam_chunk_bytes() = 64 bytes: { float *p; const float *g; float *m; float *v; int32 n (<= 65536 elements of one tensor);

@@ -15,7 +15,9 @@ between the two orders); alone it is an ensemble of the two time orders, with `-
 (edvr_amd.data.imresize, 8-bit like a stored dataset); with `--degradation bd` they are DUF's Gaussian blur and subsampling instead
 (edvr_amd.data.duf_downsample, SCALE 2, 3 or 4, float as the reference's VideoTestDUFDataset feeds them).  `--bicubic-baseline` scores the
 bicubic enlargement of the LQ frames beside the model under either degradation, as the published BI and BD tables do (the LQ frames
-themselves for --hr-in networks); `--json FILE` writes what is printed, and the degradation.  `--niqe PARAMS.npz` also scores every
+themselves for --hr-in networks); `--jpeg-quality Q [--jpeg-subsampling 420|444]` sends the 8-bit LQ frames through a baseline JPEG round
+trip first (edvr_amd.ops.jpeg_roundtrip; with --degradation bd it rounds them to 8 bits), and the baseline then enlarges the compressed
+frames; `--json FILE` writes what is printed, and the degradation.  `--niqe PARAMS.npz` also scores every
 output with the no-reference NIQE (metrics.calculate_niqe against BasicSR's niqe_pris_params.npz, lower is better) - the model's, the
 second pass's and the baseline's, next to their PSNRs.
 
@@ -83,6 +85,8 @@ def evaluate(args, log=print):
         if not lq_from_gt:
             raise ValueError('either an LQ folder or lq_from_gt is needed')
         opt['lq_from_gt'] = dict(scale=lq_from_gt, quantize=True) if degradation == 'bi' else dict(scale=lq_from_gt, degradation=degradation)
+        if getattr(args, 'jpeg_quality', None) is not None:
+            opt['lq_from_gt'].update(jpeg_quality=args.jpeg_quality, jpeg_subsampling=getattr(args, 'jpeg_subsampling', None) or '420')
     ds = VideoTestClips(opt, device=device)
     # frames of any size (--pad-mode / --tile / --tile-overlap / --tile-blend): passed on only where given
     any_size = {k: (tuple(v) if k == 'tile' else v) for k in ('pad_mode', 'tile', 'tile_overlap', 'tile_blend')
@@ -163,6 +167,8 @@ def evaluate(args, log=print):
             import json
             record = {'psnr': summary, 'average': sum(summary.values()) / max(len(summary), 1),
                       'degradation': degradation if args.lq is None else None}  # None: the LQ folder's, whatever made it
+            if args.lq is None and getattr(args, 'jpeg_quality', None) is not None:
+                record.update(jpeg_quality=args.jpeg_quality, jpeg_subsampling=getattr(args, 'jpeg_subsampling', None) or '420')
             if plus_kw:
                 record.update(self_ensemble=ensemble, self_ensemble_psnr=plus, self_ensemble_average=sum(plus.values()) / max(len(plus), 1))
                 if reverse:
@@ -187,6 +193,9 @@ def parse_args(argv=None):
                     help='make the LQ frames from the GT frames on the device: MATLAB bicubic reduction by SCALE, 8-bit (GT mod-cropped to SCALE)')
     ap.add_argument('--degradation', choices=('bi', 'bd'), default='bi',
                     help="with --lq-from-gt: bi = MATLAB bicubic, 8-bit; bd = DUF's Gaussian blur and subsampling, float (SCALE 2, 3 or 4)")
+    ap.add_argument('--jpeg-quality', type=int, default=None, metavar='Q',
+                    help='with --lq-from-gt: the 8-bit LQ frames go through a baseline JPEG round trip at quality Q (1..100)')
+    ap.add_argument('--jpeg-subsampling', choices=('420', '444'), default='420', help='chroma subsampling of --jpeg-quality')
     ap.add_argument('--bicubic-baseline', action='store_true', help='also report the PSNR of the bicubic enlargement of the LQ frames')
     ap.add_argument('--niqe', default=None, metavar='PARAMS.npz',
                     help="also report the no-reference NIQE of every output; PARAMS.npz is BasicSR's basicsr/metrics/niqe_pris_params.npz")
@@ -224,6 +233,8 @@ def parse_args(argv=None):
         ap.error('give exactly one of --lq and --lq-from-gt')
     if args.lq_from_gt is not None and not 1 <= args.lq_from_gt <= 8:
         ap.error('--lq-from-gt takes a scale in 1..8')
+    if args.jpeg_quality is not None and (args.lq_from_gt is None or not 1 <= args.jpeg_quality <= 100):
+        ap.error('--jpeg-quality takes a quality in 1..100 and needs --lq-from-gt')
     if args.tile_blend is not None and args.tile is None:
         ap.error('--tile-blend needs --tile')
     if args.degradation == 'bd' and args.lq_from_gt not in (2, 3, 4):

@@ -4,11 +4,17 @@ the reference's duf_downsample; scales 2, 3, 4).
 
     python scripts/make_lq.py datasets/REDS4/GT datasets/REDS4/sharp_bicubic --scale 4
     python scripts/make_lq.py datasets/Vid4/GT datasets/Vid4/BDx4 --scale 4 --degradation bd
+    python scripts/make_lq.py datasets/REDS/train_blur datasets/REDS/train_blur_comp --scale 1 --jpeg-quality 40
 
 GT_ROOT/<clip>/<frame>.png -> LQ_ROOT/<clip>/<frame>.png.  Frames are decoded and encoded on host threads through PIL (as
 edvr_amd/data.py decodes), mod-cropped to a multiple of the scale (as the MATLAB script does), resized by 1 / scale in one launch per
 batch of equal-sized frames (edvr_amd.ops.imresize or ops.bd_downsample, uint8 in, uint8 out: the rounding tensor2img applies) and
 written as 8-bit PNG.
+
+`--jpeg-quality Q [--jpeg-subsampling 420|444]` sends the resized bytes through a baseline JPEG round trip on the device before they are
+stored (edvr_amd.ops.jpeg_roundtrip, DESIGN 4.16: the bytes PIL's JPEG writer and reader return): compression artifacts in the LQ tree,
+still stored as PNG.  `--scale 1` skips the resize - imresize at scale 1 is the identity on bytes (tests/test_gpu_jpeg.py checks it), so
+nothing changes without the option - and with it compresses a tree at its own size (deblurcomp-style data).
 """
 import argparse
 import os
@@ -46,6 +52,12 @@ def bd_u8(frames_u8, scale, device):
     return ops.bd_downsample(torch.from_numpy(frames_u8).to(device), scale, out_dtype=torch.uint8).cpu().numpy()
 
 
+def jpeg_u8(frames_u8, quality, subsampling, device):
+    """(n, H, W, 3) uint8 host array -> the same after a JPEG round trip on the device."""
+    from edvr_amd import ops
+    return ops.jpeg_roundtrip(torch.from_numpy(frames_u8).to(device), quality, subsampling).cpu().numpy()
+
+
 def load(path, scale):
     from edvr_amd.data import decode_image
     with open(path, 'rb') as f:
@@ -58,11 +70,17 @@ def save(path, rgb_u8):
     Image.fromarray(rgb_u8).save(os.path.splitext(path)[0] + '.png', format='PNG')
 
 
-def make_lq(gt_root, lq_root, scale=4, antialiasing=True, batch=16, num_threads=8, device='cuda', log=print, degradation='bi'):
-    """Returns the number of frames written."""
+def make_lq(gt_root, lq_root, scale=4, antialiasing=True, batch=16, num_threads=8, device='cuda', log=print, degradation='bi',
+            jpeg_quality=None, jpeg_subsampling='420'):
+    """Returns the number of frames written.  jpeg_quality 1 .. 100: the stored bytes have been through a JPEG round trip."""
     from edvr_amd.data import bd_shape, imresize_shape
     if degradation not in ('bi', 'bd'):
         raise ValueError(f"degradation must be 'bi' or 'bd', got {degradation!r}")
+    if jpeg_quality is not None:
+        from edvr_amd import ops
+        jpeg_quality = ops.jpeg_quality(jpeg_quality, 'jpeg_quality')
+        if jpeg_subsampling not in ops.JPEG_SUBSAMPLINGS:
+            raise ValueError(f'jpeg_subsampling must be one of {ops.JPEG_SUBSAMPLINGS}, got {jpeg_subsampling!r}')
     if degradation == 'bd':
         bd_shape(7, 7, scale)  # a scale DUF's kernel does not have: ValueError before any file is read
     clips = walk(gt_root)
@@ -80,9 +98,13 @@ def make_lq(gt_root, lq_root, scale=4, antialiasing=True, batch=16, num_threads=
                     if degradation == 'bd':
                         bd_shape(shape[0], shape[1], scale)  # a frame too small for the kernel: ValueError naming it
                         out = bd_u8(np.stack([imgs[i] for i in sel]), scale, device)
+                    elif scale == 1:  # the identity on bytes
+                        out = np.stack([imgs[i] for i in sel])
                     else:
                         imresize_shape(shape[0], shape[1], 1 / scale, antialiasing)  # likewise
                         out = resize_u8(np.stack([imgs[i] for i in sel]), scale, antialiasing, device)
+                    if jpeg_quality is not None:
+                        out = jpeg_u8(out, jpeg_quality, jpeg_subsampling, device)
                     list(pool.map(lambda io: save(os.path.join(lq_root, clip, names[io[0]]), io[1]), zip(sel, out)))
                 written += len(names)
             log(f'{clip}: {len(frames)} frame(s)')
@@ -97,6 +119,9 @@ def parse_args(argv=None):
     ap.add_argument('--degradation', choices=('bi', 'bd'), default='bi',
                     help="bi: MATLAB's antialiased bicubic imresize; bd: DUF's 13 x 13 Gaussian blur and subsampling (scale 2, 3 or 4)")
     ap.add_argument('--no-antialias', action='store_true', help="imresize(..., 'Antialiasing', false) (bi only)")
+    ap.add_argument('--jpeg-quality', type=int, default=None, metavar='Q',
+                    help='send the LQ bytes through a baseline JPEG round trip at quality Q (1..100) before they are stored')
+    ap.add_argument('--jpeg-subsampling', choices=('420', '444'), default='420', help='chroma subsampling of --jpeg-quality')
     ap.add_argument('--batch', type=int, default=16, help='frames per launch')
     ap.add_argument('--threads', type=int, default=8, help='host threads decoding and encoding')
     args = ap.parse_args(argv)
@@ -106,12 +131,15 @@ def parse_args(argv=None):
         ap.error('--degradation bd takes --scale 2, 3 or 4')
     if args.degradation == 'bd' and args.no_antialias:
         ap.error('--no-antialias belongs to --degradation bi')
+    if args.jpeg_quality is not None and not 1 <= args.jpeg_quality <= 100:
+        ap.error('--jpeg-quality must be an integer in 1..100')
     return args
 
 
 def main():
     args = parse_args()
-    n = make_lq(args.gt_root, args.lq_root, args.scale, not args.no_antialias, args.batch, args.threads, degradation=args.degradation)
+    n = make_lq(args.gt_root, args.lq_root, args.scale, not args.no_antialias, args.batch, args.threads, degradation=args.degradation,
+                jpeg_quality=args.jpeg_quality, jpeg_subsampling=args.jpeg_subsampling)
     print(f'{n} frame(s) -> {args.lq_root}')
 
 

@@ -7,6 +7,10 @@ EnlargedSampler, gradients all-reduced over RCCL by DDP.
     python scripts/train_reds.py --gt datasets/REDS/train_sharp --lq datasets/REDS/train_sharp_bicubic/X4 \
         --meta meta_info_REDS_GT.txt --iters 600000 [--val-gt ... --val-lq ...]
 
+`--lq-jpeg LO HI [--lq-jpeg-prob P]` trains on compressed input: the LQ crops of a clip - from the LQ tree or made from GT - go through a
+baseline JPEG round trip on the device at a quality drawn from LO .. HI, with probability P (the dataset option `lq_jpeg`).
+Validation LQ frames made from GT are compressed at `--val-jpeg-quality` (default (LO + HI) // 2); a --val-lq tree is used as it is.
+
 It is a caller of the hot path, kept small on purpose: option parsing, logging and the experiment directory layout of
 basicsr/train.py are out of scope (control plane).
 """
@@ -60,6 +64,10 @@ def train(args, log=print):
     lq_from_gt = getattr(args, 'lq_from_gt', None)
     if args.lq is None:  # no LQ tree: the loader makes the LQ crops from windows of the GT frames on the device (8-bit, as a stored tree)
         data_opt['lq_from_gt'] = dict(scale=lq_from_gt, degradation=getattr(args, 'degradation', None) or 'bi')
+    lq_jpeg = getattr(args, 'lq_jpeg', None)
+    if lq_jpeg is not None:
+        prob = getattr(args, 'lq_jpeg_prob', None)
+        data_opt['lq_jpeg'] = dict(quality=list(lq_jpeg), subsampling='420', prob=1.0 if prob is None else prob)
     loader = REDSDeviceLoader(data_opt, args.batch, device=device, rank=rank, world_size=world, ratio=args.enlarge_ratio,
                               seed=args.seed, num_threads=args.threads)
     val = None
@@ -68,6 +76,9 @@ def train(args, log=print):
                        cache_data=True, num_frame=args.num_frame, padding='reflection_circle')
         if args.val_lq is None:  # the validation LQ frames likewise, quantised like the training crops
             val_opt['lq_from_gt'] = dict(data_opt['lq_from_gt'], quantize=True)
+            if lq_jpeg is not None:
+                val_q = getattr(args, 'val_jpeg_quality', None)
+                val_opt['lq_from_gt']['jpeg_quality'] = (lq_jpeg[0] + lq_jpeg[1]) // 2 if val_q is None else val_q
         val = VideoTestClips(val_opt, device=device)
     if state is not None:
         resume_training(state, [opt], [sched])
@@ -121,6 +132,11 @@ def parse_args(argv=None):
                          '(SCALE 4, the scale of the network)')
     ap.add_argument('--degradation', choices=('bi', 'bd'), default='bi',
                     help="with --lq-from-gt: bi = MATLAB bicubic, bd = DUF's Gaussian blur and subsampling")
+    ap.add_argument('--lq-jpeg', type=int, nargs=2, default=None, metavar=('LO', 'HI'),
+                    help='JPEG-compress the LQ crops of each clip on the device at a quality drawn from LO..HI (4:2:0)')
+    ap.add_argument('--lq-jpeg-prob', type=float, default=1.0, metavar='P', help='with --lq-jpeg: the share of clips that are compressed')
+    ap.add_argument('--val-jpeg-quality', type=int, default=None, metavar='Q',
+                    help='with --lq-jpeg: the quality of validation LQ frames made from --val-gt (default (LO + HI) // 2)')
     ap.add_argument('--meta', required=True)
     ap.add_argument('--val-gt')
     ap.add_argument('--val-lq', help='optional with --lq-from-gt: the validation LQ frames are then made from --val-gt the same way')
@@ -154,6 +170,12 @@ def parse_args(argv=None):
         ap.error('--lq-from-gt takes the scale of the network, 4')
     if args.degradation == 'bd' and args.lq_from_gt is None:
         ap.error('--degradation bd needs --lq-from-gt')
+    if args.lq_jpeg is not None and not 1 <= args.lq_jpeg[0] <= args.lq_jpeg[1] <= 100:
+        ap.error('--lq-jpeg takes 1 <= LO <= HI <= 100')
+    if args.lq_jpeg is None and (args.lq_jpeg_prob != 1.0 or args.val_jpeg_quality is not None):
+        ap.error('--lq-jpeg-prob and --val-jpeg-quality need --lq-jpeg')
+    if not 0 <= args.lq_jpeg_prob <= 1 or (args.val_jpeg_quality is not None and not 1 <= args.val_jpeg_quality <= 100):
+        ap.error('--lq-jpeg-prob is a probability, --val-jpeg-quality a quality in 1..100')
     if args.val_gt and args.val_lq is None and args.lq_from_gt is None:
         ap.error('--val-gt needs --val-lq (or --lq-from-gt)')
     return args
