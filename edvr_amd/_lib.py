@@ -10,7 +10,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('EDVR_AMD_LIB') or os.path.join(_HERE, 'lib', 'libedvr_amd.so')  # env: A/B kernel variants
 
 c_float_p = ctypes.c_void_p
-i32, i64, f32, sz = ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_size_t
+i32, i64, f32, sz, u32 = ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_size_t, ctypes.c_uint32
 vp = ctypes.c_void_p
 
 
@@ -109,6 +109,8 @@ PROTOTYPES = {
     'edvr_frame_sad_rgb_u8': (i32, [vp, vp, vp, i32, i32, i32, i64, vp]),
     'edvr_frame_sad_rgb_f32': (i32, [vp, vp, vp, i32, i32, i32, i64, vp]),
     'edvr_jpeg_roundtrip_u8': (i32, [vp, vp, vp, i32, i32, i32, i32, i64, i64, i32, vp]),
+    'edvr_degrade_u8': (i32, [vp, vp, vp, vp, i32, i32, i32, i64, i64, vp]),
+    'edvr_philox_words_u32': (i32, [vp, u32, u32, u32, i32, i32, vp]),
     'edvr_adam_chunk_bytes': (sz, []),
     'edvr_adam_multi_f32': (i32, [vp, i32, ctypes.c_float, ctypes.c_float, ctypes.c_float, vp]),
     'edvr_dcnv1_fwd_ws_bytes': (sz, [i32] * 12),
@@ -155,6 +157,7 @@ CONV_AUTO, CONV_DIRECT, CONV_WINOGRAD, CONV_WINOGRAD_F4, CONV_WINOGRAD_F4S = 0, 
 DTYPE_F32, DTYPE_F64, DTYPE_F16 = 0, 1, 2  # EDVR_DTYPE_*
 DCN_HALO_TAPWIN = 16  # EDVR_DCN_HALO_TAPWIN
 JPEG_SUBSAMPLINGS = {'420': 420, '444': 444}  # EDVR_JPEG_*
+DEGRADE_TILE, DEGRADE_MAX_KSIZE, DEGRADE_RECORD_INTS, DEGRADE_GRAY = 64, 21, 8, 1  # EDVR_DEGRADE_*
 
 _lib = None
 

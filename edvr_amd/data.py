@@ -101,15 +101,17 @@ def reds_keys(meta_info_file, val_partition):
 
 class ClipPlan:
     """Every random decision of one training sample: which frames, where to crop, how to augment."""
-    __slots__ = ('key', 'clip', 'center', 'frames', 'top', 'left', 'flags', 'jpeg_quality')
+    __slots__ = ('key', 'clip', 'center', 'frames', 'top', 'left', 'flags', 'jpeg_quality', 'degrade')
 
-    def __init__(self, key, clip, center, frames, top, left, flags, jpeg_quality=0):
+    def __init__(self, key, clip, center, frames, top, left, flags, jpeg_quality=0, degrade=None):
         self.key, self.clip, self.center, self.frames, self.top, self.left, self.flags = key, clip, center, frames, top, left, flags
         self.jpeg_quality = jpeg_quality  # of the LQ crops' JPEG round trip (lq_jpeg), all frames of the clip alike; 0 = none
+        self.degrade = degrade  # blur and noise of the LQ crops (lq_degrade; _draw_degrade), all frames of the clip alike; None = none
 
     def __repr__(self):
         jpeg = f', jpeg {self.jpeg_quality}' if self.jpeg_quality else ''
-        return f'ClipPlan({self.key}: frames {self.frames} of {self.clip}, crop ({self.top}, {self.left}), aug {self.flags}{jpeg})'
+        degrade = f", blur {self.degrade['blur']}, noise {self.degrade['noise']}" if self.degrade else ''
+        return f'ClipPlan({self.key}: frames {self.frames} of {self.clip}, crop ({self.top}, {self.left}), aug {self.flags}{jpeg}{degrade})'
 
 
 def _make_client(opt, client, with_lq):
@@ -172,13 +174,107 @@ def _draw_jpeg_quality(lq_jpeg, rng):
     return r.randint(lo, hi)
 
 
+LQ_DEGRADE_DEFAULTS = {'blur': {'ksize': [7, 21], 'sigma': [0.2, 3.0], 'iso_prob': 0.7, 'prob': 1.0},
+                       'noise': {'sigma': [1, 30], 'shot': [0.0025, 9.0], 'shot_prob': 0.5, 'gray_prob': 0.4, 'prob': 1.0}}
+
+
+def training_lq_degrade(opt):
+    """The `lq_degrade` key of a TRAINING option block: None without it, else {'blur': None | {...}, 'noise': None | {...}} with every
+    value of LQ_DEGRADE_DEFAULTS filled in and checked - the first-order ranges of Real-ESRGAN (its Poisson scale p is shot ~ p^2).  Either
+    key is optional.  blur: 'ksize' k | [lo, hi] (the odd sizes in it, 3 .. 21), 'sigma' s | [lo, hi] > 0, 'iso_prob', 'prob'; noise:
+    'sigma' (read noise, levels) s | [lo, hi] >= 0, 'shot' (variance per level) a | [lo, hi] > 0, 'shot_prob', 'gray_prob', 'prob'
+    (DESIGN 4.17).  ValueError for unknown keys, empty ranges and probabilities outside [0, 1]."""
+    from .ops import DEGRADE_MAX_KSIZE
+    if opt.get('lq_degrade') is None:
+        return None
+    spec = dict(opt['lq_degrade'])
+    if not spec or set(spec) - set(LQ_DEGRADE_DEFAULTS):
+        raise ValueError(f"lq_degrade takes 'blur' and / or 'noise', got {sorted(spec)}")
+
+    def number(v, what):
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v):
+            raise ValueError(f'lq_degrade: {what} must be a finite number, got {v!r}')
+        return v
+
+    def span(v, what, lo_ok):
+        v = list(v) if isinstance(v, (list, tuple)) else [v, v]
+        if len(v) != 2:
+            raise ValueError(f'lq_degrade: {what} is a number or [lo, hi], got {v!r}')
+        lo, hi = (number(x, what) for x in v)
+        if lo > hi or not lo_ok(lo):
+            raise ValueError(f'lq_degrade: {what} range [{lo}, {hi}] is empty or out of range')
+        return lo, hi
+
+    out = {'blur': None, 'noise': None}
+    for part, defaults in LQ_DEGRADE_DEFAULTS.items():
+        if spec.get(part) is None:
+            continue
+        given = dict(spec[part])
+        if set(given) - set(defaults):
+            raise ValueError(f'lq_degrade: {part} takes {sorted(defaults)}, got {sorted(given)}')
+        full = dict(defaults, **given)
+        for k in full:
+            if k.endswith('prob'):
+                if not 0 <= number(full[k], f'{part}.{k}') <= 1:
+                    raise ValueError(f'lq_degrade: {part}.{k} must lie in [0, 1], got {full[k]!r}')
+                full[k] = float(full[k])
+        if part == 'blur':
+            lo, hi = span(full['ksize'], 'blur.ksize', lambda v: True)
+            if lo != int(lo) or hi != int(hi):
+                raise ValueError(f"lq_degrade: blur.ksize takes ints, got {full['ksize']!r}")
+            full['ksize'] = [k for k in range(max(int(lo), 3) | 1, min(int(hi), DEGRADE_MAX_KSIZE) + 1, 2)]
+            if not full['ksize']:
+                raise ValueError(f'lq_degrade: blur.ksize range [{lo}, {hi}] holds no odd size in 3 .. {DEGRADE_MAX_KSIZE}')
+            full['sigma'] = tuple(float(v) for v in span(full['sigma'], 'blur.sigma', lambda v: v > 0))
+        else:
+            full['sigma'] = tuple(float(v) for v in span(full['sigma'], 'noise.sigma', lambda v: v >= 0))
+            full['shot'] = tuple(float(v) for v in span(full['shot'], 'noise.shot', lambda v: v > 0))
+        out[part] = full
+    return out
+
+
+def _draw_degrade(lq_degrade, rng):
+    """The blur and noise of one clip, made only where the option block has `lq_degrade`: None, or {'blur': None | (ksize, sigma_x,
+    sigma_y, theta), 'kernel': None | gaussian_blur_kernel of it, 'noise': None | (read_sigma, shot, gray), 'key': 64 bits} - what
+    ops.degrade takes as blur=, noise= and seed=, with frame_index = the frame's place in the clip.  The draws, on a stream
+    r = random.Random('lq_degrade' + repr(rng.getstate())) forked from the state _draw_jpeg_quality forks from, so that `rng` and every
+    other decision of the epoch stay what they are without the key: blur - [r.random() < prob where prob < 1], r.choice(odd sizes),
+    sigma_x = r.uniform(lo, hi), r.random() < iso_prob, else sigma_y = r.uniform(lo, hi) and theta = r.uniform(-pi, pi); noise -
+    [r.random() < prob where prob < 1], r.random() < shot_prob, then the read sigma r.uniform(lo, hi) or the shot exp(r.uniform(ln lo,
+    ln hi)), gray = r.random() < gray_prob; last key = r.getrandbits(64)."""
+    if lq_degrade is None:
+        return None
+    r = random.Random('lq_degrade' + repr(rng.getstate()))
+    blur = noise = kernel = None
+    b, n = lq_degrade['blur'], lq_degrade['noise']
+    if b is not None and (b['prob'] >= 1 or r.random() < b['prob']):
+        ksize = r.choice(b['ksize'])
+        sx = sy = r.uniform(*b['sigma'])
+        theta = 0.0
+        if not r.random() < b['iso_prob']:
+            sy = r.uniform(*b['sigma'])
+            theta = r.uniform(-math.pi, math.pi)
+        blur = (ksize, sx, sy, theta)
+        kernel = gaussian_blur_kernel(*blur)
+    if n is not None and (n['prob'] >= 1 or r.random() < n['prob']):
+        if r.random() < n['shot_prob']:
+            sigma, shot = 0.0, math.exp(r.uniform(math.log(n['shot'][0]), math.log(n['shot'][1])))
+        else:
+            sigma, shot = r.uniform(*n['sigma']), 0.0
+        noise = (sigma, shot, r.random() < n['gray_prob'])
+    if blur is None and noise is None:
+        return None
+    return {'blur': blur, 'kernel': kernel, 'noise': noise, 'key': r.getrandbits(64)}
+
+
 class REDSClipPlanner:
     """The decisions of REDSDataset.__getitem__ (reds_dataset.py:106-234), separated from the pixels.  `opt` has the reference's
     keys (dataroot_gt, dataroot_lq, meta_info_file, val_partition, io_backend, num_frame, gt_size, interval_list, random_reverse,
     use_flip, use_rot, scale).  plan(index, rng) draws from `rng` (a random.Random or the `random` module) exactly the values the
     reference draws, in its order: interval, [new centre frames while the window leaves 0..99], [reverse], crop top, crop left,
     [hflip], [vflip], [rot90] - and after them, with an `lq_jpeg` key only (training_lq_jpeg), the clip's JPEG quality, from a fork of
-    the stream (_draw_jpeg_quality) that leaves `rng` where the reference's draws left it."""
+    the stream (_draw_jpeg_quality) that leaves `rng` where the reference's draws left it; with an `lq_degrade` key only
+    (training_lq_degrade) the clip's blur and noise, from another fork of the same state (_draw_degrade)."""
 
     def __init__(self, opt, client=None):
         if opt.get('dataroot_flow') is not None:
@@ -192,6 +288,7 @@ class REDSClipPlanner:
         self.interval_list, self.random_reverse = opt['interval_list'], opt['random_reverse']
         self.lq_from_gt = training_lq_from_gt(opt)  # None: an LQ tree
         self.lq_jpeg = training_lq_jpeg(opt)  # None: no JPEG round trip of the LQ crops
+        self.lq_degrade = training_lq_degrade(opt)  # None: no blur or noise on the LQ crops
         self.client = _make_client(opt, client, self.lq_from_gt is None)
         self._shape = {}  # clip -> ((h_lq, w_lq), (h_gt, w_gt)): all frames of a REDS clip have one size
         # the one place the two sources of LQ part: where the sizes come from and what load() stages
@@ -238,7 +335,7 @@ class REDSClipPlanner:
             flags |= AUG_VFLIP
         if self.opt['use_rot'] and rng.random() < 0.5:
             flags |= AUG_ROT90
-        return ClipPlan(key, clip, center, frames, top, left, flags, _draw_jpeg_quality(self.lq_jpeg, rng))
+        return ClipPlan(key, clip, center, frames, top, left, flags, _draw_jpeg_quality(self.lq_jpeg, rng), _draw_degrade(self.lq_degrade, rng))
 
     def _load_gt_windows(self, plan, lq_out=None, gt_out=None):
         """load() without an LQ tree: lq is the pair (windows (t, e, pitch) uint8, table (t, 8) int32) of the decoded GT frames for
@@ -266,7 +363,7 @@ class Vimeo90KClipPlanner:
     the centred window of `num_frame` frames, and the reference's draws in its order: [reverse], crop top, crop left, [hflip],
     [vflip], [rot90].  The reference reverses its neighbour list IN PLACE (:82-83), so the orientation persists from one sample to
     the next: plan() keeps that state too (one planner = one dataset object).  With an `lq_jpeg` key the clip's JPEG quality is drawn last,
-    as REDSClipPlanner draws it."""
+    and with an `lq_degrade` key its blur and noise, as REDSClipPlanner draws them."""
 
     def __init__(self, opt, client=None):
         self.opt = opt
@@ -279,6 +376,7 @@ class Vimeo90KClipPlanner:
         self.random_reverse = opt['random_reverse']
         self.lq_from_gt = training_lq_from_gt(opt)  # None: an LQ tree
         self.lq_jpeg = training_lq_jpeg(opt)  # None: no JPEG round trip of the LQ crops
+        self.lq_degrade = training_lq_degrade(opt)  # None: no blur or noise on the LQ crops
         self.client = _make_client(opt, client, self.lq_from_gt is None)
         # the one place the two sources of LQ part: where the sizes come from and what load() stages
         if self.lq_from_gt is None:
@@ -317,7 +415,7 @@ class Vimeo90KClipPlanner:
             flags |= AUG_VFLIP
         if self.opt['use_rot'] and rng.random() < 0.5:
             flags |= AUG_ROT90
-        return ClipPlan(key, key, 4, frames, top, left, flags, _draw_jpeg_quality(self.lq_jpeg, rng))
+        return ClipPlan(key, key, 4, frames, top, left, flags, _draw_jpeg_quality(self.lq_jpeg, rng), _draw_degrade(self.lq_degrade, rng))
 
     def _load_gt_windows(self, plan, lq_out=None, gt_out=None):
         return self.windows.load(plan, [f'im{f}' for f in plan.frames], 'im4', lq_out, gt_out)
@@ -443,13 +541,89 @@ def imresize(img, scale, antialiasing=True):
     return ops.imresize(img, scale, antialiasing)
 
 
-def lq_from_gt(gt, scale, quantize=None, degradation='bi', jpeg_quality=None, jpeg_subsampling='420'):
+def gaussian_blur_kernel(ksize, sigma_x, sigma_y=None, theta=0.0):
+    """A Gaussian blur kernel for ops.degrade: int32 (ksize, ksize) Q20 weights that sum to exactly 1 << 20.  The real
+    weights are exp(-d' S^-1 d / 2) at the offsets d = (x, y) from the centre tap, S = R(theta) diag(sigma_x^2, sigma_y^2) R(theta)' -
+    isotropic where sigma_y is None or equal, else an ellipse whose sigma_x axis is turned by theta from the x axis - normalised in
+    float64 and rounded to Q20; the centre tap takes the rounding residue.  The integer blur then departs from the real-valued filter by
+    at most ksize^2 255 2^-21 levels (0.054 at 21 x 21).  ValueError for a ksize that is even or outside 3 .. 21 and sigmas that are not
+    finite and > 0."""
+    from .ops import DEGRADE_ONE, degrade_ksize
+    k = degrade_ksize(ksize)
+    sx = float(sigma_x)
+    sy = sx if sigma_y is None else float(sigma_y)
+    theta = float(theta)
+    if not (0 < sx < math.inf and 0 < sy < math.inf and math.isfinite(theta)):
+        raise ValueError(f'gaussian_blur_kernel: sigmas are finite and > 0 and theta is finite, got {sigma_x!r}, {sigma_y!r}, {theta!r}')
+    y, x = np.mgrid[-(k // 2):k // 2 + 1, -(k // 2):k // 2 + 1].astype(np.float64)
+    c, s = math.cos(theta), math.sin(theta)
+    u, v = c * x + s * y, -s * x + c * y  # R' d
+    w = np.exp(-0.5 * ((u / sx) ** 2 + (v / sy) ** 2))
+    q = np.rint(w / w.sum() * DEGRADE_ONE).astype(np.int64)
+    q[k // 2, k // 2] += DEGRADE_ONE - q.sum()
+    return q.astype(np.int32)
+
+
+def degrade_spec(degrade, what='degrade'):
+    """The `degrade` argument of lq_from_gt, checked: {'blur': {'ksize', 'sigma_x', 'sigma_y', 'theta'}, 'noise': {'sigma', 'shot',
+    'gray'}}, either key optional -> (kernel int32 (k, k) | None, (read_sigma, shot, gray) | None).  Without 'ksize' the kernel is the
+    smallest odd size that holds 3 sigma each side, 3 .. 21.  ValueError for unknown keys and bad values."""
+    from .ops import DEGRADE_MAX_KSIZE, degrade_noise
+    spec = dict(degrade)
+    if not spec or set(spec) - {'blur', 'noise'}:
+        raise ValueError(f"{what} takes 'blur' and / or 'noise', got {sorted(spec)}")
+    kernel = noise = None
+    if spec.get('blur') is not None:
+        b = dict(spec['blur'])
+        if set(b) - {'ksize', 'sigma_x', 'sigma_y', 'theta'} or 'sigma_x' not in b:
+            raise ValueError(f"{what}: blur takes 'sigma_x' and optionally 'ksize', 'sigma_y' and 'theta', got {sorted(b)}")
+        sy = b['sigma_x'] if b.get('sigma_y') is None else b['sigma_y']
+        ksize = b.get('ksize')
+        try:
+            if ksize is None:
+                reach = 3 * max(float(b['sigma_x']), float(sy))
+                ksize = min(max(2 * math.ceil(reach) + 1, 3), DEGRADE_MAX_KSIZE) if math.isfinite(reach) else 3
+            kernel = gaussian_blur_kernel(ksize, b['sigma_x'], sy, b.get('theta') or 0.0)
+        except TypeError:
+            raise ValueError(f'{what}: blur takes numbers, got {b!r}') from None
+    if spec.get('noise') is not None:
+        m = dict(spec['noise'])
+        if set(m) - {'sigma', 'shot', 'gray'}:
+            raise ValueError(f"{what}: noise takes 'sigma', 'shot' and 'gray', got {sorted(m)}")
+        noise = degrade_noise((m.get('sigma') or 0.0, m.get('shot') or 0.0, m.get('gray', False)))
+    return kernel, noise
+
+
+def degrade_options(blur_sigma=None, blur_size=None, noise_sigma=None, noise_shot=None, noise_gray=False):
+    """The `degrade` dict of lq_from_gt from the values the scripts take on their command lines (--blur-sigma SX [SY THETA], --blur-size K,
+    --noise-sigma S, --noise-shot A, --noise-gray), checked; None where none of them asks for anything.  ValueError otherwise."""
+    out = {}
+    if blur_sigma is not None:
+        if len(blur_sigma) not in (1, 3):
+            raise ValueError('--blur-sigma takes SX or SX SY THETA')
+        out['blur'] = dict(zip(('sigma_x', 'sigma_y', 'theta'), blur_sigma), ksize=blur_size)
+    elif blur_size is not None:
+        raise ValueError('--blur-size needs --blur-sigma')
+    if noise_sigma is not None or noise_shot is not None:
+        out['noise'] = {'sigma': noise_sigma or 0.0, 'shot': noise_shot or 0.0, 'gray': bool(noise_gray)}
+    elif noise_gray:
+        raise ValueError('--noise-gray needs --noise-sigma or --noise-shot')
+    if not out:
+        return None
+    degrade_spec(out, 'degrade')
+    return out
+
+
+def lq_from_gt(gt, scale, quantize=None, degradation='bi', jpeg_quality=None, jpeg_subsampling='420', degrade=None, seed=0):
     """The x`scale` LQ frames of GT frames (t, 3, H, W) float32 on the device, H and W multiples of `scale`.  degradation 'bi': imresize
     by 1 / scale, rounded to 8 bits when `quantize` (the default; what a stored PNG dataset contains) - generate_bicubic_img.m without
     the files.  'bd': duf_downsample, NOT rounded unless `quantize` is given as True - VideoTestDUFDataset feeds the float result to the
     network.  jpeg_quality 1 .. 100: the 8-bit LQ frames go through a baseline JPEG round trip (ops.jpeg_roundtrip, DESIGN 4.16;
     jpeg_subsampling '420' or '444') before they become float - compression artifacts on top of the downsampling; it works on bytes, so
-    it implies `quantize` and is a ValueError with quantize=False."""
+    it implies `quantize` and is a ValueError with quantize=False.  degrade = {'blur': {'ksize', 'sigma_x', 'sigma_y', 'theta'}, 'noise':
+    {'sigma', 'shot', 'gray'}} (either key optional; degrade_spec): the 8-bit LQ frames are blurred and made noisy (ops.degrade, DESIGN
+    4.17) after the downsampling and before the JPEG round trip - blur, noise, compression, the first-order degradation model; frame i of
+    the call takes its noise field from the 64-bit key `seed` and frame index i.  It too implies `quantize`."""
     from . import ops
     if degradation not in DEGRADATIONS:
         raise ValueError(f'degradation must be one of {DEGRADATIONS}, got {degradation!r}')
@@ -460,12 +634,19 @@ def lq_from_gt(gt, scale, quantize=None, degradation='bi', jpeg_quality=None, jp
         if quantize is not None and not quantize:
             raise ValueError('jpeg_quality compresses the 8-bit LQ frames: it cannot go with quantize=False')
         quantize = True
+    if degrade is not None:
+        kernel, noise = degrade_spec(degrade)
+        if quantize is not None and not quantize:
+            raise ValueError('degrade works on the 8-bit LQ frames: it cannot go with quantize=False')
+        quantize = True
     if quantize is None:
         quantize = degradation == 'bi'
     down = (lambda **kw: ops.imresize(gt, 1 / scale, **kw)) if degradation == 'bi' else (lambda **kw: ops.bd_downsample(gt, scale, **kw))
     if not quantize:
         return down()
     lq = down(out_dtype=torch.uint8)
+    if degrade is not None:
+        lq = ops.degrade(lq, kernel, noise, seed)
     if jpeg_quality is not None:
         lq = ops.jpeg_roundtrip(lq, jpeg_quality, jpeg_subsampling)
     return ops.frames_u8_to_f32(lq[None])[0]
@@ -690,7 +871,8 @@ class VideoTestClips:
     the device (lq_from_gt above; GT mod-cropped to a multiple of the scale first, as read_img_seq(require_mod_crop=True) does);
     lq_from_gt = {'scale': 4, 'degradation': 'bd'} makes them with duf_downsample instead (not quantised unless 'quantize' says so);
     'jpeg_quality': q (and 'jpeg_subsampling': '420' | '444') adds the JPEG round trip of lq_from_gt above, which implies 'quantize'
-    and is a ValueError with 'quantize': False."""
+    and is a ValueError with 'quantize': False; 'degrade': {'blur': ..., 'noise': ...} (and 'degrade_seed': a 64-bit key) adds the blur
+    and noise of lq_from_gt above, before the JPEG round trip, under the same rule - frame i of a read takes the noise field of index i."""
 
     def __init__(self, opt, device='cuda'):
         import glob
@@ -708,8 +890,9 @@ class VideoTestClips:
             jpeg = {k: self.lq_from_gt[k] for k in ('jpeg_quality', 'jpeg_subsampling') if self.lq_from_gt.get(k) is not None}
             if jpeg.get('jpeg_quality') is None:
                 jpeg = {}
-            self.lq_from_gt = {'scale': int(self.lq_from_gt['scale']), 'quantize': bool(self.lq_from_gt.get('quantize', degradation == 'bi' or bool(jpeg))),
-                               'degradation': degradation}
+            extra = {'degrade': self.lq_from_gt['degrade'], 'seed': self.lq_from_gt.get('degrade_seed')} if self.lq_from_gt.get('degrade') is not None else {}
+            self.lq_from_gt = {'scale': int(self.lq_from_gt['scale']),
+                               'quantize': bool(self.lq_from_gt.get('quantize', degradation == 'bi' or bool(jpeg) or bool(extra))), 'degradation': degradation}
             if jpeg:
                 from .ops import JPEG_SUBSAMPLINGS, jpeg_quality
                 jpeg['jpeg_quality'] = jpeg_quality(jpeg['jpeg_quality'], 'lq_from_gt: jpeg_quality')
@@ -718,6 +901,12 @@ class VideoTestClips:
                 if not self.lq_from_gt['quantize']:
                     raise ValueError("lq_from_gt: jpeg_quality compresses the 8-bit LQ frames: it cannot go with 'quantize': False")
             self._lq_jpeg = jpeg
+            if extra:
+                degrade_spec(extra['degrade'], 'lq_from_gt: degrade')  # ValueError now, not at the first clip
+                if not self.lq_from_gt['quantize']:
+                    raise ValueError("lq_from_gt: degrade works on the 8-bit LQ frames: it cannot go with 'quantize': False")
+                extra['seed'] = int(extra.get('seed') or 0)
+            self._lq_degrade = extra
             if degradation == 'bd':
                 if self.lq_from_gt['scale'] not in BD_SCALES:
                     raise ValueError(f"lq_from_gt: scale {self.lq_from_gt['scale']} is not one of {BD_SCALES} (degradation 'bd')")
@@ -780,7 +969,7 @@ class VideoTestClips:
         scale, quantize = self.lq_from_gt['scale'], self.lq_from_gt['quantize']
         gt = read_img_seq(paths_gt, self.device, require_mod_crop=True, scale=scale)
         src = gt if list(paths_lq) == list(paths_gt) else read_img_seq(paths_lq, self.device, require_mod_crop=True, scale=scale)
-        return lq_from_gt(src, scale, quantize, self.lq_from_gt['degradation'], **self._lq_jpeg), gt
+        return lq_from_gt(src, scale, quantize, self.lq_from_gt['degradation'], **self._lq_jpeg, **self._lq_degrade), gt
 
     def __getitem__(self, index):
         folder = self.data_info['folder'][index]
@@ -867,7 +1056,11 @@ class REDSDeviceLoader:
 
     opt['lq_jpeg'] = {'quality': q | [lo, hi], 'subsampling': '420', 'prob': 1.0} (training_lq_jpeg; either source of LQ): the LQ crop
     bytes of the batch go through ONE ops.jpeg_roundtrip launch at each clip's planned quality before the conversion to float - GT is
-    untouched, and the 8 x 8 block grid starts at the crop's corner."""
+    untouched, and the 8 x 8 block grid starts at the crop's corner.
+
+    opt['lq_degrade'] = {'blur': {...}, 'noise': {...}} (training_lq_degrade; either source of LQ): before that, ONE ops.degrade launch
+    blurs the LQ crop bytes with each clip's planned kernel and adds its planned noise, an independent field per frame, in crop
+    coordinates and before flip / rotation."""
 
     def __init__(self, opt, batch_size, device='cuda', rank=0, world_size=1, ratio=1, seed=0, num_threads=8, depth=3, drop_last=True,
                  client=None):
@@ -896,6 +1089,11 @@ class REDSDeviceLoader:
         self.slots = [(lq, torch.empty((batch_size, 1, P, P, 3), dtype=torch.uint8).pin_memory()) for lq in lq_slots]
         # lq_jpeg: one quality per LQ frame, in a pinned table per slot (copied on the loader's stream before the slot is handed back)
         self._jpeg_tables = [torch.zeros(batch_size * t, dtype=torch.int32).pin_memory() for _ in lq_slots] if self.planner.lq_jpeg else None
+        from . import ops
+        # lq_degrade: one record per LQ frame, then room for one 21 x 21 kernel per clip, in a pinned int32 buffer per slot: one copy
+        self._n_degrade_table = batch_size * t * ops.DEGRADE_RECORD_INTS
+        self._degrade_slots = ([torch.zeros(self._n_degrade_table + batch_size * ops.DEGRADE_MAX_KSIZE ** 2, dtype=torch.int32).pin_memory() for _ in lq_slots]
+                               if self.planner.lq_degrade else None)
         self.stream = torch.cuda.Stream(self.device)
         self.epoch = 0
         self._start()
@@ -953,6 +1151,27 @@ class REDSDeviceLoader:
         table = dev[self._n_win:].view(torch.int32).view(-1, LQ_WINDOW_RECORD_INTS)[:n * t]
         return ops.lq_crops_from_windows(windows, table, scale, degradation, table_host=self._tables[slot][:n * t]).view(n, t, p, p, 3)
 
+    def _degrade(self, slot, plans, lq_d):
+        """ONE ops.degrade launch on the LQ crop bytes (n, t, p, p, 3) of a batch: the t frames of a clip share its kernel and noise
+        setting and differ in the frame index, i.e. in their noise fields."""
+        from . import ops
+        n, t, p = len(plans), self.planner.num_frame, self.planner.lq_size
+        host = self._degrade_slots[slot]
+        table, weights = host[:n * t * ops.DEGRADE_RECORD_INTS].view(n, t, ops.DEGRADE_RECORD_INTS), host[self._n_degrade_table:]
+        offset = 0
+        for i, pl in enumerate(plans):
+            d = pl.degrade or {'kernel': None, 'noise': None, 'key': 0}
+            ksize = 0 if d['kernel'] is None else d['kernel'].shape[0]
+            if ksize:
+                weights[offset:offset + ksize * ksize] = torch.from_numpy(d['kernel'].ravel())
+            read, shot, gray = ops.degrade_noise(d['noise'])
+            table[i] = torch.tensor([ops.degrade_record(ksize, offset, read, shot, gray, d['key'], f) for f in range(t)], dtype=torch.int32)
+            offset += ksize * ksize
+        dev = host.to(self.device, non_blocking=True)
+        return ops.degrade(lq_d.view(n * t, p, p, 3), table=dev[:n * t * ops.DEGRADE_RECORD_INTS].view(n * t, ops.DEGRADE_RECORD_INTS),
+                           weights=dev[self._n_degrade_table:], table_host=table.view(n * t, ops.DEGRADE_RECORD_INTS),
+                           weights_host=weights).view(n, t, p, p, 3)
+
     def _preload(self):
         from . import ops
         item = self.ready.get()
@@ -967,6 +1186,8 @@ class REDSDeviceLoader:
         flags = bytes(p.flags for p in plans)
         with torch.cuda.stream(self.stream):
             lq_d, gt_d = self._lq_upload(slot, n), gt[:n].to(self.device, non_blocking=True)
+            if self._degrade_slots is not None and any(pl.degrade for pl in plans):  # blur and noise come first, on the upright crop
+                lq_d = self._degrade(slot, plans, lq_d)
             if self._jpeg_tables is not None:  # compression comes before flip / rotation: the block grid is anchored at the crop's corner
                 t, p = self.planner.num_frame, self.planner.lq_size
                 table = self._jpeg_tables[slot][:n * t]

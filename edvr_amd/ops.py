@@ -2232,3 +2232,196 @@ def jpeg_roundtrip(frames, quality, subsampling='420', out=None):
                                                                                  stride(out), _lib.JPEG_SUBSAMPLINGS[subsampling], _stream()),
                                               'edvr_jpeg_roundtrip_u8'), 0, nbytes)
     return out
+
+
+# ------------------------------------------------------------------------------------------------ blur and noise (csrc/degrade.hip)
+DEGRADE_TILE, DEGRADE_MAX_KSIZE, DEGRADE_RECORD_INTS = _lib.DEGRADE_TILE, _lib.DEGRADE_MAX_KSIZE, _lib.DEGRADE_RECORD_INTS
+DEGRADE_ONE = 1 << 20  # what the Q20 weights of a blur kernel sum to
+
+
+def degrade_ksize(ksize, what='ksize'):
+    """One blur kernel size as an int: odd, 3 .. 21; ValueError otherwise."""
+    import operator
+    try:
+        k = operator.index(ksize) if not isinstance(ksize, bool) else None
+    except TypeError:
+        k = None
+    if k is None:
+        raise ValueError(f'{what} must be an odd int in 3 .. {DEGRADE_MAX_KSIZE}, got {ksize!r}')
+    if not 3 <= k <= DEGRADE_MAX_KSIZE or k % 2 == 0:
+        raise ValueError(f'{what} {k} is not an odd size in 3 .. {DEGRADE_MAX_KSIZE}')
+    return k
+
+
+def degrade_blur(kernel, H=None, W=None):
+    """One blur kernel of ops.degrade as a contiguous int32 (k, k) NumPy array: k odd in 3 .. 21, every weight in 0 .. 2^20, the sum exactly
+    2^20 (data.gaussian_blur_kernel makes such kernels), and - given the frame - H, W > k // 2, so that one reflection covers the ring.
+    ValueError otherwise."""
+    import numpy as np
+    k = kernel.cpu().numpy() if torch.is_tensor(kernel) else np.asarray(kernel)
+    if k.dtype != np.int32 or k.ndim != 2 or k.shape[0] != k.shape[1]:
+        raise ValueError(f'a blur kernel is an int32 (k, k) array of Q20 weights, got {k.dtype} {k.shape}')
+    degrade_ksize(k.shape[0], 'the blur kernel: ksize')
+    if int(k.min()) < 0 or int(k.sum(dtype=np.int64)) != DEGRADE_ONE:
+        raise ValueError(f'the weights of a blur kernel are >= 0 and sum to 1 << 20, got a minimum of {int(k.min())} and a sum of {int(k.sum(dtype=np.int64))}')
+    if H is not None and min(H, W) <= k.shape[0] // 2:
+        raise ValueError(f'a {H} x {W} frame is not larger than the radius {k.shape[0] // 2} of its blur kernel: one reflection must cover the ring')
+    return np.ascontiguousarray(k)
+
+
+def degrade_noise(noise):
+    """One noise setting (read_sigma, shot, gray) of ops.degrade with both numbers as float32 values: read_sigma >= 0 in levels of 0 .. 255,
+    shot >= 0 the variance per level; ValueError for anything negative, NaN or infinite (as float32).  None is (0, 0, False): no noise."""
+    import numpy as np
+    if noise is None:
+        return 0.0, 0.0, False
+    try:
+        read, shot, gray = noise
+        with np.errstate(over='ignore'):
+            read, shot = float(np.float32(read)), float(np.float32(shot))
+    except (TypeError, ValueError):
+        raise ValueError(f'noise is (read_sigma, shot, gray), got {noise!r}') from None
+    if not (0 <= read < float('inf') and 0 <= shot < float('inf')):
+        raise ValueError(f'noise: read_sigma and shot are finite numbers >= 0, got {noise!r}')
+    return read + 0.0, shot + 0.0, bool(gray)
+
+
+def degrade_record(ksize, weight_offset, read_sigma, shot, gray, key, ctr_t):
+    """The eight int32 words of one image's record (include/edvr_amd.h: edvr_degrade_u8), from checked values."""
+    import struct
+    bits = lambda f: struct.unpack('<i', struct.pack('<f', f))[0]
+    s32 = lambda u: (u & 0xffffffff) - ((u & 0x80000000) << 1)
+    return [ksize, weight_offset, bits(read_sigma), bits(shot), int(bool(gray)), s32(key), s32(key >> 32), s32(ctr_t)]
+
+
+def degrade_table(n, H, W, blur=None, noise=None, seed=0, frame_index=None):
+    """The host side of ops.degrade: (table int32 (n, 8), weights int32 (m,) or None) as NumPy arrays, every argument checked (ValueError)
+    - one record per image, the distinct blur kernels once each in `weights`.  Arguments as ops.degrade takes them."""
+    import numpy as np
+    import operator
+
+    def per_image(v, single, what):
+        if single(v):
+            return [v] * n
+        v = list(v)
+        if len(v) != n:
+            raise ValueError(f'{len(v)} {what} for {n} frames')
+        return v
+    blurs = per_image(blur, lambda v: v is None or ((torch.is_tensor(v) or isinstance(v, np.ndarray)) and v.ndim == 2), 'blur kernels')
+    noises = per_image(noise, lambda v: v is None or (isinstance(v, (tuple, list)) and len(v) == 3 and not any(e is None or isinstance(e, (tuple, list)) for e in v)), 'noise settings')
+    try:
+        seeds = [operator.index(s) for s in per_image(seed, lambda v: not isinstance(v, (tuple, list, np.ndarray)) and not torch.is_tensor(v), 'seeds')]
+        frame_index = list(range(n)) if frame_index is None else [operator.index(t) for t in per_image(frame_index, lambda v: False, 'frame indices')]
+    except TypeError:
+        raise ValueError('seed and frame_index are ints') from None
+    if any(not -(1 << 63) <= s < 1 << 64 for s in seeds) or any(not 0 <= t < 1 << 32 for t in frame_index):
+        raise ValueError('a seed is a 64-bit key, a frame index lies in 0 .. 2^32 - 1')
+    table, parts, where, offset = np.zeros((n, DEGRADE_RECORD_INTS), np.int32), [], {}, 0
+    for i in range(n):
+        ksize = off = 0
+        if blurs[i] is not None:
+            if id(blurs[i]) not in where:
+                k = degrade_blur(blurs[i], H, W)
+                where[id(blurs[i])] = (k.shape[0], offset)
+                parts.append(k.ravel())
+                offset += k.size
+            ksize, off = where[id(blurs[i])]
+        table[i] = degrade_record(ksize, off, *degrade_noise(noises[i]), seeds[i], frame_index[i])
+    return table, (np.concatenate(parts) if parts else None)
+
+
+def check_degrade_table(table_host, n_weights, H, W, weights_host=None):
+    """What a launch of ops.degrade's table form checks on the host copy of its table (int32 (n, 8) NumPy array or CPU tensor): every
+    ksize, that the frame is larger than its radius, that the weights lie inside the buffer of n_weights words, the noise numbers - and,
+    given the host copy of the weights, their range and sum.  ValueError otherwise."""
+    import numpy as np
+    t = table_host.numpy() if torch.is_tensor(table_host) else np.asarray(table_host)
+    if t.dtype != np.int32 or t.ndim != 2 or t.shape[1] != DEGRADE_RECORD_INTS:
+        raise ValueError(f'table_host is the table as an int32 (n, {DEGRADE_RECORD_INTS}) host array')
+    w = None if weights_host is None else (weights_host.numpy() if torch.is_tensor(weights_host) else np.asarray(weights_host))
+    for i, (ksize, off) in enumerate(t[:, :2].tolist()):
+        if ksize == 0:
+            continue
+        degrade_ksize(ksize, f'record {i}: ksize')
+        if min(H, W) <= ksize // 2:
+            raise ValueError(f'record {i}: a {H} x {W} frame is not larger than the radius {ksize // 2} of its blur kernel')
+        if off < 0 or off + ksize * ksize > n_weights:
+            raise ValueError(f'record {i}: weights {off} .. {off + ksize * ksize} leave the buffer of {n_weights}')
+        if w is not None:
+            degrade_blur(w[off:off + ksize * ksize].reshape(ksize, ksize))
+    f = np.ascontiguousarray(t[:, 2:4]).view(np.float32)
+    if not np.all(np.isfinite(f)) or np.any(np.signbit(f)):
+        raise ValueError('a record has a negative, NaN or infinite read sigma or shot')
+
+
+def degrade(frames, blur=None, noise=None, seed=0, frame_index=None, out=None, table=None, weights=None, table_host=None, weights_host=None):
+    """Blur, then noise, on a batch of frames in ONE launch: the two steps of the first-order degradation model that come
+    before compression (jpeg_roundtrip).  frames: uint8 (n, H, W, 3) RGB on the GPU, 1 <= n <= 65535, each image dense, the images any
+    distance apart -> uint8 (n, H, W, 3).
+    blur: an int32 (k, k) kernel of Q20 weights (data.gaussian_blur_kernel; k odd in 3 .. 21, weights >= 0 that sum to 1 << 20) for every
+    image, or a sequence of n kernels / None (no blur).  The sum runs over the frame extended by the reflection that does not repeat the
+    edge sample and is exact: (acc + 2^19) >> 20 where there is no noise.
+    noise: (read_sigma, shot, gray) for every image or a sequence of n such tuples / None: Gaussian noise of standard deviation
+    sqrt(shot v + read_sigma^2) levels at a blurred value v, independent per channel or - gray - one draw for the three.
+    seed: one 64-bit key or n keys; frame_index: the third word of the Philox counter per image, default range(n) - a frame's noise
+    field is a function of (key, frame_index, x, y) alone.
+    The second form, degrade(frames, table=, weights=), takes the records and the weight buffer as int32 DEVICE tensors ((n, 8) and (m,);
+    degrade_table makes them on the host) and copies nothing: capturable in a graph.  table_host / weights_host: their host copies,
+    which are then checked before the launch; without them the caller vouches for the records.
+    out: a uint8 (n, H, W, 3) tensor of dense images to write into, which must not overlap `frames`.  ValueError for bad kernels, noise
+    numbers, layouts and an overlapping `out`; CPU tensors raise NotImplementedError: there is no fallback."""
+    for t in (frames, out, table, weights):
+        if t is not None and not t.is_cuda:
+            raise NotImplementedError('edvr_amd ops run on the GPU only (HIP/gfx950); got a CPU tensor')
+    if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[-1] != 3:
+        raise ValueError(f'frames are uint8 (n, H, W, 3), got {frames.dtype} {tuple(frames.shape)}')
+    n, H, W, _ = frames.shape
+    if not 0 < n <= 65535 or H < 1 or W < 1:
+        raise ValueError(f'degrade takes 1..65535 non-empty frames per call, got {tuple(frames.shape)}')
+
+    def dense(t):
+        return t[0].is_contiguous() and (n == 1 or t.stride(0) >= 3 * H * W)
+    if not dense(frames):
+        frames = frames.contiguous()
+    if table is None:
+        if weights is not None:
+            raise ValueError('weights go with a table')
+        table_np, weights_np = degrade_table(n, H, W, blur, noise, seed, frame_index)
+        table = torch.from_numpy(table_np).to(frames.device, non_blocking=True)
+        weights = None if weights_np is None else torch.from_numpy(weights_np).to(frames.device, non_blocking=True)
+    else:
+        if blur is not None or noise is not None or frame_index is not None:
+            raise ValueError('a table holds the blur, the noise and the frame indices: give one or the other')
+        if table.dtype != torch.int32 or tuple(table.shape) != (n, DEGRADE_RECORD_INTS) or not table.is_contiguous():
+            raise ValueError(f'a table is a contiguous int32 ({n}, {DEGRADE_RECORD_INTS}) device tensor, got {table.dtype} {tuple(table.shape)}')
+        if weights is not None and (weights.dtype != torch.int32 or weights.dim() != 1 or not weights.is_contiguous()):
+            raise ValueError(f'weights are a contiguous int32 (m,) device tensor, got {weights.dtype} {tuple(weights.shape)}')
+        if table_host is not None:
+            check_degrade_table(table_host, 0 if weights is None else weights.numel(), H, W, weights_host)
+    if out is None:
+        out = torch.empty((n, H, W, 3), dtype=torch.uint8, device=frames.device)
+    else:
+        if out.dtype != torch.uint8 or tuple(out.shape) != (n, H, W, 3) or not dense(out):
+            raise ValueError(f'out is a uint8 {(n, H, W, 3)} tensor of dense images, got {out.dtype} {tuple(out.shape)}')
+        (a0, a1), (b0, b1) = _byte_span(frames), _byte_span(out)
+        if a0 < b1 and b0 < a1:
+            raise ValueError('out overlaps the input')
+    stride = lambda t: t.stride(0) if n > 1 else 3 * H * W
+    nbytes = 6.0 * n * H * W + 4.0 * table.numel() + (4.0 * weights.numel() if weights is not None else 0.0)  # pixels in and out, table, weights
+    _run('degrade', lambda: _lib.check(_lib.lib().edvr_degrade_u8(_ptr(frames), _ptr(out), _ptr(table), _ptr(weights), n, H, W, stride(frames), stride(out),
+                                                                  _stream()), 'edvr_degrade_u8'), 0, nbytes)
+    return out
+
+
+def philox_words(key, ctr_t, H, W, device='cuda'):
+    """The generator of ops.degrade on its own: int32 (H, W, 4) on the GPU holding the BIT PATTERNS of the four uint32 words of
+    Philox4x32-10 (Random123) at counter (x, y, ctr_t, 0) and the 64-bit key `key` (low word first) - .view(numpy.uint32) on the host gives
+    the words.  ValueError for a key, ctr_t or size out of range."""
+    import operator
+    key, ctr_t, H, W = (operator.index(v) for v in (key, ctr_t, H, W))
+    if not -(1 << 63) <= key < 1 << 64 or not 0 <= ctr_t < 1 << 32 or H < 1 or W < 1 or H * W > 1 << 29:
+        raise ValueError(f'philox_words: key {key}, ctr_t {ctr_t} or size {H} x {W} out of range')
+    out = torch.empty((H, W, 4), dtype=torch.int32, device=device)
+    _run('philox_words', lambda: _lib.check(_lib.lib().edvr_philox_words_u32(_ptr(out), key & 0xffffffff, (key >> 32) & 0xffffffff, ctr_t, H, W, _stream()),
+                                            'edvr_philox_words_u32'), 0, 16.0 * H * W)
+    return out

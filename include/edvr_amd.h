@@ -771,6 +771,33 @@ int edvr_frame_sad_rgb_f32(const float *x, const float *prev, uint64_t *sad, int
 int edvr_jpeg_roundtrip_u8(const uint8_t *src, uint8_t *dst, const int32_t *quality, int quality_all, int n, int H, int W,
                            int64_t src_image_stride, int64_t dst_image_stride, int subsampling, edvr_stream_t stream);
 
+/* Blur and noise degradations (csrc/degrade.hip; definition: DESIGN 4.17): the steps of the first-order degradation model that come before
+ * compression, in ONE launch.  src, dst: n dense (H, W, 3) RGB byte images src_image_stride / dst_image_stride BYTES apart at any base
+ * address (0 = dense; a slice of a longer batch works); the two must not overlap (a workgroup reads pixels of its neighbours' tiles).
+ * table: DEVICE array of n records of EDVR_DEGRADE_RECORD_INTS int32 { ksize, weight_offset, read_bits, shot_bits, flags, key_lo, key_hi,
+ * ctr_t }.  Blur: ksize 0 (none) or odd 3 ... EDVR_DEGRADE_MAX_KSIZE, the image's ksize x ksize Q20 weights (each 0 ... 2^20, summing to
+ * 2^20) at weights[weight_offset ...]; acc = sum of weight x sample over the frame extended by the reflection that does not repeat the
+ * edge sample (H, W > ksize / 2), exact in 32-bit integers; acc = src << 20 at ksize 0.  Noise: read_bits / shot_bits are the float32 bit
+ * patterns of the read noise's sigma (levels) and the shot noise's variance per level; both +0.0: dst = (acc + 2^19) >> 20.  Otherwise v =
+ * float(acc) 2^-20, s = sqrt(shot v + read^2), dst = clamp(floor(v + s z + 0.5), 0, 255) with z standard normal: one Philox4x32-10 call per
+ * pixel, counter (x, y, ctr_t, 0), key (key_lo, key_hi), words r0 ... r3 -> Box-Muller pairs (r0, r1) -> z_R = rho cos phi, z_G = rho sin phi
+ * and (r2, r3) -> z_B = rho cos phi, rho = sqrt(-2 ln(((r >> 8) + 0.5) 2^-24)), phi = 2 pi (r' >> 8) 2^-24, float32; flags &
+ * EDVR_DEGRADE_GRAY: all three channels take z_R.  (x, y) are the coordinates in the image handed in.  weights may be NULL where no
+ * record blurs; the kernel treats any other ksize as 0 and clamps a weight to 0 ... 2^20, but trusts weight_offset: the caller checks its
+ * records (edvr_amd/ops.py does, on the host copy).  Grid (EDVR_DEGRADE_TILE^2 pixel tiles, n); dword accesses on a side whose base and
+ * stride are multiples of 4 where W % 4 == 0, bytes otherwise; same values either way.  EDVR_ERR_ARG: null src / dst / table, n outside
+ * 1 ... 65535, H or W < 1, H W > 2^29, an image stride shorter than 3 H W with n > 1.  No allocation, no wait, capturable in a graph. */
+#define EDVR_DEGRADE_TILE 64
+#define EDVR_DEGRADE_MAX_KSIZE 21
+#define EDVR_DEGRADE_RECORD_INTS 8
+#define EDVR_DEGRADE_GRAY 1
+int edvr_degrade_u8(const uint8_t *src, uint8_t *dst, const int32_t *table, const int32_t *weights, int n, int H, int W,
+                    int64_t src_image_stride, int64_t dst_image_stride, edvr_stream_t stream);
+/* The generator of edvr_degrade_u8 on its own: dst (H, W, 4) uint32, 16-byte aligned = the four words of Philox4x32-10 at
+ * counter (x, y, ctr_t, 0) and key (key_lo, key_hi) - multipliers 0xD2511F53, 0xCD9E8D57, Weyl constants 0x9E3779B9, 0xBB67AE85, as
+ * Random123 defines it.  EDVR_ERR_ARG: null or misaligned dst, H or W < 1, H W > 2^29. */
+int edvr_philox_words_u32(uint32_t *dst, uint32_t key_lo, uint32_t key_hi, uint32_t ctr_t, int H, int W, edvr_stream_t stream);
+
 /* Multi-tensor Adam step <- torch.optim.Adam.step() as the reference builds it (basicsr/models/edvr_model.py:21-53, parameter
  * groups with dcn_lr_mul; stepped in sr_model.py:112).  `chunk_table` is a DEVICE array of n_chunks records of
  * edvr_adam_chunk_bytes() = 64 bytes: { float *p; const float *g; float *m; float *v; int32 n (<= 65536 elements of one tensor);

@@ -17,7 +17,8 @@ between the two orders); alone it is an ensemble of the two time orders, with `-
 bicubic enlargement of the LQ frames beside the model under either degradation, as the published BI and BD tables do (the LQ frames
 themselves for --hr-in networks); `--jpeg-quality Q [--jpeg-subsampling 420|444]` sends the 8-bit LQ frames through a baseline JPEG round
 trip first (edvr_amd.ops.jpeg_roundtrip; with --degradation bd it rounds them to 8 bits), and the baseline then enlarges the compressed
-frames; `--json FILE` writes what is printed, and the degradation.  `--niqe PARAMS.npz` also scores every
+frames; `--blur-sigma SX [SY THETA] [--blur-size K]`, `--noise-sigma S`, `--noise-shot A`, `--noise-gray`, `--degrade-seed N` blur the
+8-bit LQ frames and add noise before that (edvr_amd.ops.degrade); `--json FILE` writes what is printed, and the degradation. `--niqe PARAMS.npz` also scores every
 output with the no-reference NIQE (metrics.calculate_niqe against BasicSR's niqe_pris_params.npz, lower is better) - the model's, the
 second pass's and the baseline's, next to their PSNRs.
 
@@ -87,6 +88,8 @@ def evaluate(args, log=print):
         opt['lq_from_gt'] = dict(scale=lq_from_gt, quantize=True) if degradation == 'bi' else dict(scale=lq_from_gt, degradation=degradation)
         if getattr(args, 'jpeg_quality', None) is not None:
             opt['lq_from_gt'].update(jpeg_quality=args.jpeg_quality, jpeg_subsampling=getattr(args, 'jpeg_subsampling', None) or '420')
+        if getattr(args, 'degrade', None) is not None:  # blur and noise on the 8-bit LQ frames, before the JPEG round trip
+            opt['lq_from_gt'].update(degrade=args.degrade, degrade_seed=getattr(args, 'degrade_seed', 0))
     ds = VideoTestClips(opt, device=device)
     # frames of any size (--pad-mode / --tile / --tile-overlap / --tile-blend): passed on only where given
     any_size = {k: (tuple(v) if k == 'tile' else v) for k in ('pad_mode', 'tile', 'tile_overlap', 'tile_blend')
@@ -169,6 +172,8 @@ def evaluate(args, log=print):
                       'degradation': degradation if args.lq is None else None}  # None: the LQ folder's, whatever made it
             if args.lq is None and getattr(args, 'jpeg_quality', None) is not None:
                 record.update(jpeg_quality=args.jpeg_quality, jpeg_subsampling=getattr(args, 'jpeg_subsampling', None) or '420')
+            if args.lq is None and getattr(args, 'degrade', None) is not None:
+                record.update(degrade=args.degrade, degrade_seed=getattr(args, 'degrade_seed', 0))
             if plus_kw:
                 record.update(self_ensemble=ensemble, self_ensemble_psnr=plus, self_ensemble_average=sum(plus.values()) / max(len(plus), 1))
                 if reverse:
@@ -196,6 +201,13 @@ def parse_args(argv=None):
     ap.add_argument('--jpeg-quality', type=int, default=None, metavar='Q',
                     help='with --lq-from-gt: the 8-bit LQ frames go through a baseline JPEG round trip at quality Q (1..100)')
     ap.add_argument('--jpeg-subsampling', choices=('420', '444'), default='420', help='chroma subsampling of --jpeg-quality')
+    ap.add_argument('--blur-sigma', type=float, nargs='+', default=None, metavar='S',
+                    help='with --lq-from-gt: Gaussian blur of the 8-bit LQ frames (edvr_amd.ops.degrade, before the JPEG round trip): SX, or SX SY THETA')
+    ap.add_argument('--blur-size', type=int, default=None, metavar='K', help='with --blur-sigma: the kernel size, odd, 3..21 (default: 3 sigma each side)')
+    ap.add_argument('--noise-sigma', type=float, default=None, metavar='S', help='with --lq-from-gt: read noise, standard deviation in levels of 0..255')
+    ap.add_argument('--noise-shot', type=float, default=None, metavar='A', help='with --lq-from-gt: shot noise, variance per level')
+    ap.add_argument('--noise-gray', action='store_true', help='one noise draw for the three channels of a pixel')
+    ap.add_argument('--degrade-seed', type=int, default=0, metavar='N', help='the 64-bit key of the noise fields')
     ap.add_argument('--bicubic-baseline', action='store_true', help='also report the PSNR of the bicubic enlargement of the LQ frames')
     ap.add_argument('--niqe', default=None, metavar='PARAMS.npz',
                     help="also report the no-reference NIQE of every output; PARAMS.npz is BasicSR's basicsr/metrics/niqe_pris_params.npz")
@@ -235,6 +247,13 @@ def parse_args(argv=None):
         ap.error('--lq-from-gt takes a scale in 1..8')
     if args.jpeg_quality is not None and (args.lq_from_gt is None or not 1 <= args.jpeg_quality <= 100):
         ap.error('--jpeg-quality takes a quality in 1..100 and needs --lq-from-gt')
+    from edvr_amd.data import degrade_options
+    try:
+        args.degrade = degrade_options(args.blur_sigma, args.blur_size, args.noise_sigma, args.noise_shot, args.noise_gray)
+    except ValueError as e:
+        ap.error(str(e))
+    if args.degrade is not None and args.lq_from_gt is None:
+        ap.error('--blur-sigma, --noise-sigma and --noise-shot need --lq-from-gt')
     if args.tile_blend is not None and args.tile is None:
         ap.error('--tile-blend needs --tile')
     if args.degradation == 'bd' and args.lq_from_gt not in (2, 3, 4):

@@ -15,6 +15,11 @@ written as 8-bit PNG.
 stored (edvr_amd.ops.jpeg_roundtrip, DESIGN 4.16: the bytes PIL's JPEG writer and reader return): compression artifacts in the LQ tree,
 still stored as PNG.  `--scale 1` skips the resize - imresize at scale 1 is the identity on bytes (tests/test_gpu_jpeg.py checks it), so
 nothing changes without the option - and with it compresses a tree at its own size (deblurcomp-style data).
+
+`--blur-sigma SX [SY THETA] [--blur-size K]`, `--noise-sigma S`, `--noise-shot A`, `--noise-gray`, `--degrade-seed N` blur the resized
+bytes with a Gaussian kernel and add read / shot noise on the device (edvr_amd.ops.degrade) before the JPEG round trip:
+blur, noise, compression, the first-order degradation model.  Frame i of a clip takes the noise field of index i of the key N, so a
+tree is reproducible whatever --batch is; `--scale 1` degrades a tree at its own size.
 """
 import argparse
 import os
@@ -58,6 +63,12 @@ def jpeg_u8(frames_u8, quality, subsampling, device):
     return ops.jpeg_roundtrip(torch.from_numpy(frames_u8).to(device), quality, subsampling).cpu().numpy()
 
 
+def degrade_u8(frames_u8, kernel, noise, seed, frame_index, device):
+    """(n, H, W, 3) uint8 host array -> the same blurred and noisy, on the device."""
+    from edvr_amd import ops
+    return ops.degrade(torch.from_numpy(frames_u8).to(device), kernel, noise, seed, frame_index).cpu().numpy()
+
+
 def load(path, scale):
     from edvr_amd.data import decode_image
     with open(path, 'rb') as f:
@@ -71,9 +82,11 @@ def save(path, rgb_u8):
 
 
 def make_lq(gt_root, lq_root, scale=4, antialiasing=True, batch=16, num_threads=8, device='cuda', log=print, degradation='bi',
-            jpeg_quality=None, jpeg_subsampling='420'):
-    """Returns the number of frames written.  jpeg_quality 1 .. 100: the stored bytes have been through a JPEG round trip."""
-    from edvr_amd.data import bd_shape, imresize_shape
+            jpeg_quality=None, jpeg_subsampling='420', degrade=None, degrade_seed=0):
+    """Returns the number of frames written.  jpeg_quality 1 .. 100: the stored bytes have been through a JPEG round trip.  degrade: the
+    dict data.lq_from_gt takes - blur and noise before that, frame i of a clip at frame index i of the key degrade_seed."""
+    from edvr_amd.data import bd_shape, degrade_spec, imresize_shape
+    kernel, noise = degrade_spec(degrade) if degrade is not None else (None, None)
     if degradation not in ('bi', 'bd'):
         raise ValueError(f"degradation must be 'bi' or 'bd', got {degradation!r}")
     if jpeg_quality is not None:
@@ -103,6 +116,8 @@ def make_lq(gt_root, lq_root, scale=4, antialiasing=True, batch=16, num_threads=
                     else:
                         imresize_shape(shape[0], shape[1], 1 / scale, antialiasing)  # likewise
                         out = resize_u8(np.stack([imgs[i] for i in sel]), scale, antialiasing, device)
+                    if degrade is not None:
+                        out = degrade_u8(out, kernel, noise, degrade_seed, [s0 + i for i in sel], device)
                     if jpeg_quality is not None:
                         out = jpeg_u8(out, jpeg_quality, jpeg_subsampling, device)
                     list(pool.map(lambda io: save(os.path.join(lq_root, clip, names[io[0]]), io[1]), zip(sel, out)))
@@ -122,6 +137,13 @@ def parse_args(argv=None):
     ap.add_argument('--jpeg-quality', type=int, default=None, metavar='Q',
                     help='send the LQ bytes through a baseline JPEG round trip at quality Q (1..100) before they are stored')
     ap.add_argument('--jpeg-subsampling', choices=('420', '444'), default='420', help='chroma subsampling of --jpeg-quality')
+    ap.add_argument('--blur-sigma', type=float, nargs='+', default=None, metavar='S',
+                    help='Gaussian blur of the LQ bytes: SX, or SX SY THETA (sigmas in pixels, THETA in radians from the x axis)')
+    ap.add_argument('--blur-size', type=int, default=None, metavar='K', help='with --blur-sigma: the kernel size, odd, 3..21 (default: 3 sigma each side)')
+    ap.add_argument('--noise-sigma', type=float, default=None, metavar='S', help='read noise: standard deviation in levels of 0..255')
+    ap.add_argument('--noise-shot', type=float, default=None, metavar='A', help='shot noise: variance per level (Poisson scale p: A = p^2)')
+    ap.add_argument('--noise-gray', action='store_true', help='one noise draw for the three channels of a pixel')
+    ap.add_argument('--degrade-seed', type=int, default=0, metavar='N', help='the 64-bit key of the noise fields')
     ap.add_argument('--batch', type=int, default=16, help='frames per launch')
     ap.add_argument('--threads', type=int, default=8, help='host threads decoding and encoding')
     args = ap.parse_args(argv)
@@ -133,13 +155,18 @@ def parse_args(argv=None):
         ap.error('--no-antialias belongs to --degradation bi')
     if args.jpeg_quality is not None and not 1 <= args.jpeg_quality <= 100:
         ap.error('--jpeg-quality must be an integer in 1..100')
+    from edvr_amd.data import degrade_options
+    try:
+        args.degrade = degrade_options(args.blur_sigma, args.blur_size, args.noise_sigma, args.noise_shot, args.noise_gray)
+    except ValueError as e:
+        ap.error(str(e))
     return args
 
 
 def main():
     args = parse_args()
     n = make_lq(args.gt_root, args.lq_root, args.scale, not args.no_antialias, args.batch, args.threads, degradation=args.degradation,
-                jpeg_quality=args.jpeg_quality, jpeg_subsampling=args.jpeg_subsampling)
+                jpeg_quality=args.jpeg_quality, jpeg_subsampling=args.jpeg_subsampling, degrade=args.degrade, degrade_seed=args.degrade_seed)
     print(f'{n} frame(s) -> {args.lq_root}')
 
 

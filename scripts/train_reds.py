@@ -10,6 +10,9 @@ EnlargedSampler, gradients all-reduced over RCCL by DDP.
 `--lq-jpeg LO HI [--lq-jpeg-prob P]` trains on compressed input: the LQ crops of a clip - from the LQ tree or made from GT - go through a
 baseline JPEG round trip on the device at a quality drawn from LO .. HI, with probability P (the dataset option `lq_jpeg`).
 Validation LQ frames made from GT are compressed at `--val-jpeg-quality` (default (LO + HI) // 2); a --val-lq tree is used as it is.
+`--lq-degrade` blurs the LQ crops of a clip and adds noise before that, on the device: the dataset option `lq_degrade` with its default
+block (edvr_amd.data.LQ_DEGRADE_DEFAULTS - the first-order blur and noise ranges of Real-ESRGAN).  Validation frames are
+not blurred or made noisy: there is no one setting to validate at.
 
 It is a caller of the hot path, kept small on purpose: option parsing, logging and the experiment directory layout of
 basicsr/train.py are out of scope (control plane).
@@ -68,6 +71,9 @@ def train(args, log=print):
     if lq_jpeg is not None:
         prob = getattr(args, 'lq_jpeg_prob', None)
         data_opt['lq_jpeg'] = dict(quality=list(lq_jpeg), subsampling='420', prob=1.0 if prob is None else prob)
+    if getattr(args, 'lq_degrade', False):
+        from edvr_amd.data import LQ_DEGRADE_DEFAULTS
+        data_opt['lq_degrade'] = {k: dict(v) for k, v in LQ_DEGRADE_DEFAULTS.items()}
     loader = REDSDeviceLoader(data_opt, args.batch, device=device, rank=rank, world_size=world, ratio=args.enlarge_ratio,
                               seed=args.seed, num_threads=args.threads)
     val = None
@@ -134,6 +140,8 @@ def parse_args(argv=None):
                     help="with --lq-from-gt: bi = MATLAB bicubic, bd = DUF's Gaussian blur and subsampling")
     ap.add_argument('--lq-jpeg', type=int, nargs=2, default=None, metavar=('LO', 'HI'),
                     help='JPEG-compress the LQ crops of each clip on the device at a quality drawn from LO..HI (4:2:0)')
+    ap.add_argument('--lq-degrade', action='store_true',
+                    help="blur the LQ crops and add noise on the device, per clip, from the default ranges of the dataset option 'lq_degrade'")
     ap.add_argument('--lq-jpeg-prob', type=float, default=1.0, metavar='P', help='with --lq-jpeg: the share of clips that are compressed')
     ap.add_argument('--val-jpeg-quality', type=int, default=None, metavar='Q',
                     help='with --lq-jpeg: the quality of validation LQ frames made from --val-gt (default (LO + HI) // 2)')
