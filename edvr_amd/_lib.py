@@ -109,6 +109,8 @@ PROTOTYPES = {
     'edvr_frame_sad_rgb_u8': (i32, [vp, vp, vp, i32, i32, i32, i64, vp]),
     'edvr_frame_sad_rgb_f32': (i32, [vp, vp, vp, i32, i32, i32, i64, vp]),
     'edvr_jpeg_roundtrip_u8': (i32, [vp, vp, vp, i32, i32, i32, i32, i64, i64, i32, vp]),
+    'edvr_mpeg_roundtrip_workspace': (sz, [i32, i32, i32, i32]),
+    'edvr_mpeg_roundtrip_u8': (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i64, i64, i64, i64, i32, i32, vp, sz, vp]),
     'edvr_degrade_u8': (i32, [vp, vp, vp, vp, i32, i32, i32, i64, i64, vp]),
     'edvr_philox_words_u32': (i32, [vp, u32, u32, u32, i32, i32, vp]),
     'edvr_adam_chunk_bytes': (sz, []),

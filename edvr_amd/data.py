@@ -101,17 +101,19 @@ def reds_keys(meta_info_file, val_partition):
 
 class ClipPlan:
     """Every random decision of one training sample: which frames, where to crop, how to augment."""
-    __slots__ = ('key', 'clip', 'center', 'frames', 'top', 'left', 'flags', 'jpeg_quality', 'degrade')
+    __slots__ = ('key', 'clip', 'center', 'frames', 'top', 'left', 'flags', 'jpeg_quality', 'degrade', 'mpeg_qscale')
 
-    def __init__(self, key, clip, center, frames, top, left, flags, jpeg_quality=0, degrade=None):
+    def __init__(self, key, clip, center, frames, top, left, flags, jpeg_quality=0, degrade=None, mpeg_qscale=0):
         self.key, self.clip, self.center, self.frames, self.top, self.left, self.flags = key, clip, center, frames, top, left, flags
         self.jpeg_quality = jpeg_quality  # of the LQ crops' JPEG round trip (lq_jpeg), all frames of the clip alike; 0 = none
         self.degrade = degrade  # blur and noise of the LQ crops (lq_degrade; _draw_degrade), all frames of the clip alike; None = none
+        self.mpeg_qscale = mpeg_qscale  # of the LQ crop clip's MPEG-style round trip (lq_mpeg); 0 = none
 
     def __repr__(self):
         jpeg = f', jpeg {self.jpeg_quality}' if self.jpeg_quality else ''
         degrade = f", blur {self.degrade['blur']}, noise {self.degrade['noise']}" if self.degrade else ''
-        return f'ClipPlan({self.key}: frames {self.frames} of {self.clip}, crop ({self.top}, {self.left}), aug {self.flags}{jpeg}{degrade})'
+        mpeg = f', mpeg {self.mpeg_qscale}' if self.mpeg_qscale else ''
+        return f'ClipPlan({self.key}: frames {self.frames} of {self.clip}, crop ({self.top}, {self.left}), aug {self.flags}{jpeg}{degrade}{mpeg})'
 
 
 def _make_client(opt, client, with_lq):
@@ -169,6 +171,48 @@ def _draw_jpeg_quality(lq_jpeg, rng):
         return 0
     lo, hi, _, prob = lq_jpeg
     r = random.Random(repr(rng.getstate()))
+    if prob < 1 and not r.random() < prob:
+        return 0
+    return r.randint(lo, hi)
+
+
+def training_lq_mpeg(opt):
+    """The `lq_mpeg` key of a TRAINING option block: None without it, else (lo, hi, search, prob) of
+    {'qscale': q | [lo, hi], 'search': 0 .. 15, 'prob': 0 .. 1}: the LQ crops of a clip go through ops.mpeg_roundtrip as one clip, its
+    first frame the only intra frame, at a quantiser scale drawn from lo .. hi with probability prob.  ValueError for a
+    qscale outside 1 .. 31, lo > hi, a search outside 0 .. 15, an unknown key and a prob outside [0, 1]."""
+    from .ops import mpeg_qscale, mpeg_search
+    if opt.get('lq_mpeg') is None:
+        return None
+    spec = dict(opt['lq_mpeg'])
+    unknown = set(spec) - {'qscale', 'search', 'prob'}
+    if unknown or 'qscale' not in spec:
+        raise ValueError(f"lq_mpeg takes 'qscale' and optionally 'search' and 'prob', got {sorted(spec)}")
+    qscale = spec['qscale']
+    if isinstance(qscale, (list, tuple)):
+        if len(qscale) != 2:
+            raise ValueError(f'lq_mpeg: qscale is an int or [lo, hi], got {qscale!r}')
+        lo, hi = (mpeg_qscale(q, 'lq_mpeg: qscale') for q in qscale)
+    else:
+        lo = hi = mpeg_qscale(qscale, 'lq_mpeg: qscale')
+    if lo > hi:
+        raise ValueError(f'lq_mpeg: qscale range [{lo}, {hi}] is empty')
+    search = mpeg_search(spec.get('search', 7), 'lq_mpeg: search')
+    prob = spec.get('prob', 1.0)
+    if isinstance(prob, bool) or not isinstance(prob, (int, float)) or not 0 <= prob <= 1:
+        raise ValueError(f'lq_mpeg: prob must be a number in [0, 1], got {prob!r}')
+    return lo, hi, search, float(prob)
+
+
+def _draw_mpeg_qscale(lq_mpeg, rng):
+    """The clip's quantiser scale, drawn only where the option block has `lq_mpeg`: [r.random() < prob where prob < 1], then
+    r.randint(lo, hi), on a stream r = random.Random('lq_mpeg' + repr(rng.getstate())) forked from the state _draw_jpeg_quality and
+    _draw_degrade fork from, so that `rng` and every other decision of the epoch - JPEG quality, blur and noise included - are what
+    they are without the key."""
+    if lq_mpeg is None:
+        return 0
+    lo, hi, _, prob = lq_mpeg
+    r = random.Random('lq_mpeg' + repr(rng.getstate()))
     if prob < 1 and not r.random() < prob:
         return 0
     return r.randint(lo, hi)
@@ -289,6 +333,7 @@ class REDSClipPlanner:
         self.lq_from_gt = training_lq_from_gt(opt)  # None: an LQ tree
         self.lq_jpeg = training_lq_jpeg(opt)  # None: no JPEG round trip of the LQ crops
         self.lq_degrade = training_lq_degrade(opt)  # None: no blur or noise on the LQ crops
+        self.lq_mpeg = training_lq_mpeg(opt)  # None: no MPEG-style round trip of the LQ crop clips
         self.client = _make_client(opt, client, self.lq_from_gt is None)
         self._shape = {}  # clip -> ((h_lq, w_lq), (h_gt, w_gt)): all frames of a REDS clip have one size
         # the one place the two sources of LQ part: where the sizes come from and what load() stages
@@ -335,7 +380,8 @@ class REDSClipPlanner:
             flags |= AUG_VFLIP
         if self.opt['use_rot'] and rng.random() < 0.5:
             flags |= AUG_ROT90
-        return ClipPlan(key, clip, center, frames, top, left, flags, _draw_jpeg_quality(self.lq_jpeg, rng), _draw_degrade(self.lq_degrade, rng))
+        return ClipPlan(key, clip, center, frames, top, left, flags, _draw_jpeg_quality(self.lq_jpeg, rng), _draw_degrade(self.lq_degrade, rng),
+                        _draw_mpeg_qscale(self.lq_mpeg, rng))
 
     def _load_gt_windows(self, plan, lq_out=None, gt_out=None):
         """load() without an LQ tree: lq is the pair (windows (t, e, pitch) uint8, table (t, 8) int32) of the decoded GT frames for
@@ -377,6 +423,7 @@ class Vimeo90KClipPlanner:
         self.lq_from_gt = training_lq_from_gt(opt)  # None: an LQ tree
         self.lq_jpeg = training_lq_jpeg(opt)  # None: no JPEG round trip of the LQ crops
         self.lq_degrade = training_lq_degrade(opt)  # None: no blur or noise on the LQ crops
+        self.lq_mpeg = training_lq_mpeg(opt)  # None: no MPEG-style round trip of the LQ crop clips
         self.client = _make_client(opt, client, self.lq_from_gt is None)
         # the one place the two sources of LQ part: where the sizes come from and what load() stages
         if self.lq_from_gt is None:
@@ -415,7 +462,8 @@ class Vimeo90KClipPlanner:
             flags |= AUG_VFLIP
         if self.opt['use_rot'] and rng.random() < 0.5:
             flags |= AUG_ROT90
-        return ClipPlan(key, key, 4, frames, top, left, flags, _draw_jpeg_quality(self.lq_jpeg, rng), _draw_degrade(self.lq_degrade, rng))
+        return ClipPlan(key, key, 4, frames, top, left, flags, _draw_jpeg_quality(self.lq_jpeg, rng), _draw_degrade(self.lq_degrade, rng),
+                        _draw_mpeg_qscale(self.lq_mpeg, rng))
 
     def _load_gt_windows(self, plan, lq_out=None, gt_out=None):
         return self.windows.load(plan, [f'im{f}' for f in plan.frames], 'im4', lq_out, gt_out)
@@ -614,7 +662,8 @@ def degrade_options(blur_sigma=None, blur_size=None, noise_sigma=None, noise_sho
     return out
 
 
-def lq_from_gt(gt, scale, quantize=None, degradation='bi', jpeg_quality=None, jpeg_subsampling='420', degrade=None, seed=0):
+def lq_from_gt(gt, scale, quantize=None, degradation='bi', jpeg_quality=None, jpeg_subsampling='420', degrade=None, seed=0,
+               mpeg_qscale=None, mpeg_gop=12, mpeg_search=7):
     """The x`scale` LQ frames of GT frames (t, 3, H, W) float32 on the device, H and W multiples of `scale`.  degradation 'bi': imresize
     by 1 / scale, rounded to 8 bits when `quantize` (the default; what a stored PNG dataset contains) - generate_bicubic_img.m without
     the files.  'bd': duf_downsample, NOT rounded unless `quantize` is given as True - VideoTestDUFDataset feeds the float result to the
@@ -623,7 +672,10 @@ def lq_from_gt(gt, scale, quantize=None, degradation='bi', jpeg_quality=None, jp
     it implies `quantize` and is a ValueError with quantize=False.  degrade = {'blur': {'ksize', 'sigma_x', 'sigma_y', 'theta'}, 'noise':
     {'sigma', 'shot', 'gray'}} (either key optional; degrade_spec): the 8-bit LQ frames are blurred and made noisy (ops.degrade, DESIGN
     4.17) after the downsampling and before the JPEG round trip - blur, noise, compression, the first-order degradation model; frame i of
-    the call takes its noise field from the 64-bit key `seed` and frame index i.  It too implies `quantize`."""
+    the call takes its noise field from the 64-bit key `seed` and frame index i.  It too implies `quantize`.  mpeg_qscale 1 .. 31: the
+    8-bit LQ frames of the call, ONE clip in order, go through the MPEG-style I / P round trip (ops.mpeg_roundtrip; an
+    intra frame every mpeg_gop frames, 0 = the first alone; motion search range mpeg_search 0 .. 15) between `degrade` and the JPEG
+    round trip - optics, sensor, codec; it implies `quantize` under the same rule."""
     from . import ops
     if degradation not in DEGRADATIONS:
         raise ValueError(f'degradation must be one of {DEGRADATIONS}, got {degradation!r}')
@@ -633,6 +685,11 @@ def lq_from_gt(gt, scale, quantize=None, degradation='bi', jpeg_quality=None, jp
             raise ValueError(f'jpeg_subsampling must be one of {ops.JPEG_SUBSAMPLINGS}, got {jpeg_subsampling!r}')
         if quantize is not None and not quantize:
             raise ValueError('jpeg_quality compresses the 8-bit LQ frames: it cannot go with quantize=False')
+        quantize = True
+    if mpeg_qscale is not None:
+        mpeg_qscale, mpeg_gop, mpeg_search = ops.mpeg_qscale(mpeg_qscale, 'mpeg_qscale'), ops.mpeg_gop(mpeg_gop, 'mpeg_gop'), ops.mpeg_search(mpeg_search, 'mpeg_search')
+        if quantize is not None and not quantize:
+            raise ValueError('mpeg_qscale compresses the 8-bit LQ frames: it cannot go with quantize=False')
         quantize = True
     if degrade is not None:
         kernel, noise = degrade_spec(degrade)
@@ -647,6 +704,8 @@ def lq_from_gt(gt, scale, quantize=None, degradation='bi', jpeg_quality=None, jp
     lq = down(out_dtype=torch.uint8)
     if degrade is not None:
         lq = ops.degrade(lq, kernel, noise, seed)
+    if mpeg_qscale is not None:
+        lq = ops.mpeg_roundtrip(lq, mpeg_qscale, mpeg_gop, mpeg_search)
     if jpeg_quality is not None:
         lq = ops.jpeg_roundtrip(lq, jpeg_quality, jpeg_subsampling)
     return ops.frames_u8_to_f32(lq[None])[0]
@@ -872,7 +931,9 @@ class VideoTestClips:
     lq_from_gt = {'scale': 4, 'degradation': 'bd'} makes them with duf_downsample instead (not quantised unless 'quantize' says so);
     'jpeg_quality': q (and 'jpeg_subsampling': '420' | '444') adds the JPEG round trip of lq_from_gt above, which implies 'quantize'
     and is a ValueError with 'quantize': False; 'degrade': {'blur': ..., 'noise': ...} (and 'degrade_seed': a 64-bit key) adds the blur
-    and noise of lq_from_gt above, before the JPEG round trip, under the same rule - frame i of a read takes the noise field of index i."""
+    and noise of lq_from_gt above, before the JPEG round trip, under the same rule - frame i of a read takes the noise field of index i;
+    'mpeg_qscale': q (and 'mpeg_gop', 'mpeg_search') adds the MPEG-style round trip of lq_from_gt above, the frames of a read being one
+    clip, between the two, under the same rule; it needs 'cache_data': True, so that a folder is read and coded whole."""
 
     def __init__(self, opt, device='cuda'):
         import glob
@@ -891,8 +952,22 @@ class VideoTestClips:
             if jpeg.get('jpeg_quality') is None:
                 jpeg = {}
             extra = {'degrade': self.lq_from_gt['degrade'], 'seed': self.lq_from_gt.get('degrade_seed')} if self.lq_from_gt.get('degrade') is not None else {}
+            mpeg = {k: self.lq_from_gt[k] for k in ('mpeg_qscale', 'mpeg_gop', 'mpeg_search') if self.lq_from_gt.get(k) is not None}
+            if mpeg.get('mpeg_qscale') is None:
+                mpeg = {}
             self.lq_from_gt = {'scale': int(self.lq_from_gt['scale']),
-                               'quantize': bool(self.lq_from_gt.get('quantize', degradation == 'bi' or bool(jpeg) or bool(extra))), 'degradation': degradation}
+                               'quantize': bool(self.lq_from_gt.get('quantize', degradation == 'bi' or bool(jpeg) or bool(extra) or bool(mpeg))),
+                               'degradation': degradation}
+            if mpeg:
+                from . import ops
+                mpeg = {'mpeg_qscale': ops.mpeg_qscale(mpeg['mpeg_qscale'], 'lq_from_gt: mpeg_qscale'),
+                        'mpeg_gop': ops.mpeg_gop(mpeg.get('mpeg_gop', 12), 'lq_from_gt: mpeg_gop'),
+                        'mpeg_search': ops.mpeg_search(mpeg.get('mpeg_search', 7), 'lq_from_gt: mpeg_search')}
+                if not self.lq_from_gt['quantize']:
+                    raise ValueError("lq_from_gt: mpeg_qscale compresses the 8-bit LQ frames: it cannot go with 'quantize': False")
+                if not self.cache_data:  # (a window read on its own repeats and reorders frames at the clip's ends)
+                    raise ValueError("lq_from_gt: mpeg_qscale codes a folder's frames as one clip: it needs 'cache_data': True")
+            self._lq_mpeg = mpeg
             if jpeg:
                 from .ops import JPEG_SUBSAMPLINGS, jpeg_quality
                 jpeg['jpeg_quality'] = jpeg_quality(jpeg['jpeg_quality'], 'lq_from_gt: jpeg_quality')
@@ -969,7 +1044,7 @@ class VideoTestClips:
         scale, quantize = self.lq_from_gt['scale'], self.lq_from_gt['quantize']
         gt = read_img_seq(paths_gt, self.device, require_mod_crop=True, scale=scale)
         src = gt if list(paths_lq) == list(paths_gt) else read_img_seq(paths_lq, self.device, require_mod_crop=True, scale=scale)
-        return lq_from_gt(src, scale, quantize, self.lq_from_gt['degradation'], **self._lq_jpeg, **self._lq_degrade), gt
+        return lq_from_gt(src, scale, quantize, self.lq_from_gt['degradation'], **self._lq_jpeg, **self._lq_degrade, **self._lq_mpeg), gt
 
     def __getitem__(self, index):
         folder = self.data_info['folder'][index]
@@ -1060,7 +1135,11 @@ class REDSDeviceLoader:
 
     opt['lq_degrade'] = {'blur': {...}, 'noise': {...}} (training_lq_degrade; either source of LQ): before that, ONE ops.degrade launch
     blurs the LQ crop bytes with each clip's planned kernel and adds its planned noise, an independent field per frame, in crop
-    coordinates and before flip / rotation."""
+    coordinates and before flip / rotation.
+
+    opt['lq_mpeg'] = {'qscale': q | [lo, hi], 'search': 7, 'prob': 1.0} (training_lq_mpeg; either source of LQ): between the two, ONE
+    ops.mpeg_roundtrip call codes the (n, t, p, p, 3) LQ crop bytes as n clips at each clip's planned quantiser scale - frame 0 of the
+    crop clip is the only intra frame, the macroblock grid and the clamp of the motion search are anchored at the crop."""
 
     def __init__(self, opt, batch_size, device='cuda', rank=0, world_size=1, ratio=1, seed=0, num_threads=8, depth=3, drop_last=True,
                  client=None):
@@ -1089,6 +1168,8 @@ class REDSDeviceLoader:
         self.slots = [(lq, torch.empty((batch_size, 1, P, P, 3), dtype=torch.uint8).pin_memory()) for lq in lq_slots]
         # lq_jpeg: one quality per LQ frame, in a pinned table per slot (copied on the loader's stream before the slot is handed back)
         self._jpeg_tables = [torch.zeros(batch_size * t, dtype=torch.int32).pin_memory() for _ in lq_slots] if self.planner.lq_jpeg else None
+        # lq_mpeg: one quantiser scale per clip, likewise
+        self._mpeg_tables = [torch.zeros(batch_size, dtype=torch.int32).pin_memory() for _ in lq_slots] if self.planner.lq_mpeg else None
         from . import ops
         # lq_degrade: one record per LQ frame, then room for one 21 x 21 kernel per clip, in a pinned int32 buffer per slot: one copy
         self._n_degrade_table = batch_size * t * ops.DEGRADE_RECORD_INTS
@@ -1188,6 +1269,10 @@ class REDSDeviceLoader:
             lq_d, gt_d = self._lq_upload(slot, n), gt[:n].to(self.device, non_blocking=True)
             if self._degrade_slots is not None and any(pl.degrade for pl in plans):  # blur and noise come first, on the upright crop
                 lq_d = self._degrade(slot, plans, lq_d)
+            if self._mpeg_tables is not None and any(pl.mpeg_qscale for pl in plans):  # the video codec, on the upright crop clip
+                table = self._mpeg_tables[slot][:n]
+                table.copy_(torch.tensor([pl.mpeg_qscale for pl in plans], dtype=torch.int32))
+                lq_d = ops.mpeg_roundtrip(lq_d, table.to(self.device, non_blocking=True), 0, self.planner.lq_mpeg[2])
             if self._jpeg_tables is not None:  # compression comes before flip / rotation: the block grid is anchored at the crop's corner
                 t, p = self.planner.num_frame, self.planner.lq_size
                 table = self._jpeg_tables[slot][:n * t]

@@ -2234,6 +2234,99 @@ def jpeg_roundtrip(frames, quality, subsampling='420', out=None):
     return out
 
 
+# ------------------------------------------------------------------------------------------------ MPEG-style round trip (csrc/mpeg.hip)
+MPEG_MAX_QSCALE, MPEG_MAX_SEARCH = 31, 15
+
+
+def _mpeg_int(v, lo, hi, what):
+    import operator
+    try:
+        i = operator.index(v) if not isinstance(v, bool) else None
+    except TypeError:
+        i = None
+    if i is None:
+        raise ValueError(f'{what} must be an int in {lo} .. {hi}, got {v!r}')
+    if not lo <= i <= hi:
+        raise ValueError(f'{what} {i} is outside {lo} .. {hi}')
+    return i
+
+
+def mpeg_qscale(qscale, what='qscale', allow_zero=False):
+    """One host-side quantiser scale as an int: 1 .. 31 (0 = no compression where `allow_zero`); ValueError otherwise."""
+    return _mpeg_int(qscale, 0 if allow_zero else 1, MPEG_MAX_QSCALE, what)
+
+
+def mpeg_gop(gop, what='gop'):
+    """The distance between intra frames as an int: positive, or 0 for frame 0 alone; ValueError otherwise."""
+    return _mpeg_int(gop, 0, 1 << 30, what)
+
+
+def mpeg_search(search, what='search'):
+    """The motion search range R as an int: 0 .. 15; ValueError otherwise."""
+    return _mpeg_int(search, 0, MPEG_MAX_SEARCH, what)
+
+
+def mpeg_roundtrip(frames, qscale, gop=12, search=7, out=None):
+    """What an MPEG-2 / MPEG-4-SP shaped I / P video encoder followed by a decoder makes of clips of frames, in t + 2 launches (DESIGN
+    4.18, M1 - M7): 4:2:0 planes, frame i intra (the MPEG-2 default matrix scaled by qscale) if i == 0 or gop > 0 and i % gop == 0, else
+    predicted from the reconstruction of frame i - 1 by a full search over [-search, search]^2 per 16 x 16 macroblock, with a half-sample
+    chroma vector and a flat dead-zone quantiser on the residual.  All integers; entropy coding is not performed and no stream
+    compatibility is claimed.  frames: uint8 (b, t, H, W, 3), or (t, H, W, 3) for one clip, RGB in display order on the GPU, b t <= 65535,
+    H, W <= 16384, each frame dense, frames at least a frame and clips at least a clip apart (any other view is gathered first) -> the same shape.  qscale: an int 1 .. 31 for every clip, a
+    sequence of b ints, or an int32 (b,) device tensor (which the kernels clamp to 0 .. 31); an entry 0 copies that clip through unchanged.
+    out: a uint8 tensor of the same shape under the same layout rule (no two frames share a byte), which must not overlap `frames`.  ValueError for values out of range, wrong
+    dtypes or shapes and an overlapping `out`; CPU tensors raise NotImplementedError: there is no fallback."""
+    for t_ in (frames, out, qscale if torch.is_tensor(qscale) else None):
+        if t_ is not None and not t_.is_cuda:
+            raise NotImplementedError('edvr_amd ops run on the GPU only (HIP/gfx950); got a CPU tensor')
+    gop, search = mpeg_gop(gop), mpeg_search(search)
+    if frames.dtype != torch.uint8 or frames.dim() not in (4, 5) or frames.shape[-1] != 3:
+        raise ValueError(f'frames are uint8 (b, t, H, W, 3) or (t, H, W, 3), got {frames.dtype} {tuple(frames.shape)}')
+    one = frames.dim() == 4
+    if one:
+        frames = frames[None]
+        if out is not None and out.dim() == 4:
+            out = out[None]
+    b, t, H, W, _ = frames.shape
+    if b < 1 or t < 1 or b * t > 65535 or not 1 <= H <= 16384 or not 1 <= W <= 16384:
+        raise ValueError(f'mpeg_roundtrip takes 1..65535 non-empty frames of at most 16384 x 16384 per call, got {tuple(frames.shape)}')
+    fb = 3 * H * W
+
+    def dense(x):
+        fs_ = x.stride(1) if t > 1 else fb  # no two frames share a byte: a frame stride of at least a frame, a clip stride of at least a clip
+        return x[0, 0].is_contiguous() and fs_ >= fb and (b == 1 or x.stride(0) >= (t - 1) * fs_ + fb)
+    if not dense(frames):
+        frames = frames.contiguous()
+    table, q_all = None, 0
+    if torch.is_tensor(qscale):
+        if qscale.dtype != torch.int32 or tuple(qscale.shape) != (b,):
+            raise ValueError(f'a qscale table is an int32 ({b},) device tensor, got {qscale.dtype} {tuple(qscale.shape)}')
+        table = qscale.contiguous()
+    elif isinstance(qscale, (list, tuple)):
+        if len(qscale) != b:
+            raise ValueError(f'{len(qscale)} qscales for {b} clips')
+        table = torch.tensor([mpeg_qscale(q, allow_zero=True) for q in qscale], dtype=torch.int32).to(frames.device, non_blocking=True)
+    else:
+        q_all = mpeg_qscale(qscale, allow_zero=True)
+    if out is None:
+        out = torch.empty((b, t, H, W, 3), dtype=torch.uint8, device=frames.device)
+    else:
+        if out.dtype != torch.uint8 or tuple(out.shape) != (b, t, H, W, 3) or not dense(out):
+            raise ValueError(f'out is a uint8 {(b, t, H, W, 3)} tensor of dense frames, got {out.dtype} {tuple(out.shape)}')
+        (a0, a1), (b0, b1) = _byte_span(frames), _byte_span(out)
+        if a0 < b1 and b0 < a1:
+            raise ValueError('out overlaps the input')
+    nbytes = int(_lib.lib().edvr_mpeg_roundtrip_workspace(b, t, H, W))
+    ws = workspace(nbytes, frames.device)
+    fs = lambda x: x.stride(1) if t > 1 else fb
+    cs = lambda x: x.stride(0) if b > 1 else t * fs(x)
+    booked = 6.0 * b * t * H * W + 2.0 * nbytes + (4.0 * b if table is not None else 0.0)  # pixels in and out, the planes written and read
+    _run('mpeg_roundtrip', lambda: _lib.check(_lib.lib().edvr_mpeg_roundtrip_u8(_ptr(frames), _ptr(out), _ptr(table), q_all, b, t, H, W, cs(frames), fs(frames),
+                                                                                 cs(out), fs(out), gop, search, _ptr(ws), nbytes, _stream()),
+                                              'edvr_mpeg_roundtrip_u8'), 0, booked)
+    return out[0] if one else out
+
+
 # ------------------------------------------------------------------------------------------------ blur and noise (csrc/degrade.hip)
 DEGRADE_TILE, DEGRADE_MAX_KSIZE, DEGRADE_RECORD_INTS = _lib.DEGRADE_TILE, _lib.DEGRADE_MAX_KSIZE, _lib.DEGRADE_RECORD_INTS
 DEGRADE_ONE = 1 << 20  # what the Q20 weights of a blur kernel sum to

@@ -771,6 +771,24 @@ int edvr_frame_sad_rgb_f32(const float *x, const float *prev, uint64_t *sad, int
 int edvr_jpeg_roundtrip_u8(const uint8_t *src, uint8_t *dst, const int32_t *quality, int quality_all, int n, int H, int W,
                            int64_t src_image_stride, int64_t dst_image_stride, int subsampling, edvr_stream_t stream);
 
+/* MPEG-style round trip (csrc/mpeg.hip; definition: DESIGN 4.18, M1 - M7): dst = what an I / P video encoder at `qscale` followed by a
+ * decoder returns for b clips of t frames in display order - the planes, 13-bit DCT and colour steps of the JPEG round trip above for
+ * 4:2:0; frame i is intra (MPEG-2 default intra matrix scaled by qscale) if i == 0 or gop > 0 and i % gop == 0, else predicted from the
+ * reconstruction of frame i - 1: per 16 x 16 macroblock a full search over [-search, search]^2 (SAD + qscale (|dy| + |dx|), ties to the
+ * first candidate in raster order, reads clamped to the padded plane), a half-sample chroma vector, a flat dead-zone quantiser on the
+ * residual.  Entropy coding is not performed and no stream compatibility is claimed.  src, dst: dense (H, W, 3) RGB byte frames,
+ * *_frame_stride BYTES apart within a clip and *_clip_stride between clips - at least a frame and at least a clip, (t - 1) frame strides
+ * and a frame, so that no two frames share a byte - at any base address (0 = dense); src and dst must not overlap.
+ * qscale: a DEVICE table of b int32, each clamped to 0 ... 31 by the kernels, or NULL: qscale_all, 0 ... 31, for every clip; 0 copies that
+ * clip through unchanged.  ws: edvr_mpeg_roundtrip_workspace(b, t, H, W) bytes, 4-byte aligned (source and reconstructed planes of every
+ * frame: 2 b t 1.5 Hp Wp, Hp = 16 ceil(H / 16), Wp likewise); 0 for sizes the entry point rejects.  t + 2 kernel launches.
+ * EDVR_ERR_ARG: null src / dst, b, t, H or W < 1, b t > 65535, H or W > 16384, gop < 0, search outside 0 ... 15, qscale_all outside
+ * 0 ... 31 with a NULL table, a frame stride shorter than 3 H W or a clip stride shorter than a clip, a workspace too small or misaligned.  No allocation, no wait. */
+size_t edvr_mpeg_roundtrip_workspace(int b, int t, int H, int W);
+int edvr_mpeg_roundtrip_u8(const uint8_t *src, uint8_t *dst, const int32_t *qscale, int qscale_all, int b, int t, int H, int W,
+                           int64_t src_clip_stride, int64_t src_frame_stride, int64_t dst_clip_stride, int64_t dst_frame_stride, int gop,
+                           int search, void *ws, size_t ws_bytes, edvr_stream_t stream);
+
 /* Blur and noise degradations (csrc/degrade.hip; definition: DESIGN 4.17): the steps of the first-order degradation model that come before
  * compression, in ONE launch.  src, dst: n dense (H, W, 3) RGB byte images src_image_stride / dst_image_stride BYTES apart at any base
  * address (0 = dense; a slice of a longer batch works); the two must not overlap (a workgroup reads pixels of its neighbours' tiles).

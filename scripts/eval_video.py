@@ -18,7 +18,9 @@ bicubic enlargement of the LQ frames beside the model under either degradation, 
 themselves for --hr-in networks); `--jpeg-quality Q [--jpeg-subsampling 420|444]` sends the 8-bit LQ frames through a baseline JPEG round
 trip first (edvr_amd.ops.jpeg_roundtrip; with --degradation bd it rounds them to 8 bits), and the baseline then enlarges the compressed
 frames; `--blur-sigma SX [SY THETA] [--blur-size K]`, `--noise-sigma S`, `--noise-shot A`, `--noise-gray`, `--degrade-seed N` blur the
-8-bit LQ frames and add noise before that (edvr_amd.ops.degrade); `--json FILE` writes what is printed, and the degradation. `--niqe PARAMS.npz` also scores every
+8-bit LQ frames and add noise before that (edvr_amd.ops.degrade); `--mpeg-qscale Q [--mpeg-gop N] [--mpeg-search R]` codes
+each folder's 8-bit LQ frames, read whole as one clip, with the MPEG-style I / P round trip between the two (edvr_amd.ops.mpeg_roundtrip,
+DESIGN 4.18; a folder is one piece, so any --mpeg-gop, 0 included, is what the whole clip gives); `--json FILE` writes what is printed, and the degradation. `--niqe PARAMS.npz` also scores every
 output with the no-reference NIQE (metrics.calculate_niqe against BasicSR's niqe_pris_params.npz, lower is better) - the model's, the
 second pass's and the baseline's, next to their PSNRs.
 
@@ -88,6 +90,8 @@ def evaluate(args, log=print):
         opt['lq_from_gt'] = dict(scale=lq_from_gt, quantize=True) if degradation == 'bi' else dict(scale=lq_from_gt, degradation=degradation)
         if getattr(args, 'jpeg_quality', None) is not None:
             opt['lq_from_gt'].update(jpeg_quality=args.jpeg_quality, jpeg_subsampling=getattr(args, 'jpeg_subsampling', None) or '420')
+        if getattr(args, 'mpeg_qscale', None) is not None:  # each folder coded whole as one clip, between blur / noise and the JPEG round trip
+            opt['lq_from_gt'].update(mpeg_qscale=args.mpeg_qscale, mpeg_gop=getattr(args, 'mpeg_gop', 12), mpeg_search=getattr(args, 'mpeg_search', 7))
         if getattr(args, 'degrade', None) is not None:  # blur and noise on the 8-bit LQ frames, before the JPEG round trip
             opt['lq_from_gt'].update(degrade=args.degrade, degrade_seed=getattr(args, 'degrade_seed', 0))
     ds = VideoTestClips(opt, device=device)
@@ -170,6 +174,8 @@ def evaluate(args, log=print):
             import json
             record = {'psnr': summary, 'average': sum(summary.values()) / max(len(summary), 1),
                       'degradation': degradation if args.lq is None else None}  # None: the LQ folder's, whatever made it
+            if args.lq is None and getattr(args, 'mpeg_qscale', None) is not None:
+                record.update(mpeg_qscale=args.mpeg_qscale, mpeg_gop=getattr(args, 'mpeg_gop', 12), mpeg_search=getattr(args, 'mpeg_search', 7))
             if args.lq is None and getattr(args, 'jpeg_quality', None) is not None:
                 record.update(jpeg_quality=args.jpeg_quality, jpeg_subsampling=getattr(args, 'jpeg_subsampling', None) or '420')
             if args.lq is None and getattr(args, 'degrade', None) is not None:
@@ -201,6 +207,11 @@ def parse_args(argv=None):
     ap.add_argument('--jpeg-quality', type=int, default=None, metavar='Q',
                     help='with --lq-from-gt: the 8-bit LQ frames go through a baseline JPEG round trip at quality Q (1..100)')
     ap.add_argument('--jpeg-subsampling', choices=('420', '444'), default='420', help='chroma subsampling of --jpeg-quality')
+    ap.add_argument('--mpeg-qscale', type=int, default=None, metavar='Q',
+                    help='with --lq-from-gt: code the 8-bit LQ frames of each folder, one clip read whole, with the MPEG-style I / P round trip at '
+                         'quantiser scale Q (1..31; edvr_amd.ops.mpeg_roundtrip), after blur and noise and before the JPEG round trip')
+    ap.add_argument('--mpeg-gop', type=int, default=12, metavar='N', help='with --mpeg-qscale: an intra frame every N frames (0: the first alone)')
+    ap.add_argument('--mpeg-search', type=int, default=7, metavar='R', help='with --mpeg-qscale: the motion search range, 0..15')
     ap.add_argument('--blur-sigma', type=float, nargs='+', default=None, metavar='S',
                     help='with --lq-from-gt: Gaussian blur of the 8-bit LQ frames (edvr_amd.ops.degrade, before the JPEG round trip): SX, or SX SY THETA')
     ap.add_argument('--blur-size', type=int, default=None, metavar='K', help='with --blur-sigma: the kernel size, odd, 3..21 (default: 3 sigma each side)')
@@ -245,6 +256,10 @@ def parse_args(argv=None):
         ap.error('give exactly one of --lq and --lq-from-gt')
     if args.lq_from_gt is not None and not 1 <= args.lq_from_gt <= 8:
         ap.error('--lq-from-gt takes a scale in 1..8')
+    if args.mpeg_qscale is not None and (args.lq_from_gt is None or not 1 <= args.mpeg_qscale <= 31):
+        ap.error('--mpeg-qscale takes a quantiser scale in 1..31 and needs --lq-from-gt')
+    if args.mpeg_gop < 0 or not 0 <= args.mpeg_search <= 15:
+        ap.error('--mpeg-gop must not be negative, --mpeg-search is an integer in 0..15')
     if args.jpeg_quality is not None and (args.lq_from_gt is None or not 1 <= args.jpeg_quality <= 100):
         ap.error('--jpeg-quality takes a quality in 1..100 and needs --lq-from-gt')
     from edvr_amd.data import degrade_options

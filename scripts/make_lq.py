@@ -20,6 +20,12 @@ nothing changes without the option - and with it compresses a tree at its own si
 bytes with a Gaussian kernel and add read / shot noise on the device (edvr_amd.ops.degrade) before the JPEG round trip:
 blur, noise, compression, the first-order degradation model.  Frame i of a clip takes the noise field of index i of the key N, so a
 tree is reproducible whatever --batch is; `--scale 1` degrades a tree at its own size.
+
+`--mpeg-qscale Q [--mpeg-gop N] [--mpeg-search R]` codes each clip's frames, in order, with the MPEG-style I / P round trip on the device
+(edvr_amd.ops.mpeg_roundtrip, DESIGN 4.18: an intra frame every N frames, motion-compensated prediction between them) after blur and
+noise and before the JPEG round trip.  A clip is handled in pieces that start on an intra frame - the largest multiple of N within
+--batch, or N itself - so the tree is what the whole clip in one call gives, whatever --batch is; `--mpeg-gop 0` (the first frame alone
+is intra) takes each clip in one piece.  The frames of a clip must then have one size.
 """
 import argparse
 import os
@@ -63,6 +69,20 @@ def jpeg_u8(frames_u8, quality, subsampling, device):
     return ops.jpeg_roundtrip(torch.from_numpy(frames_u8).to(device), quality, subsampling).cpu().numpy()
 
 
+def mpeg_u8(frames_u8, qscale, gop, search, device):
+    """(t, H, W, 3) uint8 host array, one clip in order -> the same after the MPEG-style round trip on the device."""
+    from edvr_amd import ops
+    return ops.mpeg_roundtrip(torch.from_numpy(frames_u8).to(device), qscale, gop, search).cpu().numpy()
+
+
+def gop_pieces(n, batch, gop):
+    """[(first, past the last)] frames of the pieces a clip of n frames is handled in: `batch` frames each without the MPEG round trip
+    (gop None); with it every piece starts on an intra frame - the largest multiple of gop within batch, or gop itself - and gop 0 is
+    the whole clip."""
+    step = batch if gop is None else n if gop == 0 else max(gop, batch // gop * gop)
+    return [(s0, min(s0 + step, n)) for s0 in range(0, n, max(step, 1))]
+
+
 def degrade_u8(frames_u8, kernel, noise, seed, frame_index, device):
     """(n, H, W, 3) uint8 host array -> the same blurred and noisy, on the device."""
     from edvr_amd import ops
@@ -82,9 +102,10 @@ def save(path, rgb_u8):
 
 
 def make_lq(gt_root, lq_root, scale=4, antialiasing=True, batch=16, num_threads=8, device='cuda', log=print, degradation='bi',
-            jpeg_quality=None, jpeg_subsampling='420', degrade=None, degrade_seed=0):
+            jpeg_quality=None, jpeg_subsampling='420', degrade=None, degrade_seed=0, mpeg_qscale=None, mpeg_gop=12, mpeg_search=7):
     """Returns the number of frames written.  jpeg_quality 1 .. 100: the stored bytes have been through a JPEG round trip.  degrade: the
-    dict data.lq_from_gt takes - blur and noise before that, frame i of a clip at frame index i of the key degrade_seed."""
+    dict data.lq_from_gt takes - blur and noise before that, frame i of a clip at frame index i of the key degrade_seed.  mpeg_qscale
+    1 .. 31: between the two, each clip goes through the MPEG-style round trip, in pieces cut at multiples of mpeg_gop (gop_pieces)."""
     from edvr_amd.data import bd_shape, degrade_spec, imresize_shape
     kernel, noise = degrade_spec(degrade) if degrade is not None else (None, None)
     if degradation not in ('bi', 'bd'):
@@ -94,6 +115,9 @@ def make_lq(gt_root, lq_root, scale=4, antialiasing=True, batch=16, num_threads=
         jpeg_quality = ops.jpeg_quality(jpeg_quality, 'jpeg_quality')
         if jpeg_subsampling not in ops.JPEG_SUBSAMPLINGS:
             raise ValueError(f'jpeg_subsampling must be one of {ops.JPEG_SUBSAMPLINGS}, got {jpeg_subsampling!r}')
+    if mpeg_qscale is not None:
+        from edvr_amd import ops
+        mpeg_qscale, mpeg_gop, mpeg_search = ops.mpeg_qscale(mpeg_qscale, 'mpeg_qscale'), ops.mpeg_gop(mpeg_gop, 'mpeg_gop'), ops.mpeg_search(mpeg_search, 'mpeg_search')
     if degradation == 'bd':
         bd_shape(7, 7, scale)  # a scale DUF's kernel does not have: ValueError before any file is read
     clips = walk(gt_root)
@@ -103,9 +127,11 @@ def make_lq(gt_root, lq_root, scale=4, antialiasing=True, batch=16, num_threads=
     with ThreadPoolExecutor(num_threads) as pool:
         for clip, frames in clips:
             os.makedirs(os.path.join(lq_root, clip), exist_ok=True)
-            for s0 in range(0, len(frames), batch):
-                names = frames[s0:s0 + batch]
+            for s0, s1 in gop_pieces(len(frames), batch, mpeg_gop if mpeg_qscale is not None else None):
+                names = frames[s0:s1]
                 imgs = list(pool.map(lambda n: load(os.path.join(gt_root, clip, n), scale), names))
+                if mpeg_qscale is not None and len({im.shape for im in imgs}) > 1:
+                    raise ValueError(f'{clip}: the MPEG round trip predicts a frame from the one before: the frames of a clip must have one size')
                 for shape in sorted({im.shape for im in imgs}):  # one launch per frame size (a clip normally has one)
                     sel = [i for i, im in enumerate(imgs) if im.shape == shape]
                     if degradation == 'bd':
@@ -118,6 +144,8 @@ def make_lq(gt_root, lq_root, scale=4, antialiasing=True, batch=16, num_threads=
                         out = resize_u8(np.stack([imgs[i] for i in sel]), scale, antialiasing, device)
                     if degrade is not None:
                         out = degrade_u8(out, kernel, noise, degrade_seed, [s0 + i for i in sel], device)
+                    if mpeg_qscale is not None:
+                        out = mpeg_u8(out, mpeg_qscale, mpeg_gop, mpeg_search, device)
                     if jpeg_quality is not None:
                         out = jpeg_u8(out, jpeg_quality, jpeg_subsampling, device)
                     list(pool.map(lambda io: save(os.path.join(lq_root, clip, names[io[0]]), io[1]), zip(sel, out)))
@@ -137,6 +165,10 @@ def parse_args(argv=None):
     ap.add_argument('--jpeg-quality', type=int, default=None, metavar='Q',
                     help='send the LQ bytes through a baseline JPEG round trip at quality Q (1..100) before they are stored')
     ap.add_argument('--jpeg-subsampling', choices=('420', '444'), default='420', help='chroma subsampling of --jpeg-quality')
+    ap.add_argument('--mpeg-qscale', type=int, default=None, metavar='Q',
+                    help='code each clip with the MPEG-style I / P round trip at quantiser scale Q (1..31) before the JPEG round trip')
+    ap.add_argument('--mpeg-gop', type=int, default=12, metavar='N', help='with --mpeg-qscale: an intra frame every N frames (0: the first alone)')
+    ap.add_argument('--mpeg-search', type=int, default=7, metavar='R', help='with --mpeg-qscale: the motion search range, 0..15')
     ap.add_argument('--blur-sigma', type=float, nargs='+', default=None, metavar='S',
                     help='Gaussian blur of the LQ bytes: SX, or SX SY THETA (sigmas in pixels, THETA in radians from the x axis)')
     ap.add_argument('--blur-size', type=int, default=None, metavar='K', help='with --blur-sigma: the kernel size, odd, 3..21 (default: 3 sigma each side)')
@@ -155,6 +187,10 @@ def parse_args(argv=None):
         ap.error('--no-antialias belongs to --degradation bi')
     if args.jpeg_quality is not None and not 1 <= args.jpeg_quality <= 100:
         ap.error('--jpeg-quality must be an integer in 1..100')
+    if args.mpeg_qscale is not None and not 1 <= args.mpeg_qscale <= 31:
+        ap.error('--mpeg-qscale must be an integer in 1..31')
+    if args.mpeg_gop < 0 or not 0 <= args.mpeg_search <= 15:
+        ap.error('--mpeg-gop must not be negative, --mpeg-search must be an integer in 0..15')
     from edvr_amd.data import degrade_options
     try:
         args.degrade = degrade_options(args.blur_sigma, args.blur_size, args.noise_sigma, args.noise_shot, args.noise_gray)
@@ -166,7 +202,8 @@ def parse_args(argv=None):
 def main():
     args = parse_args()
     n = make_lq(args.gt_root, args.lq_root, args.scale, not args.no_antialias, args.batch, args.threads, degradation=args.degradation,
-                jpeg_quality=args.jpeg_quality, jpeg_subsampling=args.jpeg_subsampling, degrade=args.degrade, degrade_seed=args.degrade_seed)
+                jpeg_quality=args.jpeg_quality, jpeg_subsampling=args.jpeg_subsampling, degrade=args.degrade, degrade_seed=args.degrade_seed,
+                mpeg_qscale=args.mpeg_qscale, mpeg_gop=args.mpeg_gop, mpeg_search=args.mpeg_search)
     print(f'{n} frame(s) -> {args.lq_root}')
 
 

@@ -13,6 +13,9 @@ Validation LQ frames made from GT are compressed at `--val-jpeg-quality` (defaul
 `--lq-degrade` blurs the LQ crops of a clip and adds noise before that, on the device: the dataset option `lq_degrade` with its default
 block (edvr_amd.data.LQ_DEGRADE_DEFAULTS - the first-order blur and noise ranges of Real-ESRGAN).  Validation frames are
 not blurred or made noisy: there is no one setting to validate at.
+`--lq-mpeg LO HI [--lq-mpeg-prob P]` codes the LQ crops of a clip as one clip with the MPEG-style I / P round trip on the device, between
+the two, at a quantiser scale drawn from LO .. HI (the dataset option `lq_mpeg`); validation LQ frames made from GT are
+coded folder by folder at `--val-mpeg-qscale` (default (LO + HI) // 2).
 
 It is a caller of the hot path, kept small on purpose: option parsing, logging and the experiment directory layout of
 basicsr/train.py are out of scope (control plane).
@@ -71,6 +74,10 @@ def train(args, log=print):
     if lq_jpeg is not None:
         prob = getattr(args, 'lq_jpeg_prob', None)
         data_opt['lq_jpeg'] = dict(quality=list(lq_jpeg), subsampling='420', prob=1.0 if prob is None else prob)
+    lq_mpeg = getattr(args, 'lq_mpeg', None)
+    if lq_mpeg is not None:
+        prob = getattr(args, 'lq_mpeg_prob', None)
+        data_opt['lq_mpeg'] = dict(qscale=list(lq_mpeg), search=7, prob=1.0 if prob is None else prob)
     if getattr(args, 'lq_degrade', False):
         from edvr_amd.data import LQ_DEGRADE_DEFAULTS
         data_opt['lq_degrade'] = {k: dict(v) for k, v in LQ_DEGRADE_DEFAULTS.items()}
@@ -85,6 +92,9 @@ def train(args, log=print):
             if lq_jpeg is not None:
                 val_q = getattr(args, 'val_jpeg_quality', None)
                 val_opt['lq_from_gt']['jpeg_quality'] = (lq_jpeg[0] + lq_jpeg[1]) // 2 if val_q is None else val_q
+            if lq_mpeg is not None:
+                val_q = getattr(args, 'val_mpeg_qscale', None)
+                val_opt['lq_from_gt']['mpeg_qscale'] = (lq_mpeg[0] + lq_mpeg[1]) // 2 if val_q is None else val_q
         val = VideoTestClips(val_opt, device=device)
     if state is not None:
         resume_training(state, [opt], [sched])
@@ -142,6 +152,12 @@ def parse_args(argv=None):
                     help='JPEG-compress the LQ crops of each clip on the device at a quality drawn from LO..HI (4:2:0)')
     ap.add_argument('--lq-degrade', action='store_true',
                     help="blur the LQ crops and add noise on the device, per clip, from the default ranges of the dataset option 'lq_degrade'")
+    ap.add_argument('--lq-mpeg', type=int, nargs=2, default=None, metavar=('LO', 'HI'),
+                    help='code the LQ crops of a clip as one clip with the MPEG-style I / P round trip on the device (DESIGN 4.18), its first '
+                         'frame intra, at a quantiser scale drawn from LO..HI (1..31), between blur / noise and the JPEG round trip')
+    ap.add_argument('--lq-mpeg-prob', type=float, default=1.0, metavar='P', help='with --lq-mpeg: the share of clips that are coded')
+    ap.add_argument('--val-mpeg-qscale', type=int, default=None, metavar='Q',
+                    help='with --lq-mpeg: the quantiser scale of validation LQ frames made from --val-gt (default (LO + HI) // 2)')
     ap.add_argument('--lq-jpeg-prob', type=float, default=1.0, metavar='P', help='with --lq-jpeg: the share of clips that are compressed')
     ap.add_argument('--val-jpeg-quality', type=int, default=None, metavar='Q',
                     help='with --lq-jpeg: the quality of validation LQ frames made from --val-gt (default (LO + HI) // 2)')
@@ -180,6 +196,12 @@ def parse_args(argv=None):
         ap.error('--degradation bd needs --lq-from-gt')
     if args.lq_jpeg is not None and not 1 <= args.lq_jpeg[0] <= args.lq_jpeg[1] <= 100:
         ap.error('--lq-jpeg takes 1 <= LO <= HI <= 100')
+    if args.lq_mpeg is not None and not 1 <= args.lq_mpeg[0] <= args.lq_mpeg[1] <= 31:
+        ap.error('--lq-mpeg takes 1 <= LO <= HI <= 31')
+    if args.lq_mpeg is None and (args.lq_mpeg_prob != 1.0 or args.val_mpeg_qscale is not None):
+        ap.error('--lq-mpeg-prob and --val-mpeg-qscale need --lq-mpeg')
+    if not 0 <= args.lq_mpeg_prob <= 1 or (args.val_mpeg_qscale is not None and not 1 <= args.val_mpeg_qscale <= 31):
+        ap.error('--lq-mpeg-prob is a probability, --val-mpeg-qscale a quantiser scale in 1..31')
     if args.lq_jpeg is None and (args.lq_jpeg_prob != 1.0 or args.val_jpeg_quality is not None):
         ap.error('--lq-jpeg-prob and --val-jpeg-quality need --lq-jpeg')
     if not 0 <= args.lq_jpeg_prob <= 1 or (args.val_jpeg_quality is not None and not 1 <= args.val_jpeg_quality <= 100):
