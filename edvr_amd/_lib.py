@@ -59,6 +59,9 @@ PROTOTYPES = {
     'edvr_dcnv2_fwd_f32': (i32, [vp] * 6 + [i32] * 12 + [i64, i64, i32, i32, vp, sz, vp]),
     'edvr_dcnv2_fwd_split_f32': (i32, [vp] * 6 + [i32] * 12 + [i64, i64, i32, i32, vp, sz, vp, vp]),
     'edvr_dcnv2_fwd_split_applies': (i32, [vp] + [i32] * 13),
+    'edvr_dcnv2_split_packed_weight_elems': (sz, [i32, i32]),
+    'edvr_dcnv2_split_pack_weight_f32': (i32, [vp, vp, i32, i32, vp]),
+    'edvr_dcnv2_fwd_split_packed_f32': (i32, [vp] * 6 + [i32] * 12 + [i64, i64, i32, i32, vp, vp]),
     'edvr_dcnv2_fwd_kernel_name': (i32, [vp] + [i32] * 13 + [ctypes.c_char_p, sz]),
     'edvr_dcnv2_bwd_ws_bytes': (sz, [i32] * 12),
     'edvr_dcnv2_any_ws_bytes': (sz, [i32] * 13),
@@ -124,6 +127,9 @@ PROTOTYPES = {
     'edvr_dcnv2_bwd_split_applies': (i32, []),
     'edvr_tsa_temporal_f32': (i32, [vp] * 5 + [i32] * 4 + [vp]),
     'edvr_tsa_temporal_pair_f32': (i32, [vp] * 5 + [i32] * 4 + [vp]),
+    'edvr_tsa_front_supported': (i32, [i32] * 6),
+    'edvr_tsa_front_applies': (i32, [i32] * 12 + [vp, vp, vp]),
+    'edvr_tsa_front_f32': (i32, [vp, vp, i64, vp, vp] + [vp, vp, i32, vp, vp] * 2 + [i32] * 6 + [vp]),
     'edvr_pool_maxavg_3x3s2_f32': (i32, [vp, vp, i32, i32, i32, i32, vp]),
     'edvr_upsample2x_f32': (i32, [vp, vp, i32, i32, i32, f32, vp]),
     'edvr_tsa_combine_f32': (i32, [vp, vp, vp, vp, i64, vp]),

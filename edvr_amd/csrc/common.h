@@ -147,8 +147,15 @@ bool dcn_tapwin_supported(int C, int Co, int H, int W, int kh, int kw, int strid
 int dcn_tapwin_forward(const float *x, const float *offset, const float *mask, const float *wpk, const float *bias, float *y, int B, int C,
                        int H, int W, int Co, int dg, int64_t off_bs, int64_t msk_bs, int act, hipStream_t stream);
 
-// dcn_tapwin_s.hip: the tap-window kernel with split fp32 operands on the f16 matrix pipe; packs its own weights into `wpk`
+// dcn_tapwin_s.hip: the tap-window kernel with split fp32 operands on the f16 matrix pipe.  dcn_tapwin_split_forward packs its own
+// weights into the workspace `wpk` at every call; dcn_tapwin_split_pack + dcn_tapwin_split_forward_packed: the same two steps apart,
+// for a caller that keeps the packed buffer (dcn_tapwin_split_wpk_elems dwords) across calls
 bool dcn_tapwin_split_enabled();
+size_t dcn_tapwin_split_wpk_elems(int Co, int C);
+int dcn_tapwin_split_pack(const float *weight, unsigned *wpk, int Co, int C, hipStream_t stream);
+int dcn_tapwin_split_forward_packed(const float *x, const float *offset, const float *mask, const unsigned *wpk, const float *bias, float *y,
+                                    int B, int C, int H, int W, int Co, int dg, int64_t off_bs, int64_t msk_bs, int act, const float *xm_amax,
+                                    hipStream_t stream);
 int dcn_tapwin_split_forward(const float *x, const float *offset, const float *mask, const float *weight, unsigned *wpk, const float *bias, float *y,
                              int B, int C, int H, int W, int Co, int dg, int64_t off_bs, int64_t msk_bs, int act, const float *xm_amax,
                              hipStream_t stream);

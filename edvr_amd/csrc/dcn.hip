@@ -791,6 +791,27 @@ int edvr_dcnv2_fwd_split_applies(const float *x, int B, int C, int H, int W, int
           dcn_tapwin_supported(C, Co, H, W, kh, kw, s.stride, s.pad, s.dil, groups, dg) && (reinterpret_cast<uintptr_t>(x) & 15) == 0) ? 1 : 0;
 }
 
+size_t edvr_dcnv2_split_packed_weight_elems(int Co, int C) { return (Co > 0 && C > 0) ? edvr::dcn_tapwin_split_wpk_elems(Co, C) : 0; }
+
+int edvr_dcnv2_split_pack_weight_f32(const float *weight, void *wpk, int Co, int C, edvr_stream_t stream) {
+  return edvr::dcn_tapwin_split_pack(weight, static_cast<unsigned *>(wpk), Co, C, edvr::as_stream(stream));
+}
+
+int edvr_dcnv2_fwd_split_packed_f32(const float *x, const float *offset, const float *mask, const void *wpk, const float *bias,
+                                    float *y, int B, int C, int H, int W, int Co, int kh, int kw, int stride, int pad, int dil, int groups,
+                                    int dg, int64_t offset_bstride, int64_t mask_bstride, int act, int halo_hint, const float *xm_amax,
+                                    edvr_stream_t stream) {
+  using namespace edvr;
+  EDVR_REQUIRE(x && offset && mask && wpk && y && xm_amax, "dcnv2_fwd_split_packed: null pointer");
+  EDVR_REQUIRE(edvr_dcnv2_fwd_split_applies(x, B, C, H, W, Co, kh, kw, stride, pad, dil, groups, dg, halo_hint),
+               "dcnv2_fwd_split_packed: the split tap-window kernel does not take this call");
+  DcnShape s;
+  const int rc = dcn_fill_shape(s, B, C, H, W, Co, kh, kw, stride, pad, dil, groups, dg, offset_bstride, mask_bstride);
+  if (rc) return rc;
+  return dcn_tapwin_split_forward_packed(x, offset, mask, static_cast<const unsigned *>(wpk), bias, y, B, C, H, W, Co, dg, s.off_bs, s.msk_bs, act,
+                                         xm_amax, as_stream(stream));
+}
+
 int edvr_dcnv2_fwd_kernel_name(const float *x, int B, int C, int H, int W, int Co, int kh, int kw, int stride, int pad, int dil, int groups,
                                int dg, int halo_hint, char *buf, size_t buf_len) {
   using namespace edvr;

@@ -523,16 +523,35 @@ bool dcn_tapwin_split_enabled() {
   return on;
 }
 
-// wpk: workspace of 16 + C * 9 * cop dwords, filled here (scale pre-pass + packing: two small launches per call, like dcn_fused_pack)
-int dcn_tapwin_split_forward(const float *x, const float *offset, const float *mask, const float *weight, unsigned *wpk, const float *bias, float *y,
-                             int B, int C, int H, int W, int Co, int dg, int64_t off_bs, int64_t msk_bs, int act, const float *xm_amax,
-                             hipStream_t stream) {
-  EDVR_REQUIRE(B <= 65535, "dcn_tapwin_split: batch %d exceeds grid.z", B);
-  EDVR_REQUIRE((reinterpret_cast<uintptr_t>(x) & 15) == 0 && (reinterpret_cast<uintptr_t>(wpk) & 15) == 0, "dcn_tapwin_split: x / wpk must be 16-byte aligned");
+size_t dcn_tapwin_split_wpk_elems(int Co, int C) { return 16 + (size_t)C * 9 * ((Co + 31) / 32 * 32); }
+
+// wpk: dcn_tapwin_split_wpk_elems dwords, filled here (scale pre-pass + packing: two small launches).  The weights of an inference run
+// do not change between calls: whoever keeps `wpk` packs once per parameter version and calls dcn_tapwin_split_forward_packed.
+int dcn_tapwin_split_pack(const float *weight, unsigned *wpk, int Co, int C, hipStream_t stream) {
+  EDVR_REQUIRE(weight && wpk && Co > 0 && C > 0 && (C & 3) == 0, "dcn_tapwin_split_pack: bad arguments");
+  EDVR_REQUIRE((reinterpret_cast<uintptr_t>(wpk) & 15) == 0, "dcn_tapwin_split_pack: wpk must be 16-byte aligned");
   const int cop = (Co + 31) / 32 * 32;
   hipLaunchKernelGGL(dcn_tapwin_split_scale_kernel, dim3(1), dim3(1024), 0, stream, weight, wpk, (int64_t)Co * C * 9);
   const int64_t total = (int64_t)(C / 4) * 9 * cop;
   hipLaunchKernelGGL(dcn_tapwin_split_pack_kernel, dim3((unsigned)std::min<int64_t>(cdiv64(total, 256), 2048)), dim3(256), 0, stream, weight, wpk, Co, C, cop);
+  return check_launch("dcn_tapwin_split_pack_kernel");
+}
+
+// the entry point that packs at every call (a workspace `wpk`)
+int dcn_tapwin_split_forward(const float *x, const float *offset, const float *mask, const float *weight, unsigned *wpk, const float *bias, float *y,
+                             int B, int C, int H, int W, int Co, int dg, int64_t off_bs, int64_t msk_bs, int act, const float *xm_amax,
+                             hipStream_t stream) {
+  const int rc = dcn_tapwin_split_pack(weight, wpk, Co, C, stream);
+  if (rc) return rc;
+  return dcn_tapwin_split_forward_packed(x, offset, mask, wpk, bias, y, B, C, H, W, Co, dg, off_bs, msk_bs, act, xm_amax, stream);
+}
+
+int dcn_tapwin_split_forward_packed(const float *x, const float *offset, const float *mask, const unsigned *wpk, const float *bias, float *y,
+                                    int B, int C, int H, int W, int Co, int dg, int64_t off_bs, int64_t msk_bs, int act, const float *xm_amax,
+                                    hipStream_t stream) {
+  EDVR_REQUIRE(B <= 65535, "dcn_tapwin_split: batch %d exceeds grid.z", B);
+  EDVR_REQUIRE((reinterpret_cast<uintptr_t>(x) & 15) == 0 && (reinterpret_cast<uintptr_t>(wpk) & 15) == 0, "dcn_tapwin_split: x / wpk must be 16-byte aligned");
+  const int cop = (Co + 31) / 32 * 32;
   DcnTapwinSArgs a;
   a.xm_amax = xm_amax;
   a.x = x; a.offset = offset; a.mask = mask; a.wpk = wpk; a.bias = bias; a.y = y;

@@ -212,7 +212,8 @@ def dcn_from_packed(m, x, om, act=ACT_NONE):
     # masks are sigmoid outputs and bilinear taps convex combinations of x and the zero padding: a bound of |x| bounds the columns
     # (-> the split-operand tap-window kernel) and, through the weights' norms, the output
     xb = ops.input_bound(x) if (ops.F4S_INFERENCE and hint == ops.DCN_HALO_TAPWIN and tapwin_takes(x, m)) else None
-    y = ops.dcnv2_forward(x, om[:, :split], om[:, split:], m.weight.detach(), bias, *cfg, act=act, halo_hint=hint, xm_bound=xb)
+    y = ops.dcnv2_forward(x, om[:, :split], om[:, split:], m.weight.detach(), bias, *cfg, act=act, halo_hint=hint, xm_bound=xb,
+                          w_param=m.weight)  # (the split kernel's weight layout: packed once per parameter version, not per call)
     if ops.F4S_INFERENCE:
         ops.linear_bound(y, m.weight, m.bias, (x,))
     return y
@@ -244,6 +245,27 @@ def tsa_temporal_pair(emb, emb_ref, aligned):
     if torch.is_grad_enabled():
         raise RuntimeError('tsa_temporal_pair has no backward: call it under torch.no_grad()')
     return ops.tsa_temporal_pair(emb, emb_ref, aligned)
+
+
+def tsa_front_applies(m_feat, m_attn, emb, emb_ref, aligned):
+    """Would tsa_front take the one-pass kernel for these two nn.Conv2d heads and operands?  (ops.tsa_front_applies: the C side's rule.)"""
+    grad = _needs_grad(emb, emb_ref, aligned, m_feat.weight, m_feat.bias, m_attn.weight, m_attn.bias)
+    plain = all(tuple(m.stride) == (1, 1) and tuple(m.padding) == (0, 0) and tuple(m.dilation) == (1, 1) and m.groups == 1 and m.kernel_size[0] == m.kernel_size[1]
+                for m in (m_feat, m_attn))
+    return plain and ops.tsa_front_applies(emb, emb_ref, aligned, m_feat.weight, m_attn.weight, (m_feat.bias is not None, m_attn.bias is not None), grad)
+
+
+def tsa_front(m_feat, m_attn, emb, emb_ref, aligned, act=ACT_LRELU):
+    """(act(m_feat(mod)), act(m_attn(mod))) for mod = tsa_temporal(emb, emb_ref, aligned) viewed as (b, t * c, h, w) - the head of TSA fusion.
+    Where tsa_front_applies, one kernel that never stores mod (ops.tsa_front); everywhere else - training, other shapes, EDVR_TSA_FRONT=0 -
+    the three launches.  The same bits either way."""
+    if tsa_front_applies(m_feat, m_attn, emb, emb_ref, aligned):
+        return ops.tsa_front(emb, emb_ref, aligned, ops.pack_conv_weight(m_feat.weight, f4s=True), m_feat.bias.detach(),
+                             ops.pack_conv_weight(m_attn.weight, f4s=True), m_attn.bias.detach(), m_feat.out_channels, act, act)
+    b, t, c, h, w = aligned.shape
+    mod = tsa_temporal(emb, emb_ref, aligned)
+    mod = ops.carry_bound(mod.view(b, t * c, h, w), mod)
+    return conv(m_feat, mod, act=act), conv(m_attn, mod, act=act)
 
 
 def tsa_combine(feat, attn, attn_add):

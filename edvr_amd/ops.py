@@ -154,6 +154,38 @@ def pack_conv_weight(weight, transpose_flip=False, f4=False, f4s=False, ci_range
     return out
 
 
+def pack_dcn_split_weight(weight):
+    """The (Co, C, 3, 3) weight of a DCN layer in the layout of the split-operand tap-window kernel (csrc/dcn_tapwin_s.hip: scale pre-pass +
+    packing, the two launches edvr_dcnv2_fwd_split_f32 issues at EVERY call), cached per parameter version like the conv layouts: same
+    key (id, version, pointer) under a layout slot of its own, dropped by invalidate_packed_weights, pinned by pin_packed_weights.  int32
+    buffer of edvr_dcnv2_split_packed_weight_elems(Co, C) dwords for dcnv2_forward's packed entry point."""
+    require_gpu(weight)
+    key, wid, ver = ('dcn_split',), id(weight), weight._version
+    ent = _PACKED.get(wid)
+    if ent is not None and ent[0]() is weight:
+        hit = ent[1].get(key)
+        if hit is not None and hit[0] == ver and hit[2] == weight.data_ptr():
+            return hit[1]
+    else:
+        ent = (weakref.ref(weight, lambda _r, wid=wid: _PACKED.pop(wid, None)), {})
+        _PACKED[wid] = ent
+    L = _lib.lib()
+    w = weight.detach()
+    if not w.is_contiguous():
+        w = w.contiguous()
+    co, c = w.shape[0], w.shape[1]
+    n_el = L.edvr_dcnv2_split_packed_weight_elems(co, c)
+    stale = ent[1].get(key)  # rewritten in place under the rule of the 1x1 split layout: only when the cache is the buffer's sole owner
+    if stale is not None and stale[1].numel() == n_el and stale[1].device == w.device and _sole_owner(stale):
+        out = stale[1]
+    else:
+        out = torch.empty(n_el, dtype=torch.int32, device=w.device)
+    _run('dcn_split_pack_weight', lambda: _lib.check(L.edvr_dcnv2_split_pack_weight_f32(_ptr(w), _ptr(out), co, c, _stream()),
+                                                     'edvr_dcnv2_split_pack_weight_f32'), 0, _nb(w) + 4.0 * n_el)
+    ent[1][key] = (ver, out, weight.data_ptr())
+    return out
+
+
 _PACK_CALLS = 0   # edvr_conv2d_pack_weights_multi's split_parity counter
 _PACK_TABLES = {}  # job signature -> (device table, total blocks): the table of a training iteration never changes
 
@@ -815,13 +847,15 @@ def _bstride(t):
     return t.stride(0) if t.shape[0] > 1 else 0
 
 
-def dcnv2_forward(x, offset, mask, weight, bias, stride, pad, dil, groups, dg, act=ACT_NONE, halo_hint=0, out=None, xm_bound=None):
+def dcnv2_forward(x, offset, mask, weight, bias, stride, pad, dil, groups, dg, act=ACT_NONE, halo_hint=0, out=None, xm_bound=None, w_param=None):
     """out: optional preallocated (B, Co, Ho, Wo) contiguous tensor the kernels write in place (the reference's `output` argument,
     deform_conv_cuda.cpp:530-568).
     halo_hint: which kernel class runs (performance only).  The classes compute the same operator in different summation orders:
     their results agree to fp32 rounding (<= 2e-5 of the output scale, tests/test_gpu_dcn.py), NOT bit for bit.
     xm_bound: 1-element device tensor >= max |x| * max(1, max |mask|) (for sigmoid masks: a bound of |x|, `input_bound(x)`): allows the
-    split-operand form of the tap-window kernel (csrc/dcn_tapwin_s.hip) where that kernel applies; None = the fp32 kernels."""
+    split-operand form of the tap-window kernel (csrc/dcn_tapwin_s.hip) where that kernel applies; None = the fp32 kernels.
+    w_param (no-grad callers): the Parameter `weight` is the detached form of - where the split-operand kernel runs, its weight layout is
+    then packed once per parameter version (pack_dcn_split_weight) instead of at every call; None packs per call.  Same bytes, same y."""
     dt = require_gpu(x, offset, mask, weight, bias, dtypes=tuple(DCN_DTYPES))
     L = _lib.lib()
     if not x.is_contiguous() or not weight.is_contiguous():
@@ -864,7 +898,13 @@ def dcnv2_forward(x, offset, mask, weight, bias, stride, pad, dil, groups, dg, a
         if L.edvr_dcnv2_fwd_kernel_name(_ptr(x), *dims, int(halo_hint), buf, 64) == 0:
             name = f'dcnv2_fwd[{"dcn_tapwin_split_fwd_kernel" if split else buf.value.decode()}]'
     common = (_ptr(x), _ptr(offset), _ptr(mask), _ptr(weight), _ptr(bias), _ptr(y), *dims, _bstride(offset), _bstride(mask), act, halo_hint, _ptr(ws), nbytes)
-    if split:
+    if split and w_param is not None and w_param.data_ptr() == weight.data_ptr() and w_param.is_contiguous():
+        require_gpu(xm_bound)
+        wq = pack_dcn_split_weight(w_param)  # (a launch of its own under LAUNCH_HOOK, and only when the parameter has changed)
+        launch = lambda: _lib.check(L.edvr_dcnv2_fwd_split_packed_f32(_ptr(x), _ptr(offset), _ptr(mask), _ptr(wq), _ptr(bias), _ptr(y), *dims, _bstride(offset),
+                                                                      _bstride(mask), act, halo_hint, _ptr(xm_bound), _stream()),
+                                    'edvr_dcnv2_fwd_split_packed_f32')
+    elif split:
         require_gpu(xm_bound)
         launch = lambda: _lib.check(L.edvr_dcnv2_fwd_split_f32(*common, _ptr(xm_bound), _stream()), 'edvr_dcnv2_fwd_split_f32')
     else:
@@ -928,6 +968,87 @@ def tsa_temporal(emb, emb_ref, aligned, want_prob=False):
                                        'edvr_tsa_temporal_f32'), 0, _nb(emb, emb_ref, aligned, out, prob))
     carry_bound(out, al_in)  # aligned * sigmoid(.)
     return (out, prob) if want_prob else out
+
+
+TSA_FRONT = os.environ.get('EDVR_TSA_FRONT', '1') != '0'  # TSAFusion's no-grad path: temporal attention + both 1x1 heads in one kernel
+
+
+def set_tsa_front(on=None):
+    """Switch the one-pass head of TSA fusion (tsa_front, csrc/tsa_front_s.hip) on / off at run time; with it off the three launches
+    run (tsa_temporal + two 1x1 convs: the same bits).  None leaves the setting alone.  Returns the previous value; EDVR_TSA_FRONT
+    gives the initial one."""
+    global TSA_FRONT
+    prev = TSA_FRONT
+    if on is not None:
+        TSA_FRONT = bool(on)
+    return prev
+
+
+def _emb_ref_planes(emb_ref):
+    """emb_ref (b, c, h, w) with dense images (a frame of a (b, t, c, h, w) tensor is one): no copy."""
+    return emb_ref if _plane_contig(emb_ref) else emb_ref.contiguous()
+
+
+def tsa_front_applies(emb, emb_ref, aligned, w_feat, w_attn, has_bias=(True, True), needs_grad=False, x_amax=None):
+    """THE eligibility rule of tsa_front (edvr_tsa_front_applies, C side): no gradients, both convs 1x1 with bias and one co, a shape
+    the kernel takes, and two convs that would each run on conv1x1_split_kernel - which needs a magnitude bound of `aligned` (x_amax or
+    the one travelling with the tensor) and the split kernels switched on."""
+    if not TSA_FRONT or not F4S_INFERENCE or needs_grad or aligned.dim() != 5 or w_feat.dim() != 4 or w_attn.dim() != 4:
+        return False
+    b, t, c, h, w = aligned.shape
+    if tuple(emb.shape) != (b, t, c, h, w) or tuple(emb_ref.shape) != (b, c, h, w) or w_feat.shape[1] != t * c or w_attn.shape[1] != t * c:
+        return False
+    if x_amax is None and get_bound(aligned) is None:
+        return False
+    any_ptr = ctypes.c_void_p(16)  # (any non-null, 16-byte aligned value: the packed buffers are torch allocations)
+    return bool(_lib.lib().edvr_tsa_front_applies(0, b, t, c, h, w, w_feat.shape[0], w_attn.shape[0], w_feat.shape[2], w_attn.shape[2],
+                                                  int(bool(has_bias[0])), int(bool(has_bias[1])), any_ptr, any_ptr, any_ptr))
+
+
+def tsa_front(emb, emb_ref, aligned, wq_feat, bias_feat, wq_attn, bias_attn, co, act_feat=ACT_LRELU, act_attn=ACT_LRELU, x_amax=None,
+              want_y_amax=True):
+    """(feat, attn) = the two 1x1 convs over mod = aligned * sigmoid(<emb_j, emb_ref>) viewed as (b, t * c, h, w), each with its bias and
+    activation, in ONE kernel that never stores mod (edvr_tsa_front_f32): bit for bit tsa_temporal followed by two conv2d calls on the
+    split-operand 1x1 kernel.  wq_*: pack_conv_weight(w, f4s=True) of the two (co, t * c, 1, 1) weights; x_amax: a bound of |aligned|
+    (default: the one on the tensor, else one reduction pass).  No-grad only.  Both outputs carry their measured bound."""
+    if torch.is_grad_enabled() and any(v.requires_grad for v in (emb, emb_ref, aligned)):
+        raise RuntimeError('tsa_front has no backward: call it under torch.no_grad()')
+    require_gpu(emb, emb_ref, aligned, bias_feat, bias_attn)
+    require_gpu(wq_feat, wq_attn, dtypes=(torch.int32,))
+    b, t, c, h, w = aligned.shape
+    if tuple(emb.shape) != (b, t, c, h, w) or tuple(emb_ref.shape) != (b, c, h, w):
+        raise ValueError(f'tsa_front: emb {tuple(emb.shape)} / emb_ref {tuple(emb_ref.shape)} do not match aligned {tuple(aligned.shape)}')
+    L = _lib.lib()
+    if not L.edvr_tsa_front_supported(b, t, c, h, w, co):
+        raise NotImplementedError(f'tsa_front: the kernel takes t <= 16, c % 8 == 0, co <= 128; got t {t}, c {c}, co {co}')
+    n_el = L.edvr_conv2d_packed_weight_1x1s_elems(co, t * c)
+    if wq_feat.numel() != n_el or wq_attn.numel() != n_el or bias_feat.numel() != co or bias_attn.numel() != co:
+        raise ValueError(f'tsa_front: packed weights of {n_el} dwords and biases of {co} elements expected')
+    al_in = aligned
+    emb, aligned, emb_ref = emb.contiguous(), aligned.contiguous(), _emb_ref_planes(emb_ref)
+    if x_amax is None:
+        x_amax = input_bound(al_in, aligned.view(b * t, c, h, w))
+    require_gpu(x_amax)
+    if BOUND_CHECK:  # debugging / tests, as in conv2d: the bound that reaches the kernel against the data (max |mod| <= max |aligned|; synchronises)
+        true = amax(aligned.view(b * t, c, h, w)).item()
+        if not (x_amax.item() >= true):
+            raise AssertionError(f'magnitude bound {x_amax.item():.6g} < max |aligned| = {true:.6g} for the TSA head on {tuple(aligned.shape)}')
+        BOUND_CHECK_LOG.extend([((b, t * c, h, w), x_amax.item() / max(true, 1e-30))] * 2)  # (one record per conv, as the three launches leave)
+    feat = torch.empty(b, co, h, w, dtype=torch.float32, device=aligned.device)
+    attn = torch.empty(b, co, h, w, dtype=torch.float32, device=aligned.device)
+    yb = (_arena(aligned.device).slot(aligned.device), _arena(aligned.device).slot(aligned.device)) if want_y_amax else (None, None)
+    ci = t * c
+    _run('tsa_front_split_kernel',
+         lambda: _lib.check(L.edvr_tsa_front_f32(_ptr(emb), _ptr(emb_ref), _img_stride(emb_ref), _ptr(aligned), _ptr(x_amax),
+                                                 _ptr(wq_feat), _ptr(bias_feat), int(act_feat), _ptr(feat), _ptr(yb[0]),
+                                                 _ptr(wq_attn), _ptr(bias_attn), int(act_attn), _ptr(attn), _ptr(yb[1]),
+                                                 b, t, c, h, w, co, _stream()), 'edvr_tsa_front_f32'),
+         2.0 * b * h * w * (t * c + 2 * co * ci), _nb(emb, emb_ref, aligned, feat, attn) + 8.0 * co * ci,
+         16.0 * b * (-(-h * w // 128) * 128) * (-(-ci // 32) * 32) * (128 if co > 64 else 64))
+    if want_y_amax:
+        set_bound(feat, yb[0])
+        set_bound(attn, yb[1])
+    return feat, attn
 
 
 def tsa_temporal_pair(emb, emb_ref, aligned, out=None, out_rev=None):

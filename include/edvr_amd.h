@@ -299,6 +299,16 @@ int edvr_dcnv2_fwd_split_f32(const float *x, const float *offset, const float *m
                              const float *xm_amax, edvr_stream_t stream);
 int edvr_dcnv2_fwd_split_applies(const float *x, int B, int C, int H, int W, int Co, int kh, int kw, int stride, int pad, int dil, int groups,
                                  int dg, int halo_hint);
+/* The weights of that kernel packed ONCE (they do not change between the calls of an inference run): edvr_dcnv2_split_pack_weight_f32
+ * fills a caller-owned, 16-byte aligned buffer of edvr_dcnv2_split_packed_weight_elems(Co, C) dwords (scale pre-pass + packing, the two
+ * launches edvr_dcnv2_fwd_split_f32 issues at every call) and edvr_dcnv2_fwd_split_packed_f32 runs the forward from it - valid only
+ * where edvr_dcnv2_fwd_split_applies says 1 (anything else is an error); no workspace.  Same packed bytes, same y. */
+size_t edvr_dcnv2_split_packed_weight_elems(int Co, int C);
+int edvr_dcnv2_split_pack_weight_f32(const float *weight, void *wpk, int Co, int C, edvr_stream_t stream);
+int edvr_dcnv2_fwd_split_packed_f32(const float *x, const float *offset, const float *mask, const void *wpk, const float *bias,
+                                    float *y, int B, int C, int H, int W, int Co, int kh, int kw, int stride, int pad, int dil, int groups,
+                                    int dg, int64_t offset_bstride, int64_t mask_bstride, int act, int halo_hint, const float *xm_amax,
+                                    edvr_stream_t stream);
 /* Name of the kernel edvr_dcnv2_fwd_f32 would launch for these arguments (as rocprofv3 prints it): dcn_tapwin_fwd_kernel,
  * dcn_fused_fwd_kernel or dcn_im2col_kernel (+ the conv kernel of its GEMM).  Measurement aid only. */
 int edvr_dcnv2_fwd_kernel_name(const float *x, int B, int C, int H, int W, int Co, int kh, int kw, int stride, int pad, int dil,
@@ -389,6 +399,24 @@ int edvr_tsa_temporal_f32(const float *emb, const float *emb_ref, const float *a
  * non-overlapping buffers (anything else is an error); t = 1 is legal (out_rev equals out in value). */
 int edvr_tsa_temporal_pair_f32(const float *emb, const float *emb_ref, const float *aligned, float *out, float *out_rev,
                                int b, int t, int c, int hw, edvr_stream_t stream);
+/* The head of TSA fusion in one pass over `aligned` (csrc/tsa_front_s.hip): temporal attention and the two 1x1 convs that read its
+ * product - feat = act_feat(conv1x1(mod, W_feat) + b_feat), attn likewise, mod[b, j*c + k, p] = aligned[b,j,k,p] * prob[b,j,p] as
+ * edvr_tsa_temporal_f32 defines it - without storing mod.  Bit for bit what edvr_tsa_temporal_f32 followed by two edvr_conv2d_f32 calls
+ * on conv1x1_split_kernel give.  emb / aligned (b, t, c, h, w) dense, emb_ref (b, c, h, w) with dense images emb_ref_img_stride floats
+ * apart; x_amax: device pointer to ONE float >= max |aligned| (a bound of mod as well: the sigmoid is <= 1); wq_*: the buffers of
+ * edvr_conv2d_pack_weight_1x1s_f32(w, ., co, t * c), 16-byte aligned, each head with its own scale; act_*: EDVR_ACT_*; feat / attn
+ * (b, co, h, w) dense; *_amax (may be NULL): max |y| slots with the semantics of edvr_conv2d_desc.y_amax (raw bit patterns, NaN sticky).
+ * edvr_tsa_front_supported: the kernel's own limits (t <= 16, c % 8 == 0, co <= 128, a frame pair below 2 GB).
+ * edvr_tsa_front_applies: THE eligibility rule of the fused path - no gradients, both convs 1x1 with bias and the same co, supported
+ * shape, aligned buffers, and each conv one that edvr_conv2d_f32 would run on conv1x1_split_kernel (only then are the three launches
+ * reproduced bit for bit); EDVR_TSA_FRONT=0 switches it off.  Replaces edvr_arch.py:171-193 (the ATen glue and two cuDNN calls). */
+int edvr_tsa_front_supported(int b, int t, int c, int h, int w, int co);
+int edvr_tsa_front_applies(int needs_grad, int b, int t, int c, int h, int w, int co_feat, int co_attn, int ks_feat, int ks_attn, int has_bias_feat,
+                           int has_bias_attn, const void *wq_feat, const void *wq_attn, const float *x_amax);
+int edvr_tsa_front_f32(const float *emb, const float *emb_ref, int64_t emb_ref_img_stride, const float *aligned, const float *x_amax,
+                       const void *wq_feat, const float *bias_feat, int act_feat, float *feat, float *feat_amax, const void *wq_attn,
+                       const float *bias_attn, int act_attn, float *attn, float *attn_amax, int b, int t, int c, int h, int w, int co,
+                       edvr_stream_t stream);
 /* MaxPool2d(3,2,1) and AvgPool2d(3,2,1, count_include_pad) in one pass; y (n, 2c, ho, wo) = cat(max, avg). */
 int edvr_pool_maxavg_3x3s2_f32(const float *x, float *y, int n, int c, int h, int w, edvr_stream_t stream);
 /* nn.Upsample(scale_factor=2, bilinear, align_corners=False); y = scale * up(x). */
