@@ -125,6 +125,7 @@ PROTOTYPES = {
     'edvr_dcnv2_bwd_f32': (i32, [vp] * 10 + [i32] * 12 + [i64, i64, i64, i64, i32, vp, sz, vp]),
     'edvr_dcnv2_bwd_split_f32': (i32, [vp] * 10 + [i32] * 12 + [i64, i64, i64, i64, i32, vp, sz, vp, vp, vp]),
     'edvr_dcnv2_bwd_split_applies': (i32, []),
+    'edvr_dcnv2_bwd_kernel_name': (i32, [i32] * 13 + [ctypes.c_char_p, sz]),
     'edvr_tsa_temporal_f32': (i32, [vp] * 5 + [i32] * 4 + [vp]),
     'edvr_tsa_temporal_pair_f32': (i32, [vp] * 5 + [i32] * 4 + [vp]),
     'edvr_tsa_front_supported': (i32, [i32] * 6),

@@ -161,7 +161,8 @@ int dcn_tapwin_split_forward(const float *x, const float *offset, const float *m
                              hipStream_t stream);
 
 // dcn_bwd_fused.hip: DCNv2 backward (dX, dOffset, dMask, forward columns) for the EDVR signature without the dcol buffer
-bool dcn_bwd_fused_supported(const DcnShape &s);
+bool dcn_bwd_fused_enabled();                    // false under EDVR_DCN_BWD_FUSED=0 (read once)
+bool dcn_bwd_fused_supported(const DcnShape &s);  // shapes the kernel takes
 size_t dcn_bwd_fused_wbk_elems(int dg);  // floats of the re-ordered W^T the kernel streams (workspace)
 int dcn_bwd_fused_launch(const DcnShape &s, const float *x, const float *offset, const float *mask, const float *weight, const float *dy,
                          float *wbk, float *col, float *dx, float *doffset, float *dmask, hipStream_t stream);

@@ -681,6 +681,34 @@ static BwdWs bwd_ws(const DcnShape &s) {
   return w;
 }
 
+// Which kernel produces dX (and with it dOffset / dMask) of the backward: decided here, for the launch and for
+// edvr_dcnv2_bwd_kernel_name alike.  fused_on / tile_on: the switches EDVR_DCN_BWD_FUSED / EDVR_DCN_BWD_TILE, read once.
+enum class DcnBwdRoute { FUSED, STRIP, TILE3, TILE6, DEVICE };
+static bool bwd_tile_enabled() {
+  static const bool use_tile = []() {
+    const char *e = getenv("EDVR_DCN_BWD_TILE");  // "0": never use the LDS-window kernel (A/B)
+    return !(e && e[0] == '0');
+  }();
+  return use_tile;
+}
+static DcnBwdRoute dcn_bwd_route(const DcnShape &s, int scatter_hint, bool fused_on, bool tile_on) {
+  if (scatter_hint == EDVR_DCN_SCATTER_STRIP && fused_on && dcn_bwd_fused_supported(s)) return DcnBwdRoute::FUSED;
+  const bool edvr_sig = s.kh == 3 && s.kw == 3 && s.stride == 1 && s.pad == 1 && s.dil == 1 && s.stride_w == 1 && s.pad_w == 1 && s.dil_w == 1;
+  if (scatter_hint == EDVR_DCN_SCATTER_STRIP && edvr_sig && s.dg * cdiv(s.W, 64) <= 65535) return DcnBwdRoute::STRIP;
+  if (tile_on && scatter_hint != EDVR_DCN_SCATTER_DEVICE && scatter_hint != EDVR_DCN_SCATTER_STRIP && edvr_sig && s.C / s.dg <= 16)
+    return scatter_hint == EDVR_DCN_SCATTER_LDS_WIDE ? DcnBwdRoute::TILE6 : DcnBwdRoute::TILE3;
+  return DcnBwdRoute::DEVICE;
+}
+static const char *dcn_bwd_route_name(DcnBwdRoute r) {
+  switch (r) {
+    case DcnBwdRoute::FUSED: return "dcn_bwd_fused_kernel";
+    case DcnBwdRoute::STRIP: return "dcn_bwd_dx_strip_kernel";  // followed by dcn_bwd_coord_kernel<false>
+    case DcnBwdRoute::TILE3: return "dcn_bwd_coord_tile_kernel<3>";
+    case DcnBwdRoute::TILE6: return "dcn_bwd_coord_tile_kernel<6>";
+    default: return "dcn_bwd_coord_kernel";
+  }
+}
+
 }  // namespace edvr
 
 extern "C" {
@@ -855,7 +883,8 @@ static int dcnv2_bwd_impl(const float *x, const float *offset, const float *mask
   float *wpk = reinterpret_cast<float *>(static_cast<char *>(ws) + wsz.wpk);
   float *gws = reinterpret_cast<float *>(static_cast<char *>(ws) + wsz.gemm);
   const int cig = C / groups, cog = Co / groups;
-  if (scatter_hint == EDVR_DCN_SCATTER_STRIP && dcn_bwd_fused_supported(s)) {
+  const DcnBwdRoute route = dcn_bwd_route(s, scatter_hint, dcn_bwd_fused_enabled(), bwd_tile_enabled());
+  if (route == DcnBwdRoute::FUSED) {
     // 1 + 2 in one kernel: the dcol slice of a (group, tap pair) is consumed in the registers the matrix core left it in.  Its dX
     // route is built for sub-pixel offsets, the same layers the strip hint marks (6.4 vs 8.6 ms at sigma 0.3, 13.2 vs 16.6 at 0.5)
     if (hipMemsetAsync(dx, 0, (size_t)B * C * H * W * sizeof(float), stream) != hipSuccess) {
@@ -893,25 +922,20 @@ static int dcnv2_bwd_impl(const float *x, const float *offset, const float *mask
       set_error("dcnv2_bwd: hipMemsetAsync failed");
       return EDVR_ERR_LAUNCH;
     }
-    static const bool use_tile = []() {
-      const char *e = getenv("EDVR_DCN_BWD_TILE");  // "0": never use the LDS-window kernel (A/B)
-      return !(e && e[0] == '0');
-    }();
-    const bool edvr_sig = kh == 3 && kw == 3 && s.stride == 1 && s.pad == 1 && s.dil == 1 && s.stride_w == 1 && s.pad_w == 1 && s.dil_w == 1;
-    if (scatter_hint == EDVR_DCN_SCATTER_STRIP && edvr_sig && dg * cdiv(W, 64) <= 65535) {
+    if (route == DcnBwdRoute::STRIP) {
       // dX by the register-ring kernel (reads dcol before the next kernel rewrites it), then dOffset / dMask / columns without dX
       hipLaunchKernelGGL(dcn_bwd_dx_strip_kernel, dim3(dg * cdiv(W, 64), B), dim3(256), 0, stream, offset, mask, col, dx, s);
       const int64_t total = (int64_t)B * dg * K * P;
       hipLaunchKernelGGL(dcn_bwd_coord_kernel<false>, dim3((unsigned)std::min<int64_t>(cdiv64(total, 256), 1 << 20)), dim3(256), 0, stream,
                          x, offset, mask, col, static_cast<float *>(nullptr), doffset, dmask, s);
       rc = check_launch("dcn_bwd_dx_strip_kernel + dcn_bwd_coord_kernel");
-    } else if (use_tile && scatter_hint != EDVR_DCN_SCATTER_DEVICE && scatter_hint != EDVR_DCN_SCATTER_STRIP && edvr_sig && C / dg <= 16) {
+    } else if (route == DcnBwdRoute::TILE3 || route == DcnBwdRoute::TILE6) {
       const int tiles_x = cdiv(s.Wo, 32), tiles_y = cdiv(s.Ho, 8);
       // window margin beyond the tile's 3x3 footprint (a corner outside the window is a device atomic): 3 px (42 KB of LDS, three workgroups
       // per CU) or, EDVR_DCN_SCATTER_LDS_WIDE, 6 px (66 KB, two per CU) for fields whose taps sit ~4 px out and more (15.0 -> 11.0 ms per
       // call at sigma 6 px per tap, 9.7 vs 9.8 at sigma 4, 7.9 vs 9.9 at sigma 2; 8 px = one workgroup per CU: 15-17 ms everywhere:
       // profiles/r6/dcn_bwd_margin.log)
-      if (scatter_hint == EDVR_DCN_SCATTER_LDS_WIDE)
+      if (route == DcnBwdRoute::TILE6)
         hipLaunchKernelGGL((dcn_bwd_coord_tile_kernel<6>), dim3(tiles_x * tiles_y, dg, B), dim3(256), 0, stream, x, offset, mask, col, dx, doffset, dmask, s, tiles_x);
       else
         hipLaunchKernelGGL((dcn_bwd_coord_tile_kernel<3>), dim3(tiles_x * tiles_y, dg, B), dim3(256), 0, stream, x, offset, mask, col, dx, doffset, dmask, s, tiles_x);
@@ -957,6 +981,18 @@ int edvr_dcnv2_bwd_split_f32(const float *x, const float *offset, const float *m
   EDVR_REQUIRE(xm_amax && dy_amax, "dcnv2_bwd_split: null magnitude bound");
   return dcnv2_bwd_impl(x, offset, mask, weight, dy, dx, doffset, dmask, dweight, dbias, B, C, H, W, Co, kh, kw, stride, pad, dil, groups, dg,
                         offset_bstride, mask_bstride, doffset_bstride, dmask_bstride, scatter_hint, ws, ws_bytes, xm_amax, dy_amax, stream);
+}
+
+/* host only: the route dcnv2_bwd_impl takes for these arguments */
+int edvr_dcnv2_bwd_kernel_name(int B, int C, int H, int W, int Co, int kh, int kw, int stride, int pad, int dil, int groups, int dg,
+                               int scatter_hint, char *buf, size_t buf_len) {
+  using namespace edvr;
+  EDVR_REQUIRE(buf && buf_len > 0, "dcnv2_bwd_kernel_name: null buffer");
+  DcnShape s;
+  const int rc = dcn_fill_shape(s, B, C, H, W, Co, kh, kw, stride, pad, dil, groups, dg, 0, 0);
+  if (rc) return rc;
+  snprintf(buf, buf_len, "%s", dcn_bwd_route_name(dcn_bwd_route(s, scatter_hint, dcn_bwd_fused_enabled(), bwd_tile_enabled())));
+  return EDVR_OK;
 }
 
 int edvr_dcnv2_bwd_split_applies(void) { return edvr::gemm_nt_split_enabled() ? 1 : 0; }

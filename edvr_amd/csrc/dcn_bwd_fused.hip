@@ -413,12 +413,15 @@ __global__ __launch_bounds__(BF_NT) void dcn_bwd_fused_kernel(const DcnBwdFusedA
   }
 }
 
-bool dcn_bwd_fused_supported(const DcnShape &s) {
+bool dcn_bwd_fused_enabled() {
   static const bool enabled = []() {
     const char *e = getenv("EDVR_DCN_BWD_FUSED");  // "0": the staged path (dcol GEMM + strip / window kernels), for A/B
     return !(e && e[0] == '0');
   }();
-  if (!enabled) return false;
+  return enabled;
+}
+
+bool dcn_bwd_fused_supported(const DcnShape &s) {  // the shape alone; the switch above is the caller's (dcn_bwd_route, dcn.hip)
   if (!(s.kh == 3 && s.kw == 3 && s.stride == 1 && s.pad == 1 && s.dil == 1 && s.stride_w == 1 && s.pad_w == 1 && s.dil_w == 1)) return false;
   if (s.groups != 1 || s.C != s.dg * BF_CPG || s.Co > 2 * BF_NS || s.B > 65535) return false;
   if (s.W < BF_TW) return false;  // half-empty waves: the staged path is faster (0.74 vs 0.98 ms on the 160 x 128 x 16 x 16 layer)

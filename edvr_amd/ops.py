@@ -954,6 +954,16 @@ def dcnv2_backward(x, offset, mask, weight, dy, with_bias, stride, pad, dil, gro
     return dx, doff, dmsk, dw, db
 
 
+def dcnv2_backward_kernel_name(x, weight, stride, pad, dil, groups, dg, scatter_hint=0):
+    """The kernel dcnv2_backward's dX comes from for these shapes and this hint (float32 path): the launch's own decision, asked on
+    the host - only the shapes of `x` and `weight` are read, no GPU is needed.  dcn_bwd_fused_kernel | dcn_bwd_dx_strip_kernel |
+    dcn_bwd_coord_tile_kernel<3> | dcn_bwd_coord_tile_kernel<6> | dcn_bwd_coord_kernel."""
+    buf = ctypes.create_string_buffer(64)
+    _lib.check(_lib.lib().edvr_dcnv2_bwd_kernel_name(*_dcn_dims(x, weight, stride, pad, dil, groups, dg), int(scatter_hint), buf, 64),
+               'edvr_dcnv2_bwd_kernel_name')
+    return buf.value.decode()
+
+
 # ------------------------------------------------------------------------------------------------ glue kernels
 def tsa_temporal(emb, emb_ref, aligned, want_prob=False):
     """emb/aligned (b, t, c, h, w), emb_ref (b, c, h, w) -> aligned * sigmoid(<emb_t, emb_ref>) and optionally prob."""

@@ -334,6 +334,11 @@ int edvr_dcnv2_bwd_split_f32(const float *x, const float *offset, const float *m
                              int scatter_hint, void *ws, size_t ws_bytes, const float *xm_amax, const float *dy_amax,
                              edvr_stream_t stream);
 int edvr_dcnv2_bwd_split_applies(void);
+/* Name of the kernel that produces dx for these arguments (host only; the launch decides by the same function):
+ * dcn_bwd_fused_kernel, dcn_bwd_dx_strip_kernel (followed by dcn_bwd_coord_kernel<false> for doffset / dmask),
+ * dcn_bwd_coord_tile_kernel<3>, dcn_bwd_coord_tile_kernel<6> or dcn_bwd_coord_kernel (device atomics). */
+int edvr_dcnv2_bwd_kernel_name(int B, int C, int H, int W, int Co, int kh, int kw, int stride, int pad, int dil, int groups, int dg,
+                               int scatter_hint, char *buf, size_t buf_len);
 /* scatter_hint (performance only, like halo_hint of the forward; results are the same up to the summation order of dx):
  * how the four corner contributions per (pixel, tap, channel) are accumulated into dx.
  *   EDVR_DCN_SCATTER_DEVICE (1): fp32 device atomics straight to dx, as the reference's col2im (.cu:688).  Fastest when the
