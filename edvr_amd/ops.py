@@ -2255,6 +2255,75 @@ def rgb_to_yuv(rgb, fmt='420', matrix='bt601', range='limited', out=None, siting
     return _yuv_encode('rgb_to_yuv', rgb, yuv_format(fmt), matrix, range, out, False, siting)
 
 
+# ------------------------------------------------------------------------------------------------ deinterlacing (csrc/deint.hip)
+DEINT_FIRST = {'top': 0, 'bottom': 1}   # which field of a frame is the earlier one: its even rows ('top', Y4M It) or its odd rows (Ib)
+DEINT_MODES = {'field': 1, 'frame': 0}  # a frame per field (2 n out of n) or per frame (from its first field)
+DEINT_ROWS_READ = 12 / 2 + 1 / 2        # row segments read per output row on average: 12 for a predicted row, 1 for a copied one
+
+
+def _deint_context(t, fs, depth, what):
+    """`prev` / `next` of deinterlace: one frame, uint8 (>= framesize,) or with a leading 1, dense."""
+    if t is None:
+        return None
+    require_gpu(t, dtypes=(torch.uint8,))
+    if t.dim() == 2 and t.shape[0] == 1:
+        t = t[0]
+    if t.dim() != 1 or t.shape[0] < fs:
+        raise ValueError(f'{what} is one frame, uint8 ({fs},) or (1, {fs}), got {tuple(t.shape)}')
+    if t.stride(0) != 1:
+        t = t.contiguous()
+    if depth > 8 and t.data_ptr() % 2:
+        raise ValueError(f'{what}: 16-bit samples need an even base address, got {t.data_ptr():#x}')
+    return t
+
+
+def deinterlace(yuv, H, W, format='420', *, first='top', mode='field', prev=None, next=None, out=None):
+    """Interlaced planar Y'CbCr frames -> progressive ones, on the samples as decoded, in ONE launch (integers
+    only).  yuv: uint8 (n, >= yuv_frame_size(H, W, format)) on the GPU, as yuv_to_rgb takes it - stride(1) == 1, any row stride and base
+    offset (`buf[:, 6:]` of a Y4MReader buffer), even ones above 8 bits.  Each frame weaves two fields, on its even and odd rows in every
+    plane alike; first: 'top' - the even rows are the earlier field (Y4M `It`) - or 'bottom' (`Ib`).  mode 'field': every field becomes
+    a frame - uint8 (2 n, framesize), frame 2 i + s from the s-th field in time of input frame i: a 25i clip is 50 pictures per second;
+    'frame': the first field of every frame does, (n, framesize).  A field's own rows are copied; each missing sample is predicted along
+    the least-different of five edge directions between the rows above and below it and clamped to a band around the mean of the
+    fields before and after, as wide as the fields around it differ.  prev / next: the frame before / after the batch, uint8
+    (framesize,) or with a leading 1: with them a batch inside a longer video gets exactly what the whole video would give
+    (y4m.deinterlaced does that); on a side without one the field index reflects about the batch's end.  out: a uint8 (2 n | n, >=
+    framesize) batch to write into instead, stride(1) == 1, any row stride and base offset (`buf[:, 6:]`); it must not overlap an input.
+    H >= 4 (every plane needs two rows), any W.  Bytes booked: every output sample is written once and 12 / 2 + 1 / 2 row segments are
+    read per output row on average (12 for a predicted row, 1 for a copied one): n_out framesize (1 + 6.5), most of it from the cache.
+    NotImplementedError for CPU tensors, ValueError for bad names, shapes and layouts."""
+    fmt = yuv_format(format)
+    if first not in DEINT_FIRST:
+        raise ValueError(f'first must be one of {sorted(DEINT_FIRST)}, got {first!r}')
+    if mode not in DEINT_MODES:
+        raise ValueError(f'mode must be one of {sorted(DEINT_MODES)}, got {mode!r}')
+    require_gpu(yuv, dtypes=(torch.uint8,))
+    H, W = int(H), int(W)
+    if H < 4:
+        raise ValueError(f'deinterlace: a frame needs at least 4 rows, so that every plane has 2, got {H} x {W}')
+    sx, sy, depth, _ = fmt
+    n, fs, stride = _yuv_batch(yuv, H, W, fmt, 'yuv')
+    prev, next = _deint_context(prev, fs, depth, 'prev'), _deint_context(next, fs, depth, 'next')
+    n_out = 2 * n if DEINT_MODES[mode] else n
+    if out is None:
+        out = torch.empty((n_out, fs), dtype=torch.uint8, device=yuv.device)
+    else:
+        require_gpu(out, dtypes=(torch.uint8,))
+        if out.dim() == 2 and out.shape[0] != n_out:
+            raise ValueError(f'out holds {out.shape[0]} frames, mode {mode!r} makes {n_out} of {n}')
+    _, _, out_stride = _yuv_batch(out, H, W, fmt, 'out')
+    b0, b1 = _byte_span(out)
+    for t in (yuv, prev, next):
+        if t is not None:
+            a0, a1 = _byte_span(t)
+            if a0 < b1 and b0 < a1:
+                raise ValueError('out overlaps an input')
+    _run('deinterlace', lambda: _lib.check(_lib.lib().edvr_deinterlace(_ptr(yuv), _ptr(prev), _ptr(next), _ptr(out), n, H, W, sx, sy, depth, stride,
+                                                                       out_stride, DEINT_FIRST[first], DEINT_MODES[mode], _stream()),
+                                           'edvr_deinterlace'), 0, float(n_out) * fs * (1.0 + DEINT_ROWS_READ))
+    return out
+
+
 # ------------------------------------------------------------------------------------------------ scene cuts
 def frame_sad(frames, prev=None, out=None):
     """How much consecutive frames differ, for scene-cut detection (edvr_amd/shots.py), in ONE kernel launch.

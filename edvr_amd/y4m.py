@@ -10,7 +10,8 @@ frame a line `FRAME[ parameters]` and the raw planes: for 8-bit 4:2:0 the H W lu
 planes - exactly the batch row ops.yuv420_to_rgb reads; for the other formats the chroma planes are full-size along an
 axis that is not subsampled and a sample above 8 bits is a little-endian 16-bit word - the batch row ops.yuv_to_rgb reads.  Everything
 here works on non-seekable streams (pipes), holds a bounded number of frames and uses no threads: pinned host buffers and non_blocking
-copies keep the device busy while the host reads and writes.
+copies keep the device busy while the host reads and writes.  Interlaced streams (It, Ib) are read on request and deinterlaced on the
+device, at field rate, before the colour conversion: `deinterlaced` / `restore_y4m(deinterlace=...)` around ops.deinterlace.
 """
 import torch
 
@@ -59,9 +60,11 @@ class Y4MReader:
     siting: what the tag says about where the chroma samples lie (ops.YUV_SITINGS) - 'center' for C420jpeg, 'left' for
     C420mpeg2, 'topleft' for C420paldv, None where the tag says nothing: C420, no tag, every C422 / C444 and every p9 ... p16 tag.
     (C420paldv is read as top-left co-sited chroma, which is how muxers use the tag for that chroma location; true PAL-DV siting, with Cb
-    and Cr on alternate lines, is not implemented.)"""
+    and Cr on alternate lines, is not implemented.)
+    interlaced: True also accepts It and Ib - frames that weave two fields, for `deinterlaced` / restore_y4m(deinterlace=...) (DESIGN
+    4.19); Im (mixed, flagged per frame) stays a ValueError.  interlace: the I tag's value - None, 'p', '?' and, with `interlaced`, 't' | 'b'."""
 
-    def __init__(self, stream, formats=None):
+    def __init__(self, stream, formats=None, interlaced=False):
         self.stream = stream
         line = stream.readline(1024)
         if not line.startswith(MAGIC + b' ') or not line.endswith(b'\n'):
@@ -89,8 +92,11 @@ class Y4MReader:
                 self.range = rng.lower()
         if self.width is None or self.height is None:
             raise ValueError('the YUV4MPEG2 header gives no W / H')
-        if interlace not in (None, 'p', '?'):
+        if interlace not in ((None, 'p', '?', 't', 'b') if interlaced else (None, 'p', '?')):
+            if interlaced:
+                raise ValueError(f'I{interlace} is not supported: progressive (Ip, I?), top-field-first (It) and bottom-field-first (Ib) video are')
             raise ValueError(f'interlaced video (I{interlace}) is not supported: deinterlace first')
+        self.interlace = interlace
         if formats is None:
             if self.chroma is not None and self.chroma not in CHROMA_420:
                 raise ValueError(f'C{self.chroma} is not supported: 8-bit 4:2:0 only ({", ".join("C" + c for c in CHROMA_420)})')
@@ -199,8 +205,51 @@ def resolve_siting(siting, reader):
     return siting
 
 
+FIELD_ORDERS = {'tff': 'top', 'bff': 'bottom'}  # restore_y4m's field_order -> ops.deinterlace's `first`
+
+
+def deinterlaced(pieces, H, W, format='420', first='top', mode='field'):
+    """A generator over deinterlaced device byte batches: `pieces` is an iterable of uint8 (k, >= framesize) batches of consecutive
+    interlaced frames, k >= 1 and any mix of sizes (`buf[:, 6:]` of the reader's buffers); every piece goes through ops.deinterlace
+    (first, mode: as there) with the last frame of the piece before as `prev` and the first frame of the piece after as `next`, so the
+    concatenated result is what ONE call on the whole clip gives, whatever the pieces.  A piece is held until the next one has
+    arrived: a delay of one piece and that much memory; the last piece goes out with next=None."""
+    held = before = None
+    for piece in pieces:
+        if held is not None:
+            yield ops.deinterlace(held, H, W, format, first=first, mode=mode, prev=before, next=piece[0])
+            before = held[-1]
+        held = piece
+    if held is not None:
+        yield ops.deinterlace(held, H, W, format, first=first, mode=mode, prev=before, next=None)
+
+
+def double_rate(fps):
+    """The F tag of a field-rate stream: '30000:1001' -> '60000:1001'; None (no tag) stays None."""
+    if fps is None:
+        return None
+    num, sep, den = fps.partition(':')
+    if not (sep and num.isdigit() and den.isdigit()):
+        raise ValueError(f'the frame rate F{fps} is not <num>:<den>: it cannot be doubled')
+    return f'{2 * int(num)}:{den}'
+
+
+def resolve_field_order(deinterlace, field_order, reader):
+    """restore_y4m's (deinterlace, field_order) -> (`first` of ops.deinterlace or None: nothing to do, mode).  'auto' follows the
+    reader's I tag - It: 'top', Ib: 'bottom', anything else: progressive, passed through; 'tff' / 'bff' deinterlace whatever the tag says."""
+    if deinterlace not in (None, 'field', 'frame'):
+        raise ValueError(f"deinterlace must be None, 'field' or 'frame', got {deinterlace!r}")
+    if field_order != 'auto' and field_order not in FIELD_ORDERS:
+        raise ValueError(f"field_order must be 'auto' or one of {sorted(FIELD_ORDERS)}, got {field_order!r}")
+    if deinterlace is None:
+        return None, None
+    if field_order == 'auto':
+        return {'t': 'top', 'b': 'bottom'}.get(getattr(reader, 'interlace', None)), deinterlace
+    return FIELD_ORDERS[field_order], deinterlace
+
+
 def restore_y4m(net, src, dst, *, matrix_in=None, matrix_out=None, chroma='bilinear', read_frames=8, on_chunk=None, stats=None, out_format=None,
-                siting_in='center', siting_out=None, **restorer_kwargs):
+                siting_in='center', siting_out=None, deinterlace=None, field_order='auto', **restorer_kwargs):
     """Restore a Y4M stream with `net` (an EDVR in eval mode, on the GPU) into a Y4M stream; returns the number of frames.  Call it under
     torch.no_grad().
 
@@ -229,9 +278,20 @@ def restore_y4m(net, src, dst, *, matrix_in=None, matrix_out=None, chroma='bilin
     reader's tag (`Y4MReader.siting`) and 'left' where the tag is silent, which is right for nearly all H.264 / HEVC / AV1 footage -
     decoding left-sited chroma as centred shifts the colour by half an input pixel, two output pixels.  siting_out: the siting the output
     is encoded for and, for 8-bit 4:2:0, tagged with (Y4MWriter); None - the resolved input siting.  The transfer function is never
-    touched.  With both sitings 'center' the calls are the ones made before the argument existed."""
+    touched.  With both sitings 'center' the calls are the ones made before the argument existed.
+    Interlaced video: deinterlace - None (an interlaced stream raises, as it always did), 'field' (every field becomes a
+    frame: 2 n frames out, F doubled - a 25i tape is restored as the 50 pictures per second it holds) or 'frame' (the first field of
+    every frame); a raw stream is then opened with interlaced=True.  field_order: 'auto' - the stream's tag (It / Ib); an Ip or
+    untagged stream passes through untouched, no launch - or 'tff' / 'bff', which deinterlace whatever the tag says (mis-tagged
+    captures).  The stage (`deinterlaced`: ops.deinterlace piece by piece with its neighbours' frames as context) sits between the copy
+    to the device and the colour conversion; everything after it sees a progressive video of its output frames - `cuts` indices count
+    those - and the output is written Ip."""
     from .video import VideoRestorer
-    reader = src if isinstance(src, Y4MReader) else Y4MReader(src, formats=ALL_FORMATS)
+    if deinterlace is None:
+        reader = src if isinstance(src, Y4MReader) else Y4MReader(src, formats=ALL_FORMATS)
+    else:
+        reader = src if isinstance(src, Y4MReader) else Y4MReader(src, formats=ALL_FORMATS, interlaced=True)
+    first, mode = resolve_field_order(deinterlace, field_order, reader)
     fmt_in = reader.format
     fmt_out = fmt_in if out_format is None else ops.yuv_format(out_format)[3]
     plain420 = fmt_in == '420' and fmt_out == '420'  # the 8-bit 4:2:0 operators (uint8 samples, 4:2:0 instances of csrc/yuv.hip) on both sides
@@ -253,16 +313,20 @@ def restore_y4m(net, src, dst, *, matrix_in=None, matrix_out=None, chroma='bilin
     Ho, Wo = vr.scale * H, vr.scale * W
     matrix_in = matrix_in or default_matrix(H, W)
     matrix_out = matrix_out or default_matrix(Ho, Wo)
-    writer = Y4MWriter(dst, Wo, Ho, reader.fps, reader.aspect, reader.range, fmt_out, siting_out)
+    fps = double_rate(reader.fps) if first is not None and mode == 'field' else reader.fps
+    writer = Y4MWriter(dst, Wo, Ho, fps, reader.aspect, reader.range, fmt_out, siting_out)
     row = len(FRAME) + writer.framesize
     marks = torch.tensor(list(FRAME), dtype=torch.uint8).to(device)
 
-    def decoded():
+    def batches():
         while True:
             host = reader.read(read_frames)
             if host.shape[0] == 0:
                 return
-            yuv = host.to(device, non_blocking=True)[:, len(FRAME):]
+            yield host.to(device, non_blocking=True)[:, len(FRAME):]
+
+    def decoded():
+        for yuv in (batches() if first is None else deinterlaced(batches(), H, W, fmt_in, first, mode)):
             if plain420:
                 yield ops.yuv420_to_rgb(yuv, H, W, matrix_in, reader.range, chroma, **kw_in)
             else:

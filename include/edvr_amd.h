@@ -775,6 +775,25 @@ int edvr_yuv420_to_rgb_sited_u8(const uint8_t *yuv, uint8_t *rgb, int n, int H, 
 int edvr_rgb_to_yuv420_sited_u8(const uint8_t *rgb, uint8_t *yuv, int n, int H, int W, int64_t yuv_stride, const float *coef, int siting_x,
                                 int siting_y, edvr_stream_t stream);
 
+/* Deinterlacing of interlaced planar Y'CbCr frames (csrc/deint.hip; definition: DESIGN 4.19, D1 - D6).  Replaces nothing in the
+ * reference, which restores progressive frames only: it is the `ffmpeg -vf yadif` pass otherwise run in front of the pipe, done on the
+ * device, on the samples as decoded, at field rate.  No bit-compatibility with any other deinterlacer is claimed.
+ * yuv: n frames of the format (sub_x, sub_y, depth) described above, in_stride BYTES apart at any base address (both even for 16-bit
+ * samples); each holds two fields, on its even and odd rows - in every plane alike - of which the top one (even rows) is the earlier in
+ * time unless bottom_first.  Field k = 0 ... 2 n - 1 lives in frame k / 2.  out: field_rate != 0: 2 n frames, frame k built from field k
+ * (its rows copied, the others predicted along the least-different of five edge directions between the rows above and below and clamped
+ * to a band around the mean of the fields before and after, integers throughout); field_rate == 0: n frames, from the even k.  Output
+ * frames lie out_stride bytes apart, any base address (even for 16-bit samples); bytes between them are not written.
+ * prev / next: ONE dense frame each, the one before / after the batch, or NULL: fields -2, -1 and 2 n, 2 n + 1 are read from them, so a
+ * batch cut from a longer video gets what the whole video would give; on a side without one the field index reflects about the batch's
+ * end.  Rows reflect about the plane's first and last row, columns clamp.  Odd H and W are legal.  out must not overlap the inputs.
+ * One launch, (lanes of 8 samples, output frames); whole-segment accesses of any alignment inside a row, sample by sample at its ends.
+ * EDVR_ERR_ARG: null yuv / out, n < 1 or > 32767, W < 1, H < 4 (every plane needs two rows), depth outside 8 ... 16, a subsampling other
+ * than the three, a stride shorter than a frame where more than one is read / written, an odd pointer or stride with 16-bit samples,
+ * H W > 2^29, bottom_first / field_rate other than 0 / 1.  No allocation, no wait. */
+int edvr_deinterlace(const uint8_t *yuv, const uint8_t *prev, const uint8_t *next, uint8_t *out, int n, int H, int W, int sub_x, int sub_y,
+                     int depth, int64_t in_stride, int64_t out_stride, int bottom_first, int field_rate, edvr_stream_t stream);
+
 /* Frame-to-frame change for scene-cut detection (csrc/shots.hip; definition: DESIGN 4.13).  The bytes R, G, B of a pixel are the input's
  * own (_u8: x (n, H, W, 3)) or its tensor2img bytes (_f32: x (n, 3, H, W); clamp to [0, 1], x 255, round half to even, NaN -> 0); in
  * integers Y8 = ((66 R + 129 G + 25 B + 128) >> 8) + 16, and

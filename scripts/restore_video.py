@@ -4,6 +4,12 @@
     python scripts/restore_video.py in.y4m out.y4m --weights ... --pad-mode reflect --tile 256 256 --self-ensemble flip4
     ffmpeg -i hevc10.mp4 -strict -1 -f yuv4mpegpipe - | python scripts/restore_video.py - - --weights ... | ffmpeg -i - out.mkv
     ffmpeg -i in.mp4 -f yuv4mpegpipe - | python scripts/restore_video.py - - --weights ... --out-format 420p10 | ffmpeg -i - out.mkv
+    ffmpeg -i tape.avi -f yuv4mpegpipe - | python scripts/restore_video.py - - --weights ... --deinterlace | ffmpeg -i - out.mp4
+
+Interlaced input (It / Ib: tape, DVD, 1080i) needs `--deinterlace`: the fields are deinterlaced on the device (edvr_amd.ops.deinterlace,
+DESIGN 4.19) before anything else sees them and every field becomes a frame - the output is progressive at twice the frame rate;
+`--deinterlace frame` keeps the rate (one frame per input frame, from its first field).  `--field-order tff|bff` overrides a wrong
+tag; the default `auto` follows the header and passes a progressive stream through untouched.
 
 The input is 4:2:0, 4:2:2 or 4:4:4 at 8 ... 16 bits (C420jpeg, C422p10, C444p12 ...: 10-bit phone and camera footage, 4:2:2 intermediates
 and 4:4:4 screen captures go in as they are - ffmpeg's yuv4mpegpipe muxer writes anything but 8-bit 4:2:0 only with `-strict -1`, and
@@ -46,7 +52,7 @@ def restore(args, log=log):
     from edvr_amd import EDVR
     from edvr_amd.optim import load_network
     from edvr_amd import metrics, ops
-    from edvr_amd.y4m import ALL_FORMATS, FRAME, Y4MReader, default_matrix, resolve_siting, restore_y4m
+    from edvr_amd.y4m import ALL_FORMATS, FRAME, Y4MReader, default_matrix, resolve_field_order, resolve_siting, restore_y4m
     device = torch.device('cuda', int(os.environ.get('LOCAL_RANK', 0)))
     torch.cuda.set_device(device)
     net = EDVR(num_in_ch=3, num_out_ch=3, num_feat=args.num_feat, num_frame=args.num_frame, deformable_groups=8,
@@ -63,8 +69,14 @@ def restore(args, log=log):
     src = sys.stdin.buffer if args.input == '-' else open(args.input, 'rb')
     dst = sys.stdout.buffer if args.output == '-' else open(args.output, 'wb')
     try:
-        reader = Y4MReader(src, formats=ALL_FORMATS)
+        deint = getattr(args, 'deinterlace', None)
+        reader = Y4MReader(src, formats=ALL_FORMATS, interlaced=True) if deint else Y4MReader(src, formats=ALL_FORMATS)
         log(f'{args.input}: {reader.width} x {reader.height}, F{reader.fps}, C{reader.chroma}, {reader.range} range')
+        if deint:
+            first, _ = resolve_field_order(deint, args.field_order, reader)
+            kwargs.update(deinterlace=deint, field_order=args.field_order)
+            log(f'{args.input}: I{reader.interlace}, ' + (f'deinterlaced at {deint} rate, {first} field first' if first else 'progressive: nothing to deinterlace'))
+            deint = first is not None
         siting_in = resolve_siting(getattr(args, 'siting', 'center'), reader)
         siting_out = getattr(args, 'siting_out', None)
         if (siting_in, siting_out) != ('center', None):
@@ -75,7 +87,8 @@ def restore(args, log=log):
             params = metrics.load_niqe_params(niqe_path)
             kwargs['on_chunk'] = lambda chunk: niqe_out.extend(metrics.calculate_niqe(chunk, params=params))
             H, W = reader.height, reader.width
-            if (H // metrics.NIQE_BLOCK) * (W // metrics.NIQE_BLOCK) >= 2:  # one block leaves no covariance to estimate
+            # (one block leaves no covariance to estimate; woven frames are not what the network sees: a deinterlaced input is not scored)
+            if (H // metrics.NIQE_BLOCK) * (W // metrics.NIQE_BLOCK) >= 2 and not deint:
                 read, matrix_in = reader.read, args.matrix_in or default_matrix(H, W)
 
                 def scored_read(k):  # the input as restore_y4m decodes it, scored at its own size
@@ -183,6 +196,11 @@ def parse_args(argv=None):
                     help="the siting the output is encoded for (default: the input's)")
     ap.add_argument('--out-format', default=None, metavar='NAME',
                     help="the output's format: 420 | 422 | 444 with an optional depth p9 ... p16, e.g. 420p10 (default: the input's)")
+    ap.add_argument('--deinterlace', nargs='?', const='field', default=None, choices=['field', 'frame'],
+                    help='deinterlace an interlaced stream (It / Ib) on the device first: field - every field becomes a frame, the rate doubles '
+                         '(the default of a bare --deinterlace); frame - one frame per input frame, from its first field')
+    ap.add_argument('--field-order', default='auto', choices=['auto', 'tff', 'bff'],
+                    help="with --deinterlace: auto - the stream's tag, a progressive stream passes through; tff / bff - deinterlace whatever the tag says")
     ap.add_argument('--niqe', default=None, metavar='PARAMS.npz',
                     help="score the output (and the input, where two 96 x 96 blocks fit) with NIQE; PARAMS.npz is BasicSR's niqe_pris_params.npz")
     ap.add_argument('--niqe-json', default=None, metavar='FILE', help='with --niqe: write the per-frame and mean NIQE there')
@@ -211,6 +229,8 @@ def parse_args(argv=None):
         ap.error('--cuts-json needs --scene-cuts or --cuts')
     if args.cuts is not None and (args.cuts[0] < 1 or any(b <= a for a, b in zip(args.cuts, args.cuts[1:]))):
         ap.error('--cuts are strictly increasing frame indices, at least 1')
+    if args.field_order != 'auto' and args.deinterlace is None:
+        ap.error('--field-order needs --deinterlace')
     if args.niqe_json is not None and args.niqe is None:
         ap.error('--niqe-json needs --niqe')
     if args.tile_blend is not None and args.tile is None:
