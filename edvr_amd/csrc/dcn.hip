@@ -257,7 +257,7 @@ __global__ __launch_bounds__(256, 4) void dcn_bwd_dx_strip_kernel(const float *_
         const bool valid = (ph > -1.f) && (pw > -1.f) && (ph < (float)H) && (pw < (float)W);
         const float fh = floorf(ph), fw = floorf(pw);
         const int h0 = (int)fh, w0 = (int)fw;
-        const float lh = ph - fh, lw = pw - fw;
+        const float lh = valid ? ph - fh : 0.f, lw = valid ? pw - fw : 0.f;  // (inf - inf and NaN stay out of the column weights: 0 x NaN is not 0)
         const int fy = h0 - (y - 1 + i), fx = w0 - (x - 1 + j);  // -1 or 0 for a sub-pixel offset
         const bool near = (fy == -1 || fy == 0) && (fx == -1 || fx == 0);
         const float wt = (valid && near && h0 >= 0) ? m * (1.f - lh) : 0.f, wb = (valid && near && h0 + 1 <= H - 1) ? m * lh : 0.f;

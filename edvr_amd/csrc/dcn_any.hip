@@ -64,7 +64,10 @@ __device__ __forceinline__ TapT<CT> resolve_tap_t(CT h, CT w, int H, int W) {
   TapT<CT> t;
   const bool valid = (h > (CT)-1) && (w > (CT)-1) && (h < (CT)H) && (w < (CT)W);
   const CT fh = floor(h), fw = floor(w);
-  const int h0 = (int)fh, w0 = (int)fw, h1 = h0 + 1, w1 = w0 + 1;
+  // (cell origins kept inside [-2, H] x [-2, W] before the conversion, as cell_origin of dcn_tap.h does and for its reason: an invalid
+  //  tap's floor may lie beyond the range of int, be +-inf or NaN; a valid tap's is untouched)
+  const CT gh = fh > (CT)-2 ? (fh < (CT)H ? fh : (CT)H) : (CT)-2, gw = fw > (CT)-2 ? (fw < (CT)W ? fw : (CT)W) : (CT)-2;
+  const int h0 = (int)gh, w0 = (int)gw, h1 = h0 + 1, w1 = w0 + 1;
   t.lh = h - fh;
   t.lw = w - fw;
   const CT hh = (CT)1 - t.lh, hw = (CT)1 - t.lw;

@@ -380,8 +380,10 @@ __global__ __launch_bounds__(BF_NT) void dcn_bwd_fused_kernel(const DcnBwdFusedA
       }
     }
     bstore(s_m, dmsk_rsrc, v1, g * 9 * P * 4);
-    bstore(s_y * o_m, doff_rsrc, v2, g * 18 * P * 4);
-    bstore(s_x * o_m, doff_rsrc, v2, (g * 18 + 1) * P * 4);
+    // an invalid tap has d = 0 in every term above, but where its h or w is +-inf or NaN its lh / lw are NaN, and 0 x NaN is not 0: its
+    // sums are dropped here, once per (pixel, tap).  (Gating lh / lw where they are made costs this kernel 35 more spilled registers.)
+    bstore(valid ? s_y * o_m : 0.f, doff_rsrc, v2, g * 18 * P * 4);
+    bstore(valid ? s_x * o_m : 0.f, doff_rsrc, v2, (g * 18 + 1) * P * 4);
   };
 
   for (int g = 0; g < a.dg; ++g) {

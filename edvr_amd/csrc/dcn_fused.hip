@@ -173,7 +173,7 @@ __global__ __launch_bounds__(256, 2) void dcn_fused_fwd_kernel(const DcnFusedArg
       const float h = (float)(oy - 1 + t / 3) + dy, w = (float)(ox - 1 + t % 3) + dx;
       const bool valid = pix_ok && h > -1.f && w > -1.f && h < (float)a.H && w < (float)a.W;  // .cu:618
       const float fh = floorf(h), fw = floorf(w);
-      const float lh = h - fh, lw = w - fw;
+      const float lh = valid ? h - fh : 0.f, lw = valid ? w - fw : 0.f;  // (inf - inf and NaN stay out of the weights: 0 x NaN is not 0)
       const float mm = valid ? m : 0.f;
       w00[t] = (1.f - lh) * (1.f - lw) * mm;
       w01[t] = (1.f - lh) * lw * mm;

@@ -9,14 +9,20 @@ struct Tap {
   int o00, o01, o10, o11;    // clamped element offsets inside one channel plane
   float lh, lw;
   bool ok00, ok01, ok10, ok11;  // corner inside the image AND tap valid
-  int h0, w0;                   // unclamped integer coordinates of corner 00
+  int h0, w0;                   // integer coordinates of corner 00 (a valid tap's: unclamped; any other: within [-2, H] x [-2, W])
 };
+
+// floor of a sampling coordinate -> integer cell origin, kept inside [-2, n].  A valid tap's floor lies in [-1, n - 1] and is untouched.
+// An invalid tap's may lie beyond the range of int, be +-inf or NaN (which fails the first comparison): converted as it is, a position
+// of 2^31 or more saturates to INT_MAX, `h0 + 1` wraps, the clamp of the lower corner - compiled as min(max(h0, -1) + 1, H - 1) - yields
+// INT_MIN, and the corner loads of the callers, which are unconditional (their weight is 0), read 8 GiB below the plane.
+__device__ __forceinline__ int cell_origin(float f, int n) { return (int)(f > -2.f ? (f < (float)n ? f : (float)n) : -2.f); }
 
 __device__ __forceinline__ Tap resolve_tap(float h, float w, int H, int W) {
   Tap t;
   const bool valid = (h > -1.f) && (w > -1.f) && (h < (float)H) && (w < (float)W);
   const float fh = floorf(h), fw = floorf(w);
-  const int h0 = (int)fh, w0 = (int)fw, h1 = h0 + 1, w1 = w0 + 1;
+  const int h0 = cell_origin(fh, H), w0 = cell_origin(fw, W), h1 = h0 + 1, w1 = w0 + 1;
   t.h0 = h0;
   t.w0 = w0;
   t.lh = h - fh;

@@ -233,7 +233,7 @@ __global__ __launch_bounds__(256, 2) void dcn_tapwin_fwd_kernel(const DcnTapwinA
     const float h = (float)(oy0 + s - 1 + ti) + d[3 * s], w = (float)(ox - 1 + tj) + d[3 * s + 1];
     const bool valid = pix_ok && h > -1.f && w > -1.f && h < (float)a.H && w < (float)a.W;  // .cu:618
     const float fh = floorf(h), fw = floorf(w);
-    const float lh = h - fh, lw = w - fw, m = d[3 * s + 2];
+    const float lh = valid ? h - fh : 0.f, lw = valid ? w - fw : 0.f, m = d[3 * s + 2];  // (inf - inf and NaN stay out of the weights: 0 x NaN is not 0)
     const int ry = (int)fh - wy0, rx = (int)fw - wx0;
     const bool inside = valid && ry >= 0 && ry <= IH - 2 && rx >= 0 && rx <= IW - 2;
     const float mm = inside ? m : 0.f;  // (a valid tap outside the window: zero here, added by the fix-up pass)

@@ -266,6 +266,11 @@ int edvr_conv2d_executed_flops(const edvr_conv2d_desc *d, double *flops);
  * mask (B, dg*kh*kw, Ho, Wo); weight (Co, C/groups, kh, kw); bias (Co) or NULL; y (B,Co,Ho,Wo).
  * offset_bstride / mask_bstride: elements between consecutive images of offset / mask
  * (0 = contiguous), so channel-sliced views of one conv_offset output can be passed without a copy.
+ * Validity rule, every entry point below (forward, backward, DCNv1, every dtype, every kernel class and scatter strategy): a tap whose
+ * sampling position (h, w) = regular position + offset lies outside (-1, H) x (-1, W) - offsets of any size, beyond the range of int,
+ * +-inf and NaN included; NaN fails the comparisons, as in deform_conv_cuda_kernel.cu:618 - adds nothing to y, dX or dW and has
+ * dOffset = dMask = 0 exactly, whatever its (finite) mask.  A diverging conv_offset yields zeros there, never NaN
+ * (tests/test_gpu_dcn_poison.py).  x, mask, weight and dy are the caller's to keep finite: 0 x NaN is NaN here as in the reference.
  * act: EDVR_ACT_* applied to y in the GEMM epilogue (EDVR_ACT_NONE = the reference op; PCDAlignment
  * follows two of its four DCNs with LeakyReLU, edvr_arch.py:103-104,116).
  * halo_hint: performance hint only: every class computes the same operator, but their summation orders (and the tap-window class's

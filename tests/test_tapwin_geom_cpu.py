@@ -74,9 +74,9 @@ def test_constant_field_shifts_by_the_constant_and_centres_every_lane():
 
 
 def test_shift_of_non_finite_sample_pixels_follows_the_fminf_fmaxf_clamp_chain():
-    """Arithmetic only (no kernel takes such input in the tests): fminf / fmaxf drop a NaN operand; 0.5f * (-Inf + Inf) is NaN, which
-    fmaxf(., -16384) turns into -16384."""
-    nan, inf = float('nan'), float('inf')
+    """Arithmetic only (the kernels take such input in tests/test_gpu_dcn_poison.py): fminf / fmaxf drop a NaN operand;
+    0.5f * (-Inf + Inf) is NaN, which fmaxf(., -16384) turns into -16384."""
+    nan, inf, flt_max = float('nan'), float('inf'), float(np.finfo(np.float32).max)
     def shift(vals):  # the eight sample pixels of one 8 x 32 tile, every other pixel 100 (never read)
         pl = np.full((8, 32), 100., np.float32)
         for v, (r, c) in zip(vals, [(r, c) for r in U.SAMPLE_ROWS for c in U.SAMPLE_COLS]):
@@ -90,6 +90,15 @@ def test_shift_of_non_finite_sample_pixels_follows_the_fminf_fmaxf_clamp_chain()
     assert shift([inf, -inf] + [0.] * 6) == -16384
     assert shift([1e9] + [0.] * 7) == 16384 and shift([-1e9] + [0.] * 7) == -16384
     assert shift([3e38] * 8) == 16384                      # mn + mx overflows to +Inf: clamped
+    # ... every sample non-finite, and the values of tests/util_dcn_poison.py next to ordinary ones
+    assert shift([inf] * 8) == 16384 and shift([-inf] * 8) == -16384 and shift([-3e38] * 8) == -16384
+    assert shift([-inf, inf] * 4) == -16384                # mn = -Inf, mx = +Inf: mid = NaN
+    assert shift([nan] * 6 + [-inf, inf]) == -16384 and shift([nan] * 7 + [inf]) == 16384 and shift([nan] * 7 + [-inf]) == -16384
+    assert shift([nan, inf, 2., 2., 2., 2., 2., 2.]) == 16384 and shift([nan, -inf, 2., 2., 2., 2., 2., 2.]) == -16384
+    assert shift([flt_max, -flt_max] + [0.] * 6) == 0      # mn + mx = 0 exactly: no overflow on the way
+    assert shift([flt_max] + [0.] * 7) == 16384 and shift([-flt_max] + [0.] * 7) == -16384
+    assert shift([1e4] + [0.] * 7) == 5000 and shift([-1e4] + [2.] * 7) == -4999  # 'far' is inside the clamp: half way out
+    assert shift([2147483520.] + [0.] * 7) == 16384 and shift([-2147483648.] + [0.] * 7) == -16384 and shift([3e9, -3e9] + [0.] * 6) == 0
 
 
 def _ladder_census(cpg):
