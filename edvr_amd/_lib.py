@@ -110,6 +110,8 @@ PROTOTYPES = {
     'edvr_yuv420_to_rgb_sited_u8': (i32, [vp, vp, i32, i32, i32, i64, vp, i32, i32, i32, vp]),
     'edvr_rgb_to_yuv420_sited_u8': (i32, [vp, vp, i32, i32, i32, i64, vp, i32, i32, vp]),
     'edvr_deinterlace': (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i64, i64, i32, i32, vp]),
+    'edvr_field_match': (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i64, i32, i32, i32, vp]),
+    'edvr_field_weave': (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i64, i64, i32, vp]),
     'edvr_frame_sad_rgb_u8': (i32, [vp, vp, vp, i32, i32, i32, i64, vp]),
     'edvr_frame_sad_rgb_f32': (i32, [vp, vp, vp, i32, i32, i32, i64, vp]),
     'edvr_jpeg_roundtrip_u8': (i32, [vp, vp, vp, i32, i32, i32, i32, i64, i64, i32, vp]),

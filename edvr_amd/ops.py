@@ -2324,6 +2324,113 @@ def deinterlace(yuv, H, W, format='420', *, first='top', mode='field', prev=None
     return out
 
 
+# ------------------------------------------------------------------------------------------------ inverse telecine (csrc/telecine.hip)
+FIELD_MATCH_COLUMNS = ('S_c', 'S_p', 'mic_c', 'mic_p', 'A', 'B', 'C')  # the columns of field_match's table
+FIELD_MATCHES = {'c': 0, 'p': 1}  # field_weave's `matches`: the second field comes from the frame itself or from the frame before
+
+
+def _film_level(v, what):
+    if isinstance(v, bool) or not isinstance(v, int) or not 0 <= v <= 255:
+        raise ValueError(f'{what} is an 8-bit level, an integer in 0 ... 255, got {v!r}')
+    return v
+
+
+def _overlaps(out, *inputs):
+    b0, b1 = _byte_span(out)
+    for t in inputs:
+        if t is not None:
+            a0, a1 = _byte_span(t)
+            if a0 < b1 and b0 < a1:
+                return True
+    return False
+
+
+def field_match(yuv, H, W, format='420', *, first='top', prev=None, prev2=None, nt=2, ct=9, out=None):
+    """The measurements inverse telecine decides on (integers only), for all n frames in ONE kernel launch behind
+    a clear of the table.  yuv: uint8 (n, >= yuv_frame_size(H, W, format)) on the GPU, as deinterlace takes it - stride(1) == 1, any
+    row stride and base offset (`buf[:, 6:]` of a Y4MReader buffer), even ones above 8 bits; first: 'top' | 'bottom', the field that is
+    earlier in time.  Only luma is read.  Returns int64 (n, 7) on the device, columns FIELD_MATCH_COLUMNS: for frame i, the comb sums
+    S_c, S_p and the largest 16 x 16 block counts mic_c, mic_p of the two candidates - the frame as it is (c) and its first field woven
+    with the second field of the frame before (p) - and the field differences A (first field against frame i - 1's), B (second field
+    against frame i - 1's), C (second field against frame i - 2's).  prev / prev2: frame -1 / frame -2, uint8 (framesize,) or with a
+    leading 1; where an earlier frame does not exist p is c and the differences are 0.  nt, ct: the comb thresholds in 8-bit levels
+    (shifted by depth - 8).  Exact: a row does not depend on the batch it was computed in.  out: an int64 (n, 7) contiguous tensor
+    to write into instead.  Bytes booked: the luma plane of every frame once, and the table.  H >= 4, any W.  NotImplementedError for
+    CPU tensors, ValueError for bad names, shapes and layouts."""
+    fmt = yuv_format(format)
+    if first not in DEINT_FIRST:
+        raise ValueError(f'first must be one of {sorted(DEINT_FIRST)}, got {first!r}')
+    nt, ct = _film_level(nt, 'nt'), _film_level(ct, 'ct')
+    require_gpu(yuv, dtypes=(torch.uint8,))
+    H, W = int(H), int(W)
+    if H < 4:
+        raise ValueError(f'field_match: a frame needs at least 4 rows, so that every plane has 2, got {H} x {W}')
+    sx, sy, depth, _ = fmt
+    n, fs, stride = _yuv_batch(yuv, H, W, fmt, 'yuv')
+    prev, prev2 = _deint_context(prev, fs, depth, 'prev'), _deint_context(prev2, fs, depth, 'prev2')
+    if out is None:
+        out = torch.empty((n, len(FIELD_MATCH_COLUMNS)), dtype=torch.int64, device=yuv.device)
+    else:
+        require_gpu(out, dtypes=(torch.int64,))
+        if tuple(out.shape) != (n, len(FIELD_MATCH_COLUMNS)) or not out.is_contiguous():
+            raise ValueError(f'out is a contiguous int64 ({n}, {len(FIELD_MATCH_COLUMNS)}) tensor, got {tuple(out.shape)}')
+        if _overlaps(out, yuv, prev, prev2):
+            raise ValueError('out overlaps an input')
+    _run('field_match', lambda: _lib.check(_lib.lib().edvr_field_match(_ptr(yuv), _ptr(prev), _ptr(prev2), _ptr(out), n, H, W, sx, sy, depth, stride,
+                                                                       DEINT_FIRST[first], nt, ct, _stream()), 'edvr_field_match'),
+         0, float(n) * (H * W * (2 if depth > 8 else 1) + 8 * len(FIELD_MATCH_COLUMNS)))
+    return out
+
+
+def field_weave(yuv, H, W, format='420', *, first='top', frames, matches, prev=None, out=None):
+    """Film frames put back together from their fields, all three planes, in ONE launch.  yuv: uint8 (n, >= framesize)
+    on the GPU, as field_match takes it.  frames, matches: host sequences of equal length k >= 1 - output frame j takes its rows of
+    `first`'s parity (the first field) from input frame frames[j] and its other rows from the same frame (matches[j] == 0, 'c') or from
+    frame frames[j] - 1 (1, 'p'); frame -1 is `prev`, uint8 (framesize,) or with a leading 1.  Returns uint8 (k, framesize).  out: a
+    uint8 (k, >= framesize) batch to write into instead, stride(1) == 1, any row stride and base offset (`buf[:, 6:]`); bytes outside the
+    frames are left alone; it must not overlap an input.  The (frame, match) table travels to the device as one small int32 tensor.
+    Bytes booked: every output byte read once and written once.  NotImplementedError for CPU tensors; ValueError for bad names,
+    shapes and layouts, an index outside [0, n), a match other than 0 / 1, and a 'p' match of frame 0 without prev."""
+    fmt = yuv_format(format)
+    if first not in DEINT_FIRST:
+        raise ValueError(f'first must be one of {sorted(DEINT_FIRST)}, got {first!r}')
+    require_gpu(yuv, dtypes=(torch.uint8,))
+    H, W = int(H), int(W)
+    if H < 4:
+        raise ValueError(f'field_weave: a frame needs at least 4 rows, so that every plane has 2, got {H} x {W}')
+    sx, sy, depth, _ = fmt
+    n, fs, stride = _yuv_batch(yuv, H, W, fmt, 'yuv')
+    prev = _deint_context(prev, fs, depth, 'prev')
+    try:
+        frames, matches = list(frames), list(matches)
+    except TypeError:
+        raise ValueError('frames and matches are sequences of integers') from None
+    if not frames or len(frames) != len(matches):
+        raise ValueError(f'frames and matches are of one length, at least 1: got {len(frames)} and {len(matches)}')
+    for f, m in zip(frames, matches):
+        if isinstance(f, bool) or not isinstance(f, int) or not 0 <= f < n:
+            raise ValueError(f'frames are indices into the {n} input frames, got {f!r}')
+        if isinstance(m, bool) or m not in (0, 1):
+            raise ValueError(f"matches are 0 ('c') or 1 ('p'), got {m!r}")
+        if m == 1 and f == 0 and prev is None:
+            raise ValueError("a 'p' match of frame 0 needs prev: its second field lies in the frame before the batch")
+    k = len(frames)
+    if out is None:
+        out = torch.empty((k, fs), dtype=torch.uint8, device=yuv.device)
+    else:
+        require_gpu(out, dtypes=(torch.uint8,))
+        if out.dim() == 2 and out.shape[0] != k:
+            raise ValueError(f'out holds {out.shape[0]} frames, the list names {k}')
+    _, _, out_stride = _yuv_batch(out, H, W, fmt, 'out')
+    if _overlaps(out, yuv, prev):
+        raise ValueError('out overlaps an input')
+    table = torch.tensor([v for pair in zip(frames, matches) for v in pair], dtype=torch.int32).to(yuv.device, non_blocking=True)
+    _run('field_weave', lambda: _lib.check(_lib.lib().edvr_field_weave(_ptr(yuv), _ptr(prev), _ptr(out), _ptr(table), n, k, H, W, sx, sy, depth, stride,
+                                                                       out_stride, DEINT_FIRST[first], _stream()), 'edvr_field_weave'),
+         0, 2.0 * k * fs)
+    return out
+
+
 # ------------------------------------------------------------------------------------------------ scene cuts
 def frame_sad(frames, prev=None, out=None):
     """How much consecutive frames differ, for scene-cut detection (edvr_amd/shots.py), in ONE kernel launch.

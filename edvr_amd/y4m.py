@@ -13,9 +13,12 @@ here works on non-seekable streams (pipes), holds a bounded number of frames and
 copies keep the device busy while the host reads and writes.  Interlaced streams (It, Ib) are read on request and deinterlaced on the
 device, at field rate, before the colour conversion: `deinterlaced` / `restore_y4m(deinterlace=...)` around ops.deinterlace.
 """
+import math
+
 import torch
 
 from . import ops
+from .telecine import DEFAULT_MI, PulldownDetector
 
 MAGIC = b'YUV4MPEG2'
 FRAME = b'FRAME\n'
@@ -234,11 +237,117 @@ def double_rate(fps):
     return f'{2 * int(num)}:{den}'
 
 
+def film_rate(fps):
+    """The F tag of a decimated film-rate stream: 4 / 5 of the rate, reduced - '30000:1001' -> '24000:1001'; None (no tag) stays None."""
+    if fps is None:
+        return None
+    num, sep, den = fps.partition(':')
+    if not (sep and num.isascii() and den.isascii() and num.isdigit() and den.isdigit()) or int(den) == 0:
+        raise ValueError(f'the frame rate F{fps} is not <num>:<den>: its film rate cannot be formed')
+    num, den = 4 * int(num), 5 * int(den)
+    g = math.gcd(num, den)
+    return f'{num // g}:{den // g}'
+
+
+def inverse_telecined(pieces, H, W, format='420', first='top', decimate=True, nt=2, ct=9, mi=DEFAULT_MI, stats=None):
+    """A generator over device byte batches of FILM frames: `pieces` is an iterable of uint8 (k, >= framesize) batches of
+    consecutive frames of a telecined stream, k >= 1 and any mix of sizes (`buf[:, 6:]` of the reader's buffers).  Every frame is
+    measured (ops.field_match, with the two frames before it as context), matched to the field that completes its first field and
+    scored as a repeat (telecine.PulldownDetector); of every cycle of 5 the most repeated frame is dropped (decimate) and every kept
+    frame is woven from its matching fields (ops.field_weave) - or, where even the better weave is combed, deinterlaced from its first
+    field (ops.deinterlace(mode='frame') with the frames around it as prev / next).  The concatenated result is the definition applied
+    to the whole clip, whatever the pieces.  Batches that turn out empty are not yielded.
+    Held: the pieces that reach back to the frame before the oldest frame not yet written - a frame waits for the end of its cycle
+    of 5 and, combed, for the frame after it - and the last two frames for the next piece's measurement.  One host wait per piece, on
+    an event recorded right after that piece's field_match launch and the copy of its table to pinned memory; the NEXT piece is
+    fetched (its copy to the device issued by whoever makes the pieces) and measured before that wait, so the device has work while
+    the host decides.  stats: a dict that receives 'film_matches' (0 = c, 1 = p per input frame), 'film_combed' and 'film_dropped'
+    (input frame indices) and 'film_dropped_scores' (D of the dropped frames) when the stream has ended."""
+    fs = ops.yuv_frame_size(H, W, format)
+    det = PulldownDetector(mi=mi, decimate=decimate)
+    held = []        # (index of the piece's first frame, piece), oldest first
+    last2 = []       # the last two frames that arrived
+    ready = []       # (index, match, combed) of the kept frames whose fate is final, not yet written
+    waiting = None   # (pinned table, event) of the piece measured last
+    arrived = 0
+
+    def frame(i):
+        for start, piece in held:
+            if start <= i < start + piece.shape[0]:
+                return piece[i - start]
+        raise AssertionError(f'frame {i} is no longer held')
+
+    def decide(final):
+        nonlocal waiting
+        if waiting is not None:
+            table, event = waiting
+            if event is not None:
+                event.synchronize()
+            ready.extend((i, m, c) for i, m, c, kept in det.push(table) if kept)
+            waiting = None
+        if final:
+            ready.extend((i, m, c) for i, m, c, kept in det.finish() if kept)
+
+    def written(final):
+        """The frames of `ready` that can be written now, as one batch (None: none) - a combed one needs the frame after it."""
+        take = 0
+        while take < len(ready) and (not ready[take][2] or ready[take][0] + 1 < arrived or final):
+            take += 1
+        if not take:
+            return None
+        now = ready[:take]
+        del ready[:take]
+        out = torch.empty((take, fs), dtype=torch.uint8, device=held[0][1].device)
+        at = 0
+        for start, piece in held:  # one weave per piece that holds some of the frames
+            mine = [(i, m) for i, m, _ in now if start <= i < start + piece.shape[0]]
+            if mine:
+                ops.field_weave(piece, H, W, format, first=first, frames=[i - start for i, _ in mine], matches=[m for _, m in mine],
+                                prev=frame(start - 1) if mine[0] == (start, 1) else None, out=out[at:at + len(mine)])
+                at += len(mine)
+        for j, (i, _, combed) in enumerate(now):
+            if combed:  # T9's fallback, over what the weave put there
+                ops.deinterlace(frame(i)[None], H, W, format, first=first, mode='frame', prev=frame(i - 1) if i else None,
+                                next=frame(i + 1) if i + 1 < arrived else None, out=out[j:j + 1])
+        oldest = (ready[0][0] if ready else det.released) - 1  # a p weave and the fallback read the frame before
+        while held and held[0][0] + held[0][1].shape[0] <= min(oldest, arrived - 1):
+            held.pop(0)
+        return out
+
+    for piece in pieces:
+        k = piece.shape[0]
+        table = ops.field_match(piece, H, W, format, first=first, prev=last2[-1] if last2 else None, prev2=last2[-2] if len(last2) > 1 else None,
+                                nt=nt, ct=ct)
+        host = _host_buffer((k, 7 * 8)).view(torch.int64)
+        host.copy_(table, non_blocking=True)
+        event = None
+        if piece.is_cuda:
+            event = torch.cuda.Event()
+            event.record()
+        decide(False)  # the piece before this one: its table has been on its way since before this piece was fetched
+        waiting = (host, event)
+        held.append((arrived, piece))
+        arrived += k
+        last2 = (last2 + [piece[j] for j in range(max(k - 2, 0), k)])[-2:]
+        out = written(False)
+        if out is not None:
+            yield out
+    decide(True)
+    if held:
+        out = written(True)
+        if out is not None:
+            yield out
+    if stats is not None:
+        stats.update(film_matches=list(det.matches), film_combed=[i for i, c in enumerate(det.combed) if c], film_dropped=list(det.dropped),
+                     film_dropped_scores=[det.scores[i] for i in det.dropped])
+
+
 def resolve_field_order(deinterlace, field_order, reader):
     """restore_y4m's (deinterlace, field_order) -> (`first` of ops.deinterlace or None: nothing to do, mode).  'auto' follows the
-    reader's I tag - It: 'top', Ib: 'bottom', anything else: progressive, passed through; 'tff' / 'bff' deinterlace whatever the tag says."""
-    if deinterlace not in (None, 'field', 'frame'):
-        raise ValueError(f"deinterlace must be None, 'field' or 'frame', got {deinterlace!r}")
+    reader's I tag - It: 'top', Ib: 'bottom', anything else: progressive, passed through; 'tff' / 'bff' deinterlace whatever the tag says.
+    mode is `deinterlace` itself: 'field' | 'frame' for ops.deinterlace, 'film' for `inverse_telecined`."""
+    if deinterlace not in (None, 'field', 'frame', 'film'):
+        raise ValueError(f"deinterlace must be None, 'field', 'frame' or 'film', got {deinterlace!r}")
     if field_order != 'auto' and field_order not in FIELD_ORDERS:
         raise ValueError(f"field_order must be 'auto' or one of {sorted(FIELD_ORDERS)}, got {field_order!r}")
     if deinterlace is None:
@@ -249,7 +358,8 @@ def resolve_field_order(deinterlace, field_order, reader):
 
 
 def restore_y4m(net, src, dst, *, matrix_in=None, matrix_out=None, chroma='bilinear', read_frames=8, on_chunk=None, stats=None, out_format=None,
-                siting_in='center', siting_out=None, deinterlace=None, field_order='auto', **restorer_kwargs):
+                siting_in='center', siting_out=None, deinterlace=None, field_order='auto', film_decimate=True, film_params=None,
+                **restorer_kwargs):
     """Restore a Y4M stream with `net` (an EDVR in eval mode, on the GPU) into a Y4M stream; returns the number of frames.  Call it under
     torch.no_grad().
 
@@ -285,7 +395,13 @@ def restore_y4m(net, src, dst, *, matrix_in=None, matrix_out=None, chroma='bilin
     untagged stream passes through untouched, no launch - or 'tff' / 'bff', which deinterlace whatever the tag says (mis-tagged
     captures).  The stage (`deinterlaced`: ops.deinterlace piece by piece with its neighbours' frames as context) sits between the copy
     to the device and the colour conversion; everything after it sees a progressive video of its output frames - `cuts` indices count
-    those - and the output is written Ip."""
+    those - and the output is written Ip.
+    Film: deinterlace='film' undoes 2:3 pulldown instead - `inverse_telecined` in the same place: fields that belong to one
+    film frame are woven back together, bit for bit, and (film_decimate, the default) the most repeated frame of every 5 is dropped; F
+    is then written as `film_rate` of the input's, 4 / 5 of it ('30000:1001' -> '24000:1001'), and unchanged with film_decimate=False.
+    film_params: a dict with any of nt, ct, mi, the thresholds of the definition.  stats also receives 'film_matches', 'film_combed',
+    'film_dropped' and 'film_dropped_scores'; frames listed in 'film_combed' had no clean match and were deinterlaced from one field -
+    many of them mean the passage is video, not film: use 'field'."""
     from .video import VideoRestorer
     if deinterlace is None:
         reader = src if isinstance(src, Y4MReader) else Y4MReader(src, formats=ALL_FORMATS)
@@ -314,6 +430,13 @@ def restore_y4m(net, src, dst, *, matrix_in=None, matrix_out=None, chroma='bilin
     matrix_in = matrix_in or default_matrix(H, W)
     matrix_out = matrix_out or default_matrix(Ho, Wo)
     fps = double_rate(reader.fps) if first is not None and mode == 'field' else reader.fps
+    film = {}
+    if first is not None and mode == 'film':
+        unknown = set(film_params or {}) - {'nt', 'ct', 'mi'}
+        if unknown:
+            raise ValueError(f'film_params holds nt, ct and mi, got {sorted(unknown)}')
+        if film_decimate:
+            fps = film_rate(reader.fps)
     writer = Y4MWriter(dst, Wo, Ho, fps, reader.aspect, reader.range, fmt_out, siting_out)
     row = len(FRAME) + writer.framesize
     marks = torch.tensor(list(FRAME), dtype=torch.uint8).to(device)
@@ -326,7 +449,13 @@ def restore_y4m(net, src, dst, *, matrix_in=None, matrix_out=None, chroma='bilin
             yield host.to(device, non_blocking=True)[:, len(FRAME):]
 
     def decoded():
-        for yuv in (batches() if first is None else deinterlaced(batches(), H, W, fmt_in, first, mode)):
+        if first is None:
+            stage = batches()
+        elif mode == 'film':
+            stage = inverse_telecined(batches(), H, W, fmt_in, first, bool(film_decimate), stats=film, **(film_params or {}))
+        else:
+            stage = deinterlaced(batches(), H, W, fmt_in, first, mode)
+        for yuv in stage:
             if plain420:
                 yield ops.yuv420_to_rgb(yuv, H, W, matrix_in, reader.range, chroma, **kw_in)
             else:
@@ -362,6 +491,7 @@ def restore_y4m(net, src, dst, *, matrix_in=None, matrix_out=None, chroma='bilin
         dst.flush()
     if stats is not None:
         stats['frames'] = writer.frames_written
+        stats.update(film)
         if getattr(vr, 'cuts', None) is not None:
             stats.update(cuts=vr.cuts_found, cut_scores=vr.cut_scores, cut_mafd=vr.cut_mafd)
     return writer.frames_written

@@ -799,6 +799,35 @@ int edvr_rgb_to_yuv420_sited_u8(const uint8_t *rgb, uint8_t *yuv, int n, int H, 
 int edvr_deinterlace(const uint8_t *yuv, const uint8_t *prev, const uint8_t *next, uint8_t *out, int n, int H, int W, int sub_x, int sub_y,
                      int depth, int64_t in_stride, int64_t out_stride, int bottom_first, int field_rate, edvr_stream_t stream);
 
+/* Inverse telecine (csrc/telecine.hip; definition: DESIGN 4.20, T1 - T9, integers only).  Replaces nothing in the reference: it is the
+ * `ffmpeg -vf fieldmatch,decimate` pass otherwise run in front of the pipe.  No bit-compatibility with those filters or TIVTC is claimed.
+ * Frames are as edvr_deinterlace takes them: n frames of the format (sub_x, sub_y, depth), in_stride BYTES apart at any base address
+ * (both even for 16-bit samples); bottom_first: the odd rows are the earlier field; q = bottom_first is the row parity of the first field.
+ *
+ * edvr_field_match: the metrics.  table: int64 (n, 7), row i = S_c, S_p, mic_c, mic_p, A, B, C of frame i, from LUMA alone (R = H rows):
+ *   W_c = L_i; W_p = the rows of parity q of L_i and the other rows of L_(i-1) (W_c where frame i - 1 does not exist);
+ *   comb k at 1 <= y <= R - 2: d1 = W[y] - W[y-1], d2 = W[y] - W[y+1], k = min(|d1|, |d2|) where both are > 0 or both < 0, else 0;
+ *   S = sum of max(k - (nt << (depth - 8)), 0); mic = the largest count of k > (ct << (depth - 8)) in a 16 x 16 block anchored at (0, 0);
+ *   A = sum |L_i - L_(i-1)| over the rows of parity q, B over the other rows, C = sum |L_i - L_(i-2)| over the other rows; 0 where the
+ *   earlier frame does not exist.  prev / prev2: frame -1 / frame -2, ONE dense frame each, or NULL.
+ * Exact 64-bit integers: a row does not depend on the batch it was computed in.  TWO operations on the stream: a clear of the table
+ * (hipMemsetAsync) and ONE kernel launch, grid (strips of 16 rows, workgroups per strip, n); a workgroup ends with one 64-bit integer
+ * atomic add per non-zero sum and one integer atomic max per non-zero mic.
+ * EDVR_ERR_ARG: null yuv / table, n < 1 or > 32767, W < 1, H < 4, depth outside 8 ... 16, a subsampling other than the three, a stride
+ * shorter than a frame with n > 1, an odd pointer or stride with 16-bit samples, H W > 2^29, bottom_first other than 0 / 1, nt or ct
+ * outside 0 ... 255.  No allocation, no wait.
+ *
+ * edvr_field_weave: T9's weave, ONE launch for n_out output frames, all three planes.  table: int32 (n_out, 2) ON THE DEVICE, row j =
+ * (input frame index s in [0, n), match: 0 = c, 1 = p).  Output frame j takes its rows of parity q from frame s and its other rows from
+ * frame s (c) or frame s - 1 (p; frame -1 is `prev`, one dense frame or NULL).  A row whose source does not exist (s outside [0, n), p at
+ * s = 0 without prev) is not written.  Output frames lie out_stride bytes apart at any base address; bytes between them are not written.
+ * out must not overlap the inputs.  A lane moves 16 bytes of a row, whole where they lie inside it, byte by byte at its end.
+ * EDVR_ERR_ARG: null yuv / out / table, n or n_out < 1 or > 32767, and the size / format / stride conditions above. */
+int edvr_field_match(const uint8_t *yuv, const uint8_t *prev, const uint8_t *prev2, int64_t *table, int n, int H, int W, int sub_x, int sub_y,
+                     int depth, int64_t in_stride, int bottom_first, int nt, int ct, edvr_stream_t stream);
+int edvr_field_weave(const uint8_t *yuv, const uint8_t *prev, uint8_t *out, const int32_t *table, int n, int n_out, int H, int W, int sub_x,
+                     int sub_y, int depth, int64_t in_stride, int64_t out_stride, int bottom_first, edvr_stream_t stream);
+
 /* Frame-to-frame change for scene-cut detection (csrc/shots.hip; definition: DESIGN 4.13).  The bytes R, G, B of a pixel are the input's
  * own (_u8: x (n, H, W, 3)) or its tensor2img bytes (_f32: x (n, 3, H, W); clamp to [0, 1], x 255, round half to even, NaN -> 0); in
  * integers Y8 = ((66 R + 129 G + 25 B + 128) >> 8) + 16, and

@@ -9,7 +9,12 @@
 Interlaced input (It / Ib: tape, DVD, 1080i) needs `--deinterlace`: the fields are deinterlaced on the device (edvr_amd.ops.deinterlace,
 DESIGN 4.19) before anything else sees them and every field becomes a frame - the output is progressive at twice the frame rate;
 `--deinterlace frame` keeps the rate (one frame per input frame, from its first field).  `--field-order tff|bff` overrides a wrong
-tag; the default `auto` follows the header and passes a progressive stream through untouched.
+tag; the default `auto` follows the header and passes a progressive stream through untouched.  `--deinterlace film` is for film shown
+as video (NTSC DVDs, broadcast captures: 24000/1001 frames/s stretched to 60000/1001 fields/s by 2:3 pulldown): the fields of every film
+frame are woven back together, bit for bit, and the repeated frame of every five is dropped (edvr_amd.y4m.inverse_telecined) -
+the output is progressive at 4 / 5 of the frame rate; `--no-decimate` keeps every frame and the rate, `--film-json FILE` writes every
+frame's match, the frames that had no clean match (deinterlaced from one field instead: many of them mean video, use `field`) and the
+dropped frames with their scores.
 
 The input is 4:2:0, 4:2:2 or 4:4:4 at 8 ... 16 bits (C420jpeg, C422p10, C444p12 ...: 10-bit phone and camera footage, 4:2:2 intermediates
 and 4:4:4 screen captures go in as they are - ffmpeg's yuv4mpegpipe muxer writes anything but 8-bit 4:2:0 only with `-strict -1`, and
@@ -75,7 +80,12 @@ def restore(args, log=log):
         if deint:
             first, _ = resolve_field_order(deint, args.field_order, reader)
             kwargs.update(deinterlace=deint, field_order=args.field_order)
-            log(f'{args.input}: I{reader.interlace}, ' + (f'deinterlaced at {deint} rate, {first} field first' if first else 'progressive: nothing to deinterlace'))
+            if deint == 'film':
+                kwargs.update(film_decimate=not getattr(args, 'no_decimate', False))
+                how = 'pulldown undone' + ('' if kwargs['film_decimate'] else ', every frame kept')
+            else:
+                how = f'deinterlaced at {deint} rate'
+            log(f'{args.input}: I{reader.interlace}, ' + (f'{how}, {first} field first' if first else 'progressive: nothing to deinterlace'))
             deint = first is not None
         siting_in = resolve_siting(getattr(args, 'siting', 'center'), reader)
         siting_out = getattr(args, 'siting_out', None)
@@ -111,6 +121,8 @@ def restore(args, log=log):
         log(f'{args.output}: {n} frames in {dt:.1f} s ({n / max(dt, 1e-9):.2f} frames/s)')
         if 'cuts' in stats:
             report_cuts(args, stats, log)
+        if 'film_matches' in stats:
+            report_film(args, stats, log)
         if niqe_path:
             report_niqe(args, niqe_out, niqe_in, log)
     finally:
@@ -131,6 +143,19 @@ def cut_kwargs(args):
     if getattr(args, 'min_shot', None) is not None:
         out['min_shot'] = args.min_shot
     return out
+
+
+def report_film(args, stats, log=log):
+    """What inverse telecine decided; with --film-json every frame's match, the combed and the dropped frames with their scores."""
+    m = stats['film_matches']
+    log(f'{args.input}: {len(m)} frames read, {sum(m)} matched to the frame before, {len(stats["film_dropped"])} dropped, '
+        f'{len(stats["film_combed"])} without a clean match' + (f' (frames {stats["film_combed"][:8]} ...)' if stats['film_combed'] else ''))
+    if getattr(args, 'film_json', None):
+        import json
+        record = {'frames_in': len(m), 'frames': stats['frames'], 'matches': ['cp'[v] for v in m], 'combed': stats['film_combed'],
+                  'dropped': stats['film_dropped'], 'dropped_scores': stats['film_dropped_scores']}
+        with open(args.film_json, 'w') as f:
+            json.dump(record, f, indent=1)
 
 
 def report_cuts(args, stats, log=log):
@@ -196,9 +221,12 @@ def parse_args(argv=None):
                     help="the siting the output is encoded for (default: the input's)")
     ap.add_argument('--out-format', default=None, metavar='NAME',
                     help="the output's format: 420 | 422 | 444 with an optional depth p9 ... p16, e.g. 420p10 (default: the input's)")
-    ap.add_argument('--deinterlace', nargs='?', const='field', default=None, choices=['field', 'frame'],
+    ap.add_argument('--deinterlace', nargs='?', const='field', default=None, choices=['field', 'frame', 'film'],
                     help='deinterlace an interlaced stream (It / Ib) on the device first: field - every field becomes a frame, the rate doubles '
-                         '(the default of a bare --deinterlace); frame - one frame per input frame, from its first field')
+                         '(the default of a bare --deinterlace); frame - one frame per input frame, from its first field; film - undo 2:3 '
+                         'pulldown: matching fields are woven back into film frames and the repeated frame of every 5 is dropped')
+    ap.add_argument('--no-decimate', action='store_true', help='with --deinterlace film: keep every frame and the frame rate')
+    ap.add_argument('--film-json', default=None, metavar='FILE', help='with --deinterlace film: write the matches, combed and dropped frames there')
     ap.add_argument('--field-order', default='auto', choices=['auto', 'tff', 'bff'],
                     help="with --deinterlace: auto - the stream's tag, a progressive stream passes through; tff / bff - deinterlace whatever the tag says")
     ap.add_argument('--niqe', default=None, metavar='PARAMS.npz',
@@ -231,6 +259,8 @@ def parse_args(argv=None):
         ap.error('--cuts are strictly increasing frame indices, at least 1')
     if args.field_order != 'auto' and args.deinterlace is None:
         ap.error('--field-order needs --deinterlace')
+    if (args.no_decimate or args.film_json is not None) and args.deinterlace != 'film':
+        ap.error('--no-decimate and --film-json need --deinterlace film')
     if args.niqe_json is not None and args.niqe is None:
         ap.error('--niqe-json needs --niqe')
     if args.tile_blend is not None and args.tile is None:
