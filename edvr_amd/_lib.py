@@ -95,6 +95,8 @@ PROTOTYPES = {
     'edvr_copy_rect_blend_f32': (i32, [vp, vp, i32, i32, i32, i64, i32, i32, i32, i32, i64, i64, i64, i32, i32, f32, i32, i32, i32, i32, vp]),
     'edvr_imresize_bicubic_u8': (i32, [vp, vp, i32, i32, i32, i32, i32, ctypes.c_double, i32, i32, vp]),
     'edvr_imresize_bicubic_f32': (i32, [vp, vp, i32, i32, i32, i64, i32, i32, ctypes.c_double, i32, i32, vp]),
+    'edvr_resample_tile': (i32, [i32, i32, i32, i32, i32, i32, ctypes.POINTER(i32), ctypes.POINTER(i32)]),
+    'edvr_resample_f32': (i32, [vp, vp, i32, i32, i32, i32, i64, i32, i32, i64, vp, vp, i32, vp, vp, i32, vp]),
     'edvr_bd_downsample_u8': (i32, [vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]),
     'edvr_bd_downsample_f32': (i32, [vp, vp, i32, i32, i32, i64, i32, i32, i32, i32, vp]),
     'edvr_imresize_bicubic_u8_windows': (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]),

@@ -1932,6 +1932,69 @@ def imresize(frames, scale, antialiasing=True, out_dtype=torch.float32):
     return out
 
 
+# ------------------------------------------------------------------------------------------------ resampling to a size (csrc/resample.hip)
+def _resample_size(size):
+    try:
+        ho, wo = size
+        ho, wo = int(ho), int(wo)
+    except (TypeError, ValueError):
+        raise ValueError(f'size is (Ho, Wo), got {size!r}') from None
+    return ho, wo
+
+
+def resample_tile(H, W, Ho, Wo, Ty, Tx):
+    """(toh, tow): the output tile a workgroup of resample owns for (H, W) -> (Ho, Wo) with Ty / Tx taps (resample.taps) - tow is 64,
+    toh falls from 32 as H / Ho grows toward 8.  Host arithmetic: no GPU needed."""
+    toh, tow = ctypes.c_int(0), ctypes.c_int(0)
+    rc = _lib.lib().edvr_resample_tile(int(H), int(W), int(Ho), int(Wo), int(Ty), int(Tx), ctypes.byref(toh), ctypes.byref(tow))
+    if rc != 0:
+        raise ValueError(_lib.lib().edvr_last_error().decode())
+    return toh.value, tow.value
+
+
+def resample(frames, size, kernel='lanczos3', out=None):
+    """Frames at a stated size (the project's own definition) in ONE launch: frames float32 (n, c, H, W) with
+    dense planes (a slice of a longer video works, any base alignment), size = (Ho, Wo), each axis with its own ratio, 1/8 <= I / O <= 8;
+    kernel 'lanczos3' | 'bicubic' (Keys, -0.5) | 'bilinear', stretched by I / O when reducing.  Pixel centres are aligned, the edge
+    sample repeats, columns first, then rows, every sum in float64 in tap order and rounded to float32 once per pass; an axis that keeps
+    its length is the identity.  Nothing is clamped (Lanczos overshoots [0, 1]; the encoders saturate).  Returns float32 (n, c, Ho, Wo);
+    out: such a tensor with dense planes to write into instead (a slice of a longer one works); it must not overlap frames.  The axis
+    tables are made on the host once per (I, O, kernel, device) (resample.device_table): a later call allocates its output and
+    nothing else, and waits for nothing.  NotImplementedError for a CPU tensor; ValueError - before anything is launched - for a wrong
+    dtype, rank, kernel name or size, a ratio outside [1/8, 8], more than 65535 frames, a wrong `out`."""
+    from . import resample as tables
+    if not frames.is_cuda:
+        raise NotImplementedError('edvr_amd ops run on the GPU only (HIP/gfx950); got a CPU tensor')
+    if frames.dtype != torch.float32:
+        raise ValueError(f'resample takes float32 frames, got {frames.dtype}')
+    if frames.dim() != 4:
+        raise ValueError(f'frames are (n, c, H, W), got {tuple(frames.shape)}')
+    if kernel not in tables.KERNELS:
+        raise ValueError(f'kernel must be one of {sorted(tables.KERNELS)}, got {kernel!r}')
+    ho, wo = _resample_size(size)
+    n, c, H, W = frames.shape
+    if not 0 < n <= 65535 or c < 1 or H < 1 or W < 1:
+        raise ValueError(f'resample takes 1..65535 frames of at least one plane, got {tuple(frames.shape)}')
+    tables.check_axis(H, ho, 'the row')
+    tables.check_axis(W, wo, 'the column')
+    if out is None:
+        out = torch.empty((n, c, ho, wo), dtype=torch.float32, device=frames.device)
+    else:
+        if not out.is_cuda or out.device != frames.device or out.dtype != torch.float32:
+            raise ValueError(f'out is a float32 tensor on {frames.device}, got {out.dtype} on {out.device}')
+        if tuple(out.shape) != (n, c, ho, wo) or not _plane_contig(out):
+            raise ValueError(f'out is ({n}, {c}, {ho}, {wo}) with dense planes, got {tuple(out.shape)} with strides {tuple(out.stride())}')
+        if _overlaps(out, frames):
+            raise ValueError('out overlaps frames')
+    frames = _as_planes(frames)
+    fy, wy, ty = tables.device_table(H, ho, kernel, frames.device)
+    fx, wx, tx = tables.device_table(W, wo, kernel, frames.device)
+    _run('resample', lambda: _lib.check(_lib.lib().edvr_resample_f32(_ptr(frames), _ptr(out), n, c, H, W, _img_stride(frames), ho, wo, _img_stride(out),
+                                                                     _ptr(fy), _ptr(wy), ty, _ptr(fx), _ptr(wx), tx, _stream()), 'edvr_resample_f32'),
+         0, 4.0 * n * c * (H * W + ho * wo))  # source + output, each element once
+    return out
+
+
 # ------------------------------------------------------------------------------------------------ BD downsampling (csrc/bd.hip)
 def bd_downsample(frames, scale=4, out_dtype=torch.float32):
     """DUF's "BD" degradation (duf_downsample, basicsr/data/data_util.py:281-331) of a batch of frames in ONE launch: the 13 x 13 Gaussian

@@ -12,12 +12,16 @@ axis that is not subsampled and a sample above 8 bits is a little-endian 16-bit 
 here works on non-seekable streams (pipes), holds a bounded number of frames and uses no threads: pinned host buffers and non_blocking
 copies keep the device busy while the host reads and writes.  Interlaced streams (It, Ib) are read on request and deinterlaced on the
 device, at field rate, before the colour conversion: `deinterlaced` / `restore_y4m(deinterlace=...)` around ops.deinterlace.
+The result can leave at a delivery size instead of s W x s H: `fit_size` / `restore_y4m(out_height=..., square_pixels=...)` around
+ops.resample, on the float32 frames before the one quantisation.
 """
 import math
+from fractions import Fraction
 
 import torch
 
 from . import ops
+from .resample import KERNELS as RESAMPLE_KERNELS
 from .telecine import DEFAULT_MI, PulldownDetector
 
 MAGIC = b'YUV4MPEG2'
@@ -33,6 +37,72 @@ ALL_FORMATS = tuple(base + (f'p{d}' if d > 8 else '') for base in ('420', '422',
 def default_matrix(H, W):
     """What players assume when a stream does not say: BT.709 for HD sizes (W >= 1280 or H > 576), BT.601 below."""
     return 'bt709' if W >= 1280 or H > 576 else 'bt601'
+
+
+def _aspect_fraction(aspect):
+    """The A tag 'num:den' as a Fraction; None and the unknown aspect 0:0 count as 1:1."""
+    if aspect is None:
+        return Fraction(1)
+    num, sep, den = str(aspect).partition(':')
+    if not (sep and num.isascii() and den.isascii() and num.isdigit() and den.isdigit()):
+        raise ValueError(f'the aspect A{aspect} is not <num>:<den>')
+    if int(num) == 0 or int(den) == 0:
+        if int(num) == 0 and int(den) == 0:
+            return Fraction(1)
+        raise ValueError(f'the aspect A{aspect} has a zero on one side')
+    return Fraction(int(num), int(den))
+
+
+def _round_to_multiple(x, multiple):
+    """The multiple of `multiple` nearest to the Fraction x, ties up, at least `multiple`."""
+    return max(math.floor(x / multiple + Fraction(1, 2)), 1) * multiple
+
+
+def fit_size(H, W, aspect, *, size=None, height=None, width=None, square=False, multiple=2):
+    """The delivered size of an (H, W) frame with sample aspect `aspect` (the A tag: 'num:den' or None; None and 0:0 count as 1:1 and
+    stay absent): (Ho, Wo, aspect_out), in integers and fractions only.  Exactly one selector: size=(Wo, Ho) - that size as
+    stated; height=N - Ho = N and Wo = W N / H, times num / den when `square` (the samples become square: a 2880 x 1920 A32:27 frame at
+    height 1080 is 1920 x 1080), rounded to the nearest multiple of `multiple` (ties up, at least `multiple`); width=N - the mirror.
+    aspect_out is '1:1' when `square`; otherwise the input's aspect times (W Ho) / (H Wo), reduced, so that the display aspect survives
+    the rounding (an unknown aspect - no tag, 0:0 - stays as it is).  ValueError: no or two selectors, non-positive
+    numbers, an axis ratio outside [1/8, 8] (ops.resample's range), `square` with size= (the user states the size: no aspect arithmetic
+    applies)."""
+    given = [name for name, v in (('size', size), ('height', height), ('width', width)) if v is not None]
+    if len(given) != 1:
+        raise ValueError(f'exactly one of size=, height= and width= selects the delivered size, got {given or "none"}')
+    H, W, multiple = int(H), int(W), int(multiple)
+    if H < 1 or W < 1 or multiple < 1:
+        raise ValueError(f'a frame and the multiple are positive, got {H} x {W} and multiple {multiple}')
+    sar = _aspect_fraction(aspect)
+    if size is not None:
+        if square:
+            raise ValueError('square applies to height= and width=: size= states both axes')
+        try:
+            Wo, Ho = (int(v) for v in size)
+        except (TypeError, ValueError):
+            raise ValueError(f'size is (Wo, Ho), got {size!r}') from None
+    elif height is not None:
+        Ho = int(height)
+        if Ho < 1:
+            raise ValueError(f'height must be positive, got {height}')
+        Wo = _round_to_multiple(Fraction(W * Ho, H) * (sar if square else 1), multiple)
+    else:
+        Wo = int(width)
+        if Wo < 1:
+            raise ValueError(f'width must be positive, got {width}')
+        Ho = _round_to_multiple(Fraction(H * Wo, W) / (sar if square else 1), multiple)
+    if Ho < 1 or Wo < 1:
+        raise ValueError(f'the delivered size must be positive, got {Wo} x {Ho}')
+    for name, i, o in (('height', H, Ho), ('width', W, Wo)):
+        if i > 8 * o or o > 8 * i:
+            raise ValueError(f'the {name} ratio {i} / {o} is outside [1/8, 8]')
+    if square:
+        return Ho, Wo, '1:1'
+    unknown = aspect is None or not any(int(v) for v in str(aspect).split(':'))
+    if unknown or Fraction(W * Ho, H * Wo) == 1:
+        return Ho, Wo, aspect  # as written; an unknown aspect (no tag, 0:0) stays unknown
+    out = sar * Fraction(W * Ho, H * Wo)
+    return Ho, Wo, f'{out.numerator}:{out.denominator}'
 
 
 def _host_buffer(shape):
@@ -359,7 +429,7 @@ def resolve_field_order(deinterlace, field_order, reader):
 
 def restore_y4m(net, src, dst, *, matrix_in=None, matrix_out=None, chroma='bilinear', read_frames=8, on_chunk=None, stats=None, out_format=None,
                 siting_in='center', siting_out=None, deinterlace=None, field_order='auto', film_decimate=True, film_params=None,
-                **restorer_kwargs):
+                out_size=None, out_height=None, out_width=None, square_pixels=False, resample='lanczos3', **restorer_kwargs):
     """Restore a Y4M stream with `net` (an EDVR in eval mode, on the GPU) into a Y4M stream; returns the number of frames.  Call it under
     torch.no_grad().
 
@@ -401,8 +471,19 @@ def restore_y4m(net, src, dst, *, matrix_in=None, matrix_out=None, chroma='bilin
     is then written as `film_rate` of the input's, 4 / 5 of it ('30000:1001' -> '24000:1001'), and unchanged with film_decimate=False.
     film_params: a dict with any of nt, ct, mi, the thresholds of the definition.  stats also receives 'film_matches', 'film_combed',
     'film_dropped' and 'film_dropped_scores'; frames listed in 'film_combed' had no clean match and were deinterlaced from one field -
-    many of them mean the passage is video, not film: use 'field'."""
+    many of them mean the passage is video, not film: use 'field'.
+    Delivery size: out_size=(Wo, Ho), out_height=N or out_width=N (one of them; square_pixels with the last two) write
+    the result at `fit_size(s H, s W, A, ...)` instead of s W x s H, with that call's A tag: every restored float32 chunk goes through
+    ops.resample (resample: 'lanczos3' | 'bicubic' | 'bilinear') on the device before the one quantisation - a 720 x 480 A32:27 disc
+    with out_height=1080, square_pixels=True leaves as 1920 x 1080 A1:1, not as 2880 x 1920 for a second scaler to quantise again.
+    matrix_out then defaults by the delivered size and on_chunk receives the delivered chunk - what is written.  A delivered size
+    equal to s W x s H makes no launch; without a selector no call differs from those made before the arguments existed."""
     from .video import VideoRestorer
+    if resample not in RESAMPLE_KERNELS:
+        raise ValueError(f'resample must be one of {sorted(RESAMPLE_KERNELS)}, got {resample!r}')
+    fit = {k: v for k, v in (('size', out_size), ('height', out_height), ('width', out_width)) if v is not None}
+    if not fit and square_pixels:
+        raise ValueError('square_pixels needs out_height or out_width')
     if deinterlace is None:
         reader = src if isinstance(src, Y4MReader) else Y4MReader(src, formats=ALL_FORMATS)
     else:
@@ -426,7 +507,12 @@ def restore_y4m(net, src, dst, *, matrix_in=None, matrix_out=None, chroma='bilin
     vr = VideoRestorer(net, out_dtype=torch.float32, **restorer_kwargs)
     device = next(net.parameters()).device
     H, W = reader.height, reader.width
-    Ho, Wo = vr.scale * H, vr.scale * W
+    Ho, Wo, aspect = vr.scale * H, vr.scale * W, reader.aspect
+    delivered = None  # (Ho, Wo) where the restored chunks are resampled
+    if fit:
+        Hd, Wd, aspect = fit_size(Ho, Wo, reader.aspect, square=bool(square_pixels), **fit)
+        if (Hd, Wd) != (Ho, Wo):
+            delivered = Ho, Wo = Hd, Wd
     matrix_in = matrix_in or default_matrix(H, W)
     matrix_out = matrix_out or default_matrix(Ho, Wo)
     fps = double_rate(reader.fps) if first is not None and mode == 'field' else reader.fps
@@ -437,7 +523,7 @@ def restore_y4m(net, src, dst, *, matrix_in=None, matrix_out=None, chroma='bilin
             raise ValueError(f'film_params holds nt, ct and mi, got {sorted(unknown)}')
         if film_decimate:
             fps = film_rate(reader.fps)
-    writer = Y4MWriter(dst, Wo, Ho, fps, reader.aspect, reader.range, fmt_out, siting_out)
+    writer = Y4MWriter(dst, Wo, Ho, fps, aspect, reader.range, fmt_out, siting_out)
     row = len(FRAME) + writer.framesize
     marks = torch.tensor(list(FRAME), dtype=torch.uint8).to(device)
 
@@ -470,6 +556,8 @@ def restore_y4m(net, src, dst, *, matrix_in=None, matrix_out=None, chroma='bilin
             writer.write(pending[0])
 
     for out in vr.restore_chunks(decoded()):
+        if delivered is not None:
+            out = ops.resample(out, delivered, resample)
         buf = torch.empty((out.shape[0], row), dtype=torch.uint8, device=device)
         buf[:, :len(FRAME)] = marks
         if on_chunk is not None:

@@ -690,6 +690,25 @@ int edvr_imresize_bicubic_u8(const uint8_t *src, void *dst, int n, int H, int W,
 int edvr_imresize_bicubic_f32(const float *src, void *dst, int n, int H, int W, int64_t src_img_stride, int ho, int wo, double scale,
                               int antialiasing, int out_kind, edvr_stream_t stream);
 
+/* Separable resampling of float32 planes to a stated size (csrc/resample.hip; definition: DESIGN 4.21, R1 - R7 - the project's own, no
+ * reference): one launch resamples n images of c planes from (H, W) to (Ho, Wo), each axis with its own ratio in [1/8, 8], columns first,
+ * then rows.  The taps come from the caller as DEVICE tables (edvr_amd/resample.py: axis_table): fy int32 (Ho) / fx int32 (Wo) - the
+ * first tap of every output row / column - and wy float32 (Ho, Ty) / wx float32 (Wo, Tx), its weights, 1 <= T <= 49.  A pass is
+ *   out[j] = float32(sum_t double(w[j][t]) * double(in[clamp(first[j] + t, 0, I - 1)])),
+ * added in float64 in tap order from 0: the edge sample repeats, nothing else is clamped (Lanczos overshoots), and a result does not
+ * depend on the image's place in the batch.  The clamp is the kernel's: whatever the tables hold, no read leaves src.
+ * src (n, c, H, W): dense planes, images src_img_stride floats apart, any base alignment; dst (n, c, Ho, Wo) likewise with
+ * dst_img_stride (a slice of a longer tensor works on either side).  16-byte loads where the source rows start on 16-byte boundaries
+ * (W % 4 == 0, aligned pointer and stride), 16-byte stores where the output rows do; scalar accesses otherwise - the same bits.
+ * EDVR_ERR_ARG, nothing launched: a null pointer, n outside 1 ... 65535, c < 1, a T outside 1 ... 49, an axis ratio outside [1/8, 8], an
+ * image stride smaller than an image.  No allocation, no wait.
+ * edvr_resample_tile: the output tile (toh x tow) a workgroup of that call owns - tow is 64, toh falls from 32 as H / Ho grows toward 8,
+ * so that the source rows a tile's vertical taps reach fit 64 KB of LDS with the tables; pure host arithmetic. */
+int edvr_resample_tile(int H, int W, int Ho, int Wo, int Ty, int Tx, int *toh, int *tow);
+int edvr_resample_f32(const float *src, float *dst, int n, int c, int H, int W, int64_t src_img_stride, int Ho, int Wo,
+                      int64_t dst_img_stride, const int32_t *fy, const float *wy, int Ty, const int32_t *fx, const float *wx, int Tx,
+                      edvr_stream_t stream);
+
 /* "BD" downsampling on the device <- duf_downsample / generate_gaussian_kernel (basicsr/data/data_util.py:281-331; the LQ frames of
  * VideoTestDUFDataset, video_test_dataset.py:231-290): DUF's 13 x 13 Gaussian blur, sigma = 0.4 * scale, sampled at every scale-th
  * input sample, as ONE launch.  For scale s in {2, 3, 4}:

@@ -5,6 +5,13 @@
     ffmpeg -i hevc10.mp4 -strict -1 -f yuv4mpegpipe - | python scripts/restore_video.py - - --weights ... | ffmpeg -i - out.mkv
     ffmpeg -i in.mp4 -f yuv4mpegpipe - | python scripts/restore_video.py - - --weights ... --out-format 420p10 | ffmpeg -i - out.mkv
     ffmpeg -i tape.avi -f yuv4mpegpipe - | python scripts/restore_video.py - - --weights ... --deinterlace | ffmpeg -i - out.mp4
+    ffmpeg -i dvd.vob -f yuv4mpegpipe - | python scripts/restore_video.py - - --weights ... --deinterlace film --out-height 1080 --square-pixels | ffmpeg -i - out.mp4
+
+`--out-size WxH`, `--out-height N` or `--out-width N` deliver the result at that size instead of 4 W x 4 H: the float32 frames are
+resampled on the device (edvr_amd.ops.resample; `--resample lanczos3|bicubic|bilinear`) before the one quantisation, so no
+scaler behind the pipe quantises them again and the pipe carries the delivered bytes only.  With `--square-pixels` the sample aspect (the
+A tag) is folded into the size and A1:1 is written: a 720 x 480 A32:27 disc at `--out-height 1080` leaves as 1920 x 1080; without it the A
+tag is corrected for the rounding, so the display aspect stays.
 
 Interlaced input (It / Ib: tape, DVD, 1080i) needs `--deinterlace`: the fields are deinterlaced on the device (edvr_amd.ops.deinterlace,
 DESIGN 4.19) before anything else sees them and every field becomes a frame - the output is progressive at twice the frame rate;
@@ -92,6 +99,11 @@ def restore(args, log=log):
         if (siting_in, siting_out) != ('center', None):
             kwargs.update(siting_in=siting_in, siting_out=siting_out)
             log(f'{args.input}: chroma siting {siting_in} in, {resolve_siting(siting_out or siting_in, reader)} out')
+        fit = {k: v for k in ('out_size', 'out_height', 'out_width') for v in [getattr(args, k, None)] if v is not None}
+        if fit:
+            kwargs.update(fit, square_pixels=bool(getattr(args, 'square_pixels', False)), resample=getattr(args, 'resample', 'lanczos3'))
+            log(f'{args.output}: delivered at ' + ', '.join(f'{k} {v}' for k, v in fit.items()) + (', square pixels' if kwargs['square_pixels'] else '')
+                + f' ({kwargs["resample"]})')
         niqe_path, niqe_out, niqe_in = getattr(args, 'niqe', None), [], []
         if niqe_path:
             params = metrics.load_niqe_params(niqe_path)
@@ -221,6 +233,14 @@ def parse_args(argv=None):
                     help="the siting the output is encoded for (default: the input's)")
     ap.add_argument('--out-format', default=None, metavar='NAME',
                     help="the output's format: 420 | 422 | 444 with an optional depth p9 ... p16, e.g. 420p10 (default: the input's)")
+    ap.add_argument('--out-size', default=None, metavar='WxH', help='deliver at exactly this size (resampled on the device before the one quantisation)')
+    ap.add_argument('--out-height', type=int, default=None, metavar='N', help='deliver N rows; the width follows the frame (and, with --square-pixels, its A tag)')
+    ap.add_argument('--out-width', type=int, default=None, metavar='N', help='deliver N columns; the height follows')
+    ap.add_argument('--square-pixels', action='store_true',
+                    help='with --out-height / --out-width: fold the sample aspect (A tag) into the size and write A1:1 - a 720 x 480 A32:27 disc at '
+                         '--out-height 1080 leaves as 1920 x 1080')
+    ap.add_argument('--resample', default='lanczos3', choices=['lanczos3', 'bicubic', 'bilinear'], metavar='NAME',
+                    help='the filter of the delivery resampling: lanczos3 (default), bicubic or bilinear')
     ap.add_argument('--deinterlace', nargs='?', const='field', default=None, choices=['field', 'frame', 'film'],
                     help='deinterlace an interlaced stream (It / Ib) on the device first: field - every field becomes a frame, the rate doubles '
                          '(the default of a bare --deinterlace); frame - one frame per input frame, from its first field; film - undo 2:3 '
@@ -247,6 +267,19 @@ def parse_args(argv=None):
             args.out_format = yuv_format(args.out_format)[3]
         except ValueError as e:
             ap.error(f'--out-format: {e}')
+    if args.out_size is not None:
+        w, sep, h = args.out_size.lower().partition('x')
+        if not (sep and w.isascii() and h.isascii() and w.isdigit() and h.isdigit() and int(w) > 0 and int(h) > 0):
+            ap.error(f'--out-size is WxH, two positive integers, got {args.out_size!r}')
+        args.out_size = (int(w), int(h))
+    if sum(v is not None for v in (args.out_size, args.out_height, args.out_width)) > 1:
+        ap.error('--out-size, --out-height and --out-width exclude each other')
+    if any(v is not None and v < 1 for v in (args.out_height, args.out_width)):
+        ap.error('--out-height and --out-width are positive')
+    if args.square_pixels and args.out_height is None and args.out_width is None:
+        ap.error('--square-pixels needs --out-height or --out-width (--out-size states both axes)')
+    if args.resample != 'lanczos3' and args.out_size is None and args.out_height is None and args.out_width is None:
+        ap.error('--resample needs --out-size, --out-height or --out-width')
     if args.cuts is not None and args.scene_cuts is not None:
         ap.error('--cuts and --scene-cuts exclude each other')
     if args.min_shot is not None and args.scene_cuts is None:
