@@ -114,6 +114,8 @@ PROTOTYPES = {
     'edvr_deinterlace': (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i64, i64, i32, i32, vp]),
     'edvr_field_match': (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i64, i32, i32, i32, vp]),
     'edvr_field_weave': (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i64, i64, i32, vp]),
+    'edvr_bar_profile': (i32, [vp, vp, i32, i32, i32, i32, i32, i32, i64, vp]),
+    'edvr_yuv_crop': (i32, [vp, vp, i32, i32, i32, i32, i32, i32, i64, i64, i32, i32, i32, i32, vp]),
     'edvr_frame_sad_rgb_u8': (i32, [vp, vp, vp, i32, i32, i32, i64, vp]),
     'edvr_frame_sad_rgb_f32': (i32, [vp, vp, vp, i32, i32, i32, i64, vp]),
     'edvr_jpeg_roundtrip_u8': (i32, [vp, vp, vp, i32, i32, i32, i32, i64, i64, i32, vp]),

@@ -11,6 +11,7 @@ import weakref
 import torch
 
 from . import _lib
+from .bars import check_rect
 from ._lib import (ACT_LRELU, ACT_NONE, ACT_RELU, ACT_SIGMOID, CONV_AUTO, CONV_DIRECT, CONV_WINOGRAD, CONV_WINOGRAD_F4, CONV_WINOGRAD_F4S, OUT_NCHW,  # noqa: F401
                    OUT_PIXEL_SHUFFLE2)
 
@@ -2491,6 +2492,63 @@ def field_weave(yuv, H, W, format='420', *, first='top', frames, matches, prev=N
     _run('field_weave', lambda: _lib.check(_lib.lib().edvr_field_weave(_ptr(yuv), _ptr(prev), _ptr(out), _ptr(table), n, k, H, W, sx, sy, depth, stride,
                                                                        out_stride, DEINT_FIRST[first], _stream()), 'edvr_field_weave'),
          0, 2.0 * k * fs)
+    return out
+
+
+# ------------------------------------------------------------------------------------------------ bars (csrc/bars.hip)
+def bar_profile(yuv, H, W, format='420', *, out=None):
+    """How dark every row and column of every frame is, for letterbox / pillarbox detection (integers only), for all n
+    frames in ONE kernel launch behind a clear of the table.  yuv: uint8 (n, >= yuv_frame_size(H, W, format)) on the GPU, as field_match
+    takes it - stride(1) == 1, any row stride and base offset (`buf[:, 6:]` of a Y4MReader buffer), even ones above 8 bits.  Only luma
+    is read, every sample once.  Returns int64 (n, H + W) on the device: [:, :H] the row sums P (row y: the sum of its W samples, as
+    integers), [:, H:] the column sums Q.  Exact: a row does not depend on the batch it was computed in.  out: an int64 (n, H + W)
+    contiguous tensor to write into instead.  What the sums mean is host arithmetic: edvr_amd/bars.py (B2 - B6).  Bytes booked: the
+    luma plane of every frame once, and the table.  NotImplementedError for CPU tensors, ValueError for bad names, shapes and
+    layouts."""
+    fmt = yuv_format(format)
+    require_gpu(yuv, dtypes=(torch.uint8,))
+    H, W = int(H), int(W)
+    sx, sy, depth, _ = fmt
+    n, fs, stride = _yuv_batch(yuv, H, W, fmt, 'yuv')
+    if out is None:
+        out = torch.empty((n, H + W), dtype=torch.int64, device=yuv.device)
+    else:
+        require_gpu(out, dtypes=(torch.int64,))
+        if tuple(out.shape) != (n, H + W) or not out.is_contiguous():
+            raise ValueError(f'out is a contiguous int64 ({n}, {H + W}) tensor, got {tuple(out.shape)}')
+        if _overlaps(out, yuv):
+            raise ValueError('out overlaps the input')
+    _run('bar_profile', lambda: _lib.check(_lib.lib().edvr_bar_profile(_ptr(yuv), _ptr(out), n, H, W, sx, sy, depth, stride, _stream()),
+                                           'edvr_bar_profile'), 0, float(n) * (H * W * (2 if depth > 8 else 1) + 8 * (H + W)))
+    return out
+
+
+def yuv_crop(yuv, H, W, format='420', *, rect, out=None):
+    """The rect (y0, x0, h, w) of every frame, all three planes, in ONE launch: luma [y0, y0 + h) x [x0, x0 + w) and
+    the chroma rects (y0 >> sy, x0 >> sx, h >> sy, w >> sx), as frames of yuv_frame_size(h, w, format) bytes.  yuv: uint8 (n, >=
+    yuv_frame_size(H, W, format)) on the GPU, as bar_profile takes it.  The rect lies inside the frame, on the chroma steps (rows in
+    multiples of 1 << sy, columns of 1 << sx: chroma siting and field parity survive exactly) and is not empty.  Returns uint8
+    (n, yuv_frame_size(h, w, format)).  out: a uint8 (n, >= that) batch to write into instead, stride(1) == 1, any row stride and base
+    offset (`buf[:, 6:]`), even ones above 8 bits; bytes outside the frames are left alone; it must not overlap the input.  Bytes booked:
+    every output byte read once and written once.  NotImplementedError for CPU tensors; ValueError for bad names, shapes and layouts,
+    a rect outside the frame, off the chroma steps or empty, and an `out` that overlaps the input."""
+    fmt = yuv_format(format)
+    require_gpu(yuv, dtypes=(torch.uint8,))
+    H, W = int(H), int(W)
+    sx, sy, depth, _ = fmt
+    n, fs, stride = _yuv_batch(yuv, H, W, fmt, 'yuv')
+    y0, x0, h, w = check_rect(rect, H, W, (1 << sy, 1 << sx))
+    if out is None:
+        out = torch.empty((n, _yuv_frame_bytes(h, w, sx, sy, depth)), dtype=torch.uint8, device=yuv.device)
+    else:
+        require_gpu(out, dtypes=(torch.uint8,))
+        if out.dim() == 2 and out.shape[0] != n:
+            raise ValueError(f'out holds {out.shape[0]} frames, the input {n}')
+    _, out_fs, out_stride = _yuv_batch(out, h, w, fmt, 'out')
+    if _overlaps(out, yuv):
+        raise ValueError('out overlaps the input')
+    _run('yuv_crop', lambda: _lib.check(_lib.lib().edvr_yuv_crop(_ptr(yuv), _ptr(out), n, H, W, sx, sy, depth, stride, out_stride, y0, x0, h, w,
+                                                                 _stream()), 'edvr_yuv_crop'), 0, 2.0 * n * out_fs)
     return out
 
 

@@ -13,7 +13,9 @@ here works on non-seekable streams (pipes), holds a bounded number of frames and
 copies keep the device busy while the host reads and writes.  Interlaced streams (It, Ib) are read on request and deinterlaced on the
 device, at field rate, before the colour conversion: `deinterlaced` / `restore_y4m(deinterlace=...)` around ops.deinterlace.
 The result can leave at a delivery size instead of s W x s H: `fit_size` / `restore_y4m(out_height=..., square_pixels=...)` around
-ops.resample, on the float32 frames before the one quantisation.
+ops.resample, on the float32 frames before the one quantisation.  Letterbox / pillarbox bars can be dropped before the
+network pays for them: `cropped` / `BarProbe` / `restore_y4m(crop=...)` around ops.yuv_crop and ops.bar_profile, on the byte planes
+between the deinterlace stage and the colour conversion.
 """
 import math
 from fractions import Fraction
@@ -21,6 +23,7 @@ from fractions import Fraction
 import torch
 
 from . import ops
+from .bars import DEFAULT_LIMIT, DEFAULT_MIN_BAR, DEFAULT_PROBE, BarDetector, aligned_rect, check_rect
 from .resample import KERNELS as RESAMPLE_KERNELS
 from .telecine import DEFAULT_MI, PulldownDetector
 
@@ -412,6 +415,79 @@ def inverse_telecined(pieces, H, W, format='420', first='top', decimate=True, nt
                      film_dropped_scores=[det.scores[i] for i in det.dropped])
 
 
+def cropped(pieces, H, W, format, rect):
+    """A generator over cropped device byte batches: every uint8 (k, >= framesize) batch of `pieces` goes through
+    ops.yuv_crop with rect = (y0, x0, h, w) and leaves as (k, yuv_frame_size(h, w, format)).  The rect is checked before the first
+    piece is fetched (ValueError: outside the frame, off the chroma steps, empty)."""
+    sx, sy = ops.yuv_format(format)[:2]
+    rect = check_rect(rect, int(H), int(W), (1 << sy, 1 << sx))
+    for piece in pieces:
+        yield ops.yuv_crop(piece, H, W, format, rect=rect)
+
+
+class BarProbe:
+    """restore_y4m(crop='auto') in front of the crop: profiles the byte batches of `pieces` as they arrive
+    (ops.bar_profile; the table copied to pinned memory behind the launch) and holds them; decide() returns the rect of B4 - B6 -
+    or None: nothing to believe - once `probe` non-blank frames have been seen, 4 probe frames are held or the stream has ended,
+    after ONE host wait where no held frame is blank: on the event behind the last table's copy.  replay() then yields the held
+    pieces and every later one as they are; the later ones are profiled too, without a wait, and finish() reads their tables:
+    `blank` (frame indices), `outside` (frames whose own box reaches beyond the rect: the picture grew after the probe) and `box`
+    (the probe's video box).  step, multiple: B5's, (rows, columns)."""
+
+    def __init__(self, pieces, H, W, format='420', *, probe=DEFAULT_PROBE, limit=DEFAULT_LIMIT, margin=0, min_bar=DEFAULT_MIN_BAR, step=1, multiple=1):
+        self.source, self.H, self.W, self.format = iter(pieces), int(H), int(W), format
+        self.probe, self.margin, self.min_bar, self.step, self.multiple = int(probe), margin, min_bar, step, multiple
+        self.detector = BarDetector(self.H, self.W, ops.yuv_format(format)[2], limit)
+        self.held, self.unread = [], []  # pieces not yet replayed; (pinned table, event) not yet read
+        self.rect = self.box = None
+        self.blank, self.outside = [], []
+
+    def _measure(self, piece):
+        table = ops.bar_profile(piece, self.H, self.W, self.format)
+        host = _host_buffer((piece.shape[0], 8 * (self.H + self.W))).view(torch.int64)
+        host.copy_(table, non_blocking=True)
+        event = None
+        if piece.is_cuda:
+            event = torch.cuda.Event()
+            event.record()
+        self.unread.append((host, event))
+
+    def _read(self):
+        for host, event in self.unread:
+            if event is not None:
+                event.synchronize()
+            self.detector.push(host)
+        self.unread = []
+
+    def decide(self):
+        held, look_at = 0, self.probe
+        for piece in self.source:
+            self._measure(piece)
+            self.held.append(piece)
+            held += piece.shape[0]
+            if held >= min(look_at, 4 * self.probe):
+                self._read()
+                if self.detector.nonblank >= self.probe or held >= 4 * self.probe:
+                    break
+                look_at = held + self.probe - self.detector.nonblank  # blank frames in front: at least that many more
+        self._read()
+        self.box = self.detector.box()
+        self.rect = aligned_rect(self.box, self.H, self.W, self.step, self.multiple, self.margin, self.min_bar)
+        return self.rect
+
+    def replay(self):
+        while self.held:
+            yield self.held.pop(0)
+        for piece in self.source:
+            self._measure(piece)
+            yield piece
+
+    def finish(self):
+        self._read()
+        self.blank = self.detector.blank
+        self.outside = self.detector.outside(self.rect) if self.rect is not None else []
+
+
 def resolve_field_order(deinterlace, field_order, reader):
     """restore_y4m's (deinterlace, field_order) -> (`first` of ops.deinterlace or None: nothing to do, mode).  'auto' follows the
     reader's I tag - It: 'top', Ib: 'bottom', anything else: progressive, passed through; 'tff' / 'bff' deinterlace whatever the tag says.
@@ -429,7 +505,8 @@ def resolve_field_order(deinterlace, field_order, reader):
 
 def restore_y4m(net, src, dst, *, matrix_in=None, matrix_out=None, chroma='bilinear', read_frames=8, on_chunk=None, stats=None, out_format=None,
                 siting_in='center', siting_out=None, deinterlace=None, field_order='auto', film_decimate=True, film_params=None,
-                out_size=None, out_height=None, out_width=None, square_pixels=False, resample='lanczos3', **restorer_kwargs):
+                out_size=None, out_height=None, out_width=None, square_pixels=False, resample='lanczos3', crop=None, crop_probe=DEFAULT_PROBE,
+                crop_limit=DEFAULT_LIMIT, crop_margin=0, crop_min_bar=DEFAULT_MIN_BAR, **restorer_kwargs):
     """Restore a Y4M stream with `net` (an EDVR in eval mode, on the GPU) into a Y4M stream; returns the number of frames.  Call it under
     torch.no_grad().
 
@@ -477,7 +554,21 @@ def restore_y4m(net, src, dst, *, matrix_in=None, matrix_out=None, chroma='bilin
     ops.resample (resample: 'lanczos3' | 'bicubic' | 'bilinear') on the device before the one quantisation - a 720 x 480 A32:27 disc
     with out_height=1080, square_pixels=True leaves as 1920 x 1080 A1:1, not as 2880 x 1920 for a second scaler to quantise again.
     matrix_out then defaults by the delivered size and on_chunk receives the delivered chunk - what is written.  A delivered size
-    equal to s W x s H makes no launch; without a selector no call differs from those made before the arguments existed."""
+    equal to s W x s H makes no launch; without a selector no call differs from those made before the arguments existed.
+    Bars: crop - None, a rect (y0, x0, h, w) of the progressive frames the deinterlace / film stage emits, or 'auto' - drops
+    letterbox / pillarbox bars on the byte planes, between that stage and the decode (`cropped`: ops.yuv_crop): everything after sees
+    an h x w video - the decode, the restorer with all its arguments (`cuts` indices are unchanged), fit_size(s h, s w, A, ...), the
+    matrix defaults, the header.  A is copied: the samples keep their shape.  A rect is on the format's chroma steps and, unless
+    pad_mode is given, h and w are multiples of the restorer's size multiple: ValueError before anything is launched or written.
+    'auto' (`BarProbe`): the pieces are profiled as they arrive (ops.bar_profile) and held until crop_probe frames that are not blank
+    have been seen (or 4 crop_probe frames are held, or the stream ends); the rect is then decided from their common box (bars.py:
+    crop_limit - the 8-bit level up to which a row or column's mean counts as dark; crop_margin - samples taken off each side that has
+    a bar; crop_min_bar - an axis that would lose fewer samples is left alone), aligned inward to the chroma steps and the size multiple
+    (the chroma steps alone with pad_mode), and the held pieces are replayed - the one host wait.  A rect with an axis under half the
+    frame's is not believed: nothing is cropped.  Later pieces are profiled without a wait; stats receives 'crop' (the rect or None),
+    'crop_box' (the probe's box), 'bars_blank' and 'bars_outside' - frames whose own picture reaches beyond the rect: the picture
+    grew after the probe, use scripts/detect_bars.py and give the rect.  A rect equal to the whole frame makes no launch; with
+    crop=None no call differs from those made before the argument existed."""
     from .video import VideoRestorer
     if resample not in RESAMPLE_KERNELS:
         raise ValueError(f'resample must be one of {sorted(RESAMPLE_KERNELS)}, got {resample!r}')
@@ -504,17 +595,16 @@ def restore_y4m(net, src, dst, *, matrix_in=None, matrix_out=None, chroma='bilin
     # (no keyword at 'center': the calls of every caller and stand-in that predates the argument)
     kw_in = {} if siting_in == 'center' else {'siting': siting_in}
     kw_out = {} if siting_out == 'center' else {'siting': siting_out}
+    if crop is not None:
+        if crop != 'auto':
+            crop = check_rect(crop, reader.height, reader.width, tuple(1 << s for s in reversed(reader.subsampling)))
+        if isinstance(crop_probe, bool) or not isinstance(crop_probe, int) or crop_probe < 1:
+            raise ValueError(f'crop_probe is a number of frames, at least 1, got {crop_probe!r}')
+        aligned_rect((0, 1, 0, 1), 1, 1, margin=crop_margin, min_bar=crop_min_bar)  # their argument errors now
+        BarDetector(reader.height, reader.width, ops.yuv_format(fmt_in)[2], crop_limit)  # ... and the limit's
     vr = VideoRestorer(net, out_dtype=torch.float32, **restorer_kwargs)
     device = next(net.parameters()).device
     H, W = reader.height, reader.width
-    Ho, Wo, aspect = vr.scale * H, vr.scale * W, reader.aspect
-    delivered = None  # (Ho, Wo) where the restored chunks are resampled
-    if fit:
-        Hd, Wd, aspect = fit_size(Ho, Wo, reader.aspect, square=bool(square_pixels), **fit)
-        if (Hd, Wd) != (Ho, Wo):
-            delivered = Ho, Wo = Hd, Wd
-    matrix_in = matrix_in or default_matrix(H, W)
-    matrix_out = matrix_out or default_matrix(Ho, Wo)
     fps = double_rate(reader.fps) if first is not None and mode == 'field' else reader.fps
     film = {}
     if first is not None and mode == 'film':
@@ -523,9 +613,6 @@ def restore_y4m(net, src, dst, *, matrix_in=None, matrix_out=None, chroma='bilin
             raise ValueError(f'film_params holds nt, ct and mi, got {sorted(unknown)}')
         if film_decimate:
             fps = film_rate(reader.fps)
-    writer = Y4MWriter(dst, Wo, Ho, fps, aspect, reader.range, fmt_out, siting_out)
-    row = len(FRAME) + writer.framesize
-    marks = torch.tensor(list(FRAME), dtype=torch.uint8).to(device)
 
     def batches():
         while True:
@@ -534,14 +621,45 @@ def restore_y4m(net, src, dst, *, matrix_in=None, matrix_out=None, chroma='bilin
                 return
             yield host.to(device, non_blocking=True)[:, len(FRAME):]
 
-    def decoded():
+    def progressive():
         if first is None:
-            stage = batches()
-        elif mode == 'film':
-            stage = inverse_telecined(batches(), H, W, fmt_in, first, bool(film_decimate), stats=film, **(film_params or {}))
+            return batches()
+        if mode == 'film':
+            return inverse_telecined(batches(), reader.height, reader.width, fmt_in, first, bool(film_decimate), stats=film, **(film_params or {}))
+        return deinterlaced(batches(), reader.height, reader.width, fmt_in, first, mode)
+
+    bars, stage = None, None  # the BarProbe of crop='auto'; the byte batches behind the crop (None: `progressive()`, as before the argument)
+    if crop is not None:
+        steps = tuple(1 << s for s in reversed(reader.subsampling))  # (rows, columns)
+        m = 1 if restorer_kwargs.get('pad_mode') is not None else vr.multiple
+        multiple = tuple(s * m // math.gcd(s, m) for s in steps)
+        if crop == 'auto':
+            # the header states the size: the rect is decided on the first frames, before anything is written
+            bars = BarProbe(progressive(), H, W, fmt_in, probe=crop_probe, limit=crop_limit, margin=crop_margin, min_bar=crop_min_bar,
+                            step=steps, multiple=multiple)
+            rect, stage = bars.decide(), bars.replay()
         else:
-            stage = deinterlaced(batches(), H, W, fmt_in, first, mode)
-        for yuv in stage:
+            rect, stage = crop, progressive()
+            if rect[2] % multiple[0] or rect[3] % multiple[1]:
+                raise ValueError(f'the crop {rect[2]} x {rect[3]} (rows x columns) is no multiple of {m}, the size the network takes: '
+                                 f'give pad_mode, or a rect that is')
+        if rect is not None and rect != (0, 0, H, W):
+            stage = cropped(stage, H, W, fmt_in, rect)
+            H, W = rect[2], rect[3]
+    Ho, Wo, aspect = vr.scale * H, vr.scale * W, reader.aspect
+    delivered = None  # (Ho, Wo) where the restored chunks are resampled
+    if fit:
+        Hd, Wd, aspect = fit_size(Ho, Wo, reader.aspect, square=bool(square_pixels), **fit)
+        if (Hd, Wd) != (Ho, Wo):
+            delivered = Ho, Wo = Hd, Wd
+    matrix_in = matrix_in or default_matrix(H, W)
+    matrix_out = matrix_out or default_matrix(Ho, Wo)
+    writer = Y4MWriter(dst, Wo, Ho, fps, aspect, reader.range, fmt_out, siting_out)
+    row = len(FRAME) + writer.framesize
+    marks = torch.tensor(list(FRAME), dtype=torch.uint8).to(device)
+
+    def decoded():
+        for yuv in (progressive() if stage is None else stage):
             if plain420:
                 yield ops.yuv420_to_rgb(yuv, H, W, matrix_in, reader.range, chroma, **kw_in)
             else:
@@ -580,6 +698,11 @@ def restore_y4m(net, src, dst, *, matrix_in=None, matrix_out=None, chroma='bilin
     if stats is not None:
         stats['frames'] = writer.frames_written
         stats.update(film)
+        if bars is not None:
+            bars.finish()
+            stats.update(crop=bars.rect, crop_box=bars.box, bars_blank=bars.blank, bars_outside=bars.outside)
+        elif crop is not None:
+            stats.update(crop=crop)
         if getattr(vr, 'cuts', None) is not None:
             stats.update(cuts=vr.cuts_found, cut_scores=vr.cut_scores, cut_mafd=vr.cut_mafd)
     return writer.frames_written

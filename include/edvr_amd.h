@@ -847,6 +847,29 @@ int edvr_field_match(const uint8_t *yuv, const uint8_t *prev, const uint8_t *pre
 int edvr_field_weave(const uint8_t *yuv, const uint8_t *prev, uint8_t *out, const int32_t *table, int n, int n_out, int H, int W, int sub_x,
                      int sub_y, int depth, int64_t in_stride, int64_t out_stride, int bottom_first, edvr_stream_t stream);
 
+/* Letterbox / pillarbox bars (csrc/bars.hip; definition: DESIGN 4.22, B1 - B7, integers only).  Replaces nothing in the reference: it is the
+ * `ffmpeg -vf cropdetect,crop` pass otherwise run in front of the pipe.  No bit-compatibility with cropdetect is claimed.  Frames are as
+ * edvr_field_match takes them: n frames of the format (sub_x, sub_y, depth), in_stride BYTES apart at any base address (both even for
+ * 16-bit samples).
+ *
+ * edvr_bar_profile: B1.  table: int64 (n, H + W), row i = the H row sums P_i[y] = sum over x of L_i[y, x] and then the W column sums
+ * Q_i[x] = sum over y of L_i[y, x] of frame i's LUMA plane L_i, samples as integers.  ONE kernel launch for all n frames behind a
+ * hipMemsetAsync of the table; every luma sample is read once and reduced along both axes in that pass; 64-bit integer atomics carry the
+ * totals, so a row does not depend on the batch it was computed in.  EDVR_ERR_ARG: null yuv / table, n < 1 or > 32767, H or W < 1, a
+ * depth outside 8 ... 16, a subsampling other than (1, 1), (1, 0), (0, 0), in_stride shorter than a frame with n > 1, an odd pointer or
+ * stride with 16-bit samples, H W > 2^29.  No allocation, no wait.
+ *
+ * edvr_yuv_crop: B7, ONE launch for all n frames, all three planes: output frame i is the luma rect (y0, x0, h, w) of input frame i and the
+ * chroma rects (y0 >> sub_y, x0 >> sub_x, h >> sub_y, w >> sub_x), in the layout of an h x w frame of the format; output frames lie
+ * out_stride bytes apart at any base address, bytes between them are not written.  out must not overlap the input.  A lane moves 16 bytes
+ * of an output row, whole where they lie inside it, byte by byte at its end; source rows start at any byte offset.  EDVR_ERR_ARG: null
+ * yuv / out, a rect that is empty, leaves the frame or is off the chroma steps (y0, h multiples of 1 << sub_y; x0, w of 1 << sub_x), an
+ * out_stride shorter than an h x w frame with n > 1, and the size / format / stride conditions above. */
+int edvr_bar_profile(const uint8_t *yuv, int64_t *table, int n, int H, int W, int sub_x, int sub_y, int depth, int64_t in_stride,
+                     edvr_stream_t stream);
+int edvr_yuv_crop(const uint8_t *yuv, uint8_t *out, int n, int H, int W, int sub_x, int sub_y, int depth, int64_t in_stride, int64_t out_stride,
+                  int y0, int x0, int h, int w, edvr_stream_t stream);
+
 /* Frame-to-frame change for scene-cut detection (csrc/shots.hip; definition: DESIGN 4.13).  The bytes R, G, B of a pixel are the input's
  * own (_u8: x (n, H, W, 3)) or its tensor2img bytes (_f32: x (n, 3, H, W); clamp to [0, 1], x 255, round half to even, NaN -> 0); in
  * integers Y8 = ((66 R + 129 G + 25 B + 128) >> 8) + 16, and

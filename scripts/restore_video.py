@@ -13,6 +13,12 @@ scaler behind the pipe quantises them again and the pipe carries the delivered b
 A tag) is folded into the size and A1:1 is written: a 720 x 480 A32:27 disc at `--out-height 1080` leaves as 1920 x 1080; without it the A
 tag is corrected for the rounding, so the display aspect stays.
 
+`--crop auto` drops letterbox / pillarbox bars on the device, on the bytes as decoded, before the network pays for them
+(edvr_amd.ops.bar_profile / yuv_crop): the rect is decided on the first `--crop-probe` frames that are not blank, aligned
+inward to the chroma steps and the network's size multiple, and everything after - the restorer, `--out-height`, the matrix defaults -
+sees the picture alone; the A tag is kept.  `--crop W:H:X:Y` (ffmpeg's order) gives the rect; `scripts/detect_bars.py IN` prints one
+for a whole stream, for films whose picture grows after the first minute.  `--bars-json FILE` writes what was found.
+
 Interlaced input (It / Ib: tape, DVD, 1080i) needs `--deinterlace`: the fields are deinterlaced on the device (edvr_amd.ops.deinterlace,
 DESIGN 4.19) before anything else sees them and every field becomes a frame - the output is progressive at twice the frame rate;
 `--deinterlace frame` keeps the rate (one frame per input frame, from its first field).  `--field-order tff|bff` overrides a wrong
@@ -64,6 +70,7 @@ def restore(args, log=log):
     from edvr_amd import EDVR
     from edvr_amd.optim import load_network
     from edvr_amd import metrics, ops
+    from edvr_amd.bars import crop_string
     from edvr_amd.y4m import ALL_FORMATS, FRAME, Y4MReader, default_matrix, resolve_field_order, resolve_siting, restore_y4m
     device = torch.device('cuda', int(os.environ.get('LOCAL_RANK', 0)))
     torch.cuda.set_device(device)
@@ -104,6 +111,10 @@ def restore(args, log=log):
             kwargs.update(fit, square_pixels=bool(getattr(args, 'square_pixels', False)), resample=getattr(args, 'resample', 'lanczos3'))
             log(f'{args.output}: delivered at ' + ', '.join(f'{k} {v}' for k, v in fit.items()) + (', square pixels' if kwargs['square_pixels'] else '')
                 + f' ({kwargs["resample"]})')
+        if getattr(args, 'crop', None) is not None:
+            kwargs.update(crop=args.crop, crop_probe=args.crop_probe, crop_limit=args.crop_limit, crop_margin=args.crop_margin)
+            log(f'{args.input}: bars ' + (f'detected on the first {args.crop_probe} frames that are not blank (limit {args.crop_limit})'
+                                         if args.crop == 'auto' else f'cropped to {crop_string(args.crop)}'))
         niqe_path, niqe_out, niqe_in = getattr(args, 'niqe', None), [], []
         if niqe_path:
             params = metrics.load_niqe_params(niqe_path)
@@ -135,6 +146,8 @@ def restore(args, log=log):
             report_cuts(args, stats, log)
         if 'film_matches' in stats:
             report_film(args, stats, log)
+        if 'crop' in stats:
+            report_bars(args, stats, log)
         if niqe_path:
             report_niqe(args, niqe_out, niqe_in, log)
     finally:
@@ -167,6 +180,26 @@ def report_film(args, stats, log=log):
         record = {'frames_in': len(m), 'frames': stats['frames'], 'matches': ['cp'[v] for v in m], 'combed': stats['film_combed'],
                   'dropped': stats['film_dropped'], 'dropped_scores': stats['film_dropped_scores']}
         with open(args.film_json, 'w') as f:
+            json.dump(record, f, indent=1)
+
+
+def report_bars(args, stats, log=log):
+    """The rect a run cropped to; with crop='auto' also the probe's box, the blank frames and - a warning - the frames whose picture reaches
+    beyond the rect; with --bars-json all of it."""
+    from edvr_amd.bars import crop_string
+    rect, outside = stats['crop'], stats.get('bars_outside', [])
+    if rect is None:
+        log(f'{args.input}: no bars cropped' + (f' (the box {stats["crop_box"]} is under half the frame: not believed)' if stats.get('crop_box') else ''))
+    else:
+        log(f'{args.input}: cropped to {crop_string(rect)} (W:H:X:Y)' + (f', {len(stats["bars_blank"])} blank frames' if stats.get('bars_blank') else ''))
+    if outside:
+        log(f'{args.input}: WARNING: the picture of {len(outside)} frames (from frame {outside[0]}) reaches beyond the rect - it grew after the '
+            f'probe; run scripts/detect_bars.py on the whole stream and give its rect with --crop')
+    if getattr(args, 'bars_json', None):
+        import json
+        record = {'frames': stats['frames'], 'crop': None if rect is None else crop_string(rect), 'rect': rect, 'box': stats.get('crop_box'),
+                  'blank': stats.get('bars_blank', []), 'outside': outside}
+        with open(args.bars_json, 'w') as f:
             json.dump(record, f, indent=1)
 
 
@@ -241,6 +274,14 @@ def parse_args(argv=None):
                          '--out-height 1080 leaves as 1920 x 1080')
     ap.add_argument('--resample', default='lanczos3', choices=['lanczos3', 'bicubic', 'bilinear'], metavar='NAME',
                     help='the filter of the delivery resampling: lanczos3 (default), bicubic or bilinear')
+    ap.add_argument('--crop', default=None, metavar='auto|W:H:X:Y',
+                    help="drop letterbox / pillarbox bars on the device before anything else sees them: auto - detected on the first frames; "
+                         "W:H:X:Y - that rect, in ffmpeg's crop order (scripts/detect_bars.py prints one for a whole stream)")
+    ap.add_argument('--crop-probe', type=int, default=48, metavar='N', help='with --crop auto: decide on the first N frames that are not blank')
+    ap.add_argument('--crop-limit', type=int, default=24, metavar='L',
+                    help='with --crop auto: a row or column whose mean luma does not exceed the 8-bit level L is dark (default 24)')
+    ap.add_argument('--crop-margin', type=int, default=0, metavar='G', help='with --crop auto: G more samples off every side that has a bar')
+    ap.add_argument('--bars-json', default=None, metavar='FILE', help='with --crop: write the rect, the box, the blank and the outside frames there')
     ap.add_argument('--deinterlace', nargs='?', const='field', default=None, choices=['field', 'frame', 'film'],
                     help='deinterlace an interlaced stream (It / Ib) on the device first: field - every field becomes a frame, the rate doubles '
                          '(the default of a bare --deinterlace); frame - one frame per input frame, from its first field; film - undo 2:3 '
@@ -280,6 +321,20 @@ def parse_args(argv=None):
         ap.error('--square-pixels needs --out-height or --out-width (--out-size states both axes)')
     if args.resample != 'lanczos3' and args.out_size is None and args.out_height is None and args.out_width is None:
         ap.error('--resample needs --out-size, --out-height or --out-width')
+    if args.crop is not None and args.crop != 'auto':
+        from edvr_amd.bars import parse_crop
+        try:
+            args.crop = parse_crop(args.crop)
+        except ValueError as e:
+            ap.error(f'--crop: {e}')
+        if args.crop[2] < 1 or args.crop[3] < 1:
+            ap.error('--crop: W and H are positive')
+    if args.crop != 'auto' and (args.crop_probe != 48 or args.crop_limit != 24 or args.crop_margin != 0):
+        ap.error('--crop-probe, --crop-limit and --crop-margin need --crop auto')
+    if args.crop_probe < 1 or not 0 <= args.crop_limit <= 255 or args.crop_margin < 0:
+        ap.error('--crop-probe is at least 1, --crop-limit an 8-bit level 0 ... 255, --crop-margin at least 0')
+    if args.bars_json is not None and args.crop is None:
+        ap.error('--bars-json needs --crop')
     if args.cuts is not None and args.scene_cuts is not None:
         ap.error('--cuts and --scene-cuts exclude each other')
     if args.min_shot is not None and args.scene_cuts is None:
